@@ -8,7 +8,20 @@ is already resident in HBM:  to_minmax -> attack (N x [model fwd + input-bwd, fu
 revert_minmax -> target-model forward -> sigmoid / threshold.  After the K timed steps the per-utterance scores are
 aggregated once (RCCL all-reduce + all-gather when N > 1) inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3}] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (utterances/s), `ms_per_step` and the
+fields read off the timed region itself (`roofline` from its in-loop brackets, `adv_eval`, `ms_each_step`).  `--full` adds
+everything that takes runs of its own, after the timed region: the live `rocprofv3 --pmc` traffic passes, the legs listed
+under --no-extras (shipped path without brackets, one batch in flight, model-side and per-family step rooflines, the
+shipped loop end to end, the cold regime, CW without its early stop) and the CPU baseline; --no-extras / --no-cpu-baseline
+drop parts of it again.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed (rank 0): per attack the last step's
+adversarial waveforms `<attack>_adv.npy` (B, T) and its scores / hard labels `<attack>_scores.npy` / `<attack>_labels.npy`,
+and the end-of-run aggregate over all timed steps and ranks `<attack>_all_scores.npy` / `<attack>_all_labels.npy`; float32,
+at most 64 MB in all (waveform rows beyond the budget: a fixed seeded sample, its row indices in `<attack>_adv_rows.npy`).
+Inputs, weights and random starts are seeded, so the same arguments give the same inputs in every run.
 
 With N > 1 and no launcher in the environment (WORLD_SIZE unset) the script starts its own N ranks — it re-executes
 itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` — so both
@@ -27,7 +40,7 @@ still one batch through the whole body; K steps are timed between the same barri
 W warm-up steps let every stream capture its graph (a graph is captured at the second sight of a workload).
 
 `roofline` prices the dominant hand-written kernel of the workload with HIP events recorded on its launch stream
-inside the timed region; `cpu_baseline` times the CPU oracle ("port": oracle/attacks.py, torch CPU ops in the
+inside the timed region; `cpu_baseline` (--full) times the CPU oracle ("port": oracle/attacks.py, torch CPU ops in the
 reference's order) on a bounded sample of the same workload on this box's host cores (rank 0, N = 1 only)."""
 import argparse
 import json
@@ -116,10 +129,15 @@ def parse(argv=None):
     p.add_argument("--in-flight", type=int, default=None,
                    help="batches in flight, each on its own stream (default: 2 for --config 1 and 2, 1 for --config 3 whose CW "
                         "loop is driven from the host)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what takes runs of its own after the timed region: the extras below and the CPU baseline "
+                        "(N = 1 only); a plain run measures the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the timed path's outputs of its last step (and the end-of-run aggregate) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the legs after the timed region (graph-replay timing, model-side roofline, cold-regime and "
-                        "live PMC traffic of the priced kernel); N = 1 only anyway")
+                   help="with --full: skip the legs after the timed region (graph-replay timing, model-side roofline, "
+                        "cold-regime and live PMC traffic of the priced kernel); N = 1 only anyway")
     p.add_argument("--cpu-threads", type=int, default=0, help="host threads for the CPU baseline (0 = swept default)")
     p.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                    help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only for single-GPU rehearsals)")
@@ -354,6 +372,41 @@ def measured_traffic(entry_point: str, B: int):
     return row["hbm_bytes_per_launch"], f"profiles/hbm_traffic.json: {table['source']}"
 
 
+DUMP_BUDGET = 64 * 10**6       # bytes of all --dump-outputs files together
+
+
+def dump_outputs(directory, last, gathered):
+    """--dump-outputs: `last` = {attack: (adv, scores, labels)} host arrays of the last timed step, `gathered` = the
+    end-of-run aggregate per attack (evaluation.aggregate_across_ranks).  Everything as float32; the waveforms get what the
+    score arrays leave of DUMP_BUDGET, split evenly over the attacks, and a fixed seeded sample of rows when they exceed it."""
+    import numpy as np
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    files = {}
+    for m, (adv, scores, labels) in last.items():
+        all_pred, all_label = gathered[m][0], gathered[m][1]
+        files[f"{m}_scores"] = np.asarray(scores, dtype=np.float32)
+        files[f"{m}_labels"] = np.asarray(labels, dtype=np.float32)
+        files[f"{m}_all_scores"] = np.asarray(all_pred, dtype=np.float32)
+        files[f"{m}_all_labels"] = np.asarray(all_label, dtype=np.float32)
+    header = 256                                                        # room per file for its .npy header (6 files per attack)
+    left = DUMP_BUDGET - sum(a.nbytes for a in files.values()) - header * 6 * len(last)
+    for m, (adv, _, _) in last.items():
+        adv = np.asarray(adv, dtype=np.float32)
+        share = left // len(last)
+        if adv.nbytes > share:
+            keep = max(1, share // (adv.shape[1] * 4 + 4))              # + 4: the row index kept beside each row
+            rows = np.sort(np.random.default_rng(0).choice(adv.shape[0], size=keep, replace=False))
+            adv = adv[rows]
+            files[f"{m}_adv_rows"] = rows.astype(np.float32)
+        files[f"{m}_adv"] = adv
+    total = sum(a.nbytes + header for a in files.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    for name, a in files.items():
+        np.save(out / f"{name}.npy", a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -413,9 +466,10 @@ def main():
     one_lane = _Lanes(device, 1)
     counter = [0]                                    # steps queued so far: consecutive steps alternate streams across calls
 
-    def timed_loop(first, last, lanes=lanes):
+    def timed_loop(first, last, lanes=lanes, keep_last=None):
         """The loop body for batches [first, last): per attack the scores, labels and a per-step event mark (recorded on the
-        stream the step ran on); returns after every stream's work has been ordered in front of the caller's stream."""
+        stream the step ran on); returns after every stream's work has been ordered in front of the caller's stream.
+        keep_last (a dict): filled with each attack's (adversarial batch, scores, labels) of the last step."""
         out = {m: ([], [], []) for m, _ in attacks}
         correct = {m: [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)] for m, _ in attacks}
         marks = [torch.cuda.Event(enable_timing=True)]
@@ -430,10 +484,14 @@ def main():
                     out[m][0].append(p), out[m][1].append(l), out[m][2].append(by)
                     correct[m][lane] += (l == by.int()).sum()
                     lanes.keep(p, l)
+                    if keep_last is not None:
+                        keep_last[m] = (adv, p, l)
                     marks.append(torch.cuda.Event(enable_timing=True))
                     marks[-1].record()
         for m in correct:
             lanes.keep(*correct[m])
+        if keep_last:
+            lanes.keep(*(v[0] for v in keep_last.values()))
         lanes.join()
         return out, {m: torch.stack(v).sum() for m, v in correct.items()}, marks
 
@@ -465,12 +523,16 @@ def main():
     # graph_ok: the brackets sit on launches OUTSIDE the captured model part (update step, random start, min-max), so the
     # iteration keeps replaying from its graph — the timed region runs the shipped launch path
     hip_ops.start_profile(*PROFILED, graph_ok=True)
+    last = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    out, correct, marks = timed_loop(args.warmup, n_batches)
+    out, correct, marks = timed_loop(args.warmup, n_batches, keep_last=last)
     gathered = aggregate(out, correct, args.steps)
     sync_all()
     elapsed = time.perf_counter() - t0
     kernel_ms = hip_ops.stop_profile()
+    if rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, {m: tuple(t.cpu().numpy() for t in v) for m, v in last.items()}, gathered)
+    del last
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -484,7 +546,7 @@ def main():
         avg_ms = sum(step_ms) / len(step_ms)
         launch_bytes = bytes_per_sample * B * T
         achieved = launch_bytes / (avg_ms * 1e-3) / 1e9
-        extras = world == 1 and not args.no_extras
+        extras = world == 1 and args.full and not args.no_extras
         traffic, provenance = live_traffic(entry, B) if extras else (None, "")
         if traffic is None:
             t2, p2 = measured_traffic(entry, B)
@@ -737,7 +799,7 @@ def main():
                 cw["without_early_stop"] = {"iterations": atk_cw.steps, "ms_per_batch": round(full_ms, 1),
                                             "ms_per_iteration": round(full_ms / atk_cw.steps, 3),
                                             "utterances_per_s": round(B / (full_ms * 1e-3), 2)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_threads, cw_iters)
         print(json.dumps(line), flush=True)
 

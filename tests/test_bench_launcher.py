@@ -32,6 +32,39 @@ def test_defaults_and_workload_table():
     assert AttackEnum.PGD40_eps003.value[1] == {"eps": 0.003, "steps": 40}
 
 
+def test_plain_run_is_the_headline_and_dumps_fit_the_budget(tmp_path):
+    """A plain run takes no extra legs (--full adds them); --dump-outputs writes float32 arrays, at most 64 MB in all, a
+    fixed seeded sample of waveform rows when a batch is larger than that."""
+    import numpy as np
+
+    import bench
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path), "--steps", "7"])
+    assert a.full and a.dump_outputs == str(tmp_path) and a.steps == 7
+    rng = np.random.default_rng(3)
+    for B, attacks in ((128, ("PGD40_eps003",)), (64, ("FGSM", "CW")), (512, ("PGD40_eps003",))):
+        out = tmp_path / f"b{B}_{len(attacks)}"
+        last = {m: (rng.standard_normal((B, bench.T), dtype=np.float32), rng.random(B, dtype=np.float32),
+                    (rng.random(B) > 0.5).astype(np.int32)) for m in attacks}
+        gathered = {m: (np.tile(v[1], 3), np.tile(v[2], 3)) for m, v in last.items()}
+        bench.dump_outputs(out, last, gathered)
+        again = tmp_path / "again"
+        bench.dump_outputs(again, last, gathered)
+        assert sum(p.stat().st_size for p in out.iterdir()) <= bench.DUMP_BUDGET
+        for p in out.iterdir():
+            x = np.load(p)
+            assert x.dtype == np.float32 and np.array_equal(x, np.load(again / p.name)), p.name
+        for m, (adv, scores, labels) in last.items():
+            got = np.load(out / f"{m}_adv.npy")
+            rows = out / f"{m}_adv_rows.npy"
+            want = adv[np.load(rows).astype(np.int64)] if rows.exists() else adv
+            assert rows.exists() == (B * bench.T * 4 * len(attacks) > bench.DUMP_BUDGET)
+            assert np.array_equal(got, want)
+            assert np.array_equal(np.load(out / f"{m}_scores.npy"), scores)
+            assert np.array_equal(np.load(out / f"{m}_all_labels.npy"), np.tile(labels, 3).astype(np.float32))
+
+
 @pytest.mark.timeout(300)
 def test_gpus_2_without_launcher_starts_two_ranks(tmp_path):
     """On this GPU-less box both ranks must come up (so the re-exec happened) and stop loudly: no CPU fallback."""

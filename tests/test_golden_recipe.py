@@ -1,46 +1,46 @@
-"""The committed fixture recipe runs END TO END in one process and reproduces every committed fixture bit for bit.
+"""The committed fixture recipe (tests/golden/generate_golden.py): what of it can run without the reference's sources.
 
 VERDICT r05 (What's weak 9): `generate_golden.main()` used to die half-way — a generator left its inert `torchaudio`
 module in sys.modules and a later `import transformers.audio_utils` refused the spec-less module — so three fixtures could
-only be regenerated in a fresh process.  The stand-ins now live inside `_stand_ins()`.  Needs the reference tree, which
-exists only in the build container: skipped elsewhere (the GPU box never regenerates fixtures).
+only be regenerated in a fresh process.  The stand-ins now live inside `_stand_ins()`.  Most generators import the
+reference itself, which is not part of this repository, so the suite regenerates only the fixture built from third-party
+code alone and checks the stand-ins' host logic.
 """
-import os
-import subprocess
 import sys
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 GOLDEN = ROOT / "tests" / "golden"
 
 
-@pytest.mark.skipif(not Path("/root/reference").exists(), reason="the reference tree is only mounted in the build container")
-def test_whole_recipe_in_one_process_reproduces_the_committed_fixtures(tmp_path):
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    run = subprocess.run([sys.executable, str(GOLDEN / "generate_golden.py"), "--out", str(tmp_path)], cwd=ROOT, env=env,
-                         capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
-    committed = sorted(p.name for p in GOLDEN.glob("*.npz"))
-    assert sorted(p.name for p in tmp_path.glob("*.npz")) == committed      # every generator of main() ran
-    for name in committed:
-        new, old = np.load(tmp_path / name, allow_pickle=True), np.load(GOLDEN / name, allow_pickle=True)
-        assert set(new.files) == set(old.files), name
-        for k in old.files:
-            assert new[k].shape == old[k].shape and new[k].dtype == old[k].dtype, (name, k)
-            assert new[k].tobytes() == old[k].tobytes(), f"{name}:{k} differs from the committed fixture"
-    assert (tmp_path / "datasets_listing.json").read_text() == (GOLDEN / "datasets_listing.json").read_text()
-
-
-def test_stand_in_modules_do_not_outlive_their_generator():
-    """Host logic of the fix, no reference needed: whatever a generator registers is gone (or restored) afterwards."""
+def _recipe():
     sys.path.insert(0, str(GOLDEN))
     try:
         import generate_golden as gg
     finally:
         sys.path.pop(0)
+    return gg
+
+
+def test_reference_free_generator_reproduces_its_committed_fixture(tmp_path, monkeypatch):
+    """gen_frontends_batch_floor (transformers.audio_utils + scipy, no reference) rebuilds frontends_batch_floor.npz bit for
+    bit, into a scratch directory (nothing under tests/ is touched)."""
+    gg = _recipe()
+    monkeypatch.setattr(gg, "OUT", tmp_path)
+    gg.gen_frontends_batch_floor()
+    name = "frontends_batch_floor.npz"
+    new, old = np.load(tmp_path / name), np.load(GOLDEN / name)
+    assert set(new.files) == set(old.files)
+    for k in old.files:
+        assert new[k].shape == old[k].shape and new[k].dtype == old[k].dtype, k
+        assert new[k].tobytes() == old[k].tobytes(), f"{name}:{k} differs from the committed fixture"
+
+
+def test_stand_in_modules_do_not_outlive_their_generator():
+    """Host logic of the fix, no reference needed: whatever a generator registers is gone (or restored) afterwards."""
+    gg = _recipe()
     import types
     keep = types.ModuleType("soundfile")
     had = {k: sys.modules.get(k) for k in gg._STAND_IN_NAMES}

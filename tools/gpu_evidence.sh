@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -3 | tee "$O/tests.txt"
 cp gpurun_out/parity_record.json "$O/parity.json"
 for c in 1 2 3; do
-  python bench.py --config $c 2>/dev/null | grep '^{' | tail -1 > "$O/bench_c$c.json"
+  python bench.py --config $c --full 2>/dev/null | grep '^{' | tail -1 > "$O/bench_c$c.json"
   python -c "import json;d=json.load(open('$O/bench_c$c.json'));print('config $c', d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('through_loop',{}).get('value'))"
 done
 # kernel traces.  (a) ONE batch in flight: every kernel has the chip to itself - the per-kernel durations the rooflines are priced
