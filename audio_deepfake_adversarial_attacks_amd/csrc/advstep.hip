@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "advstep.h"
+#include "advstep_common.h"
 
 namespace {
 
@@ -47,11 +48,6 @@ __device__ __forceinline__ float min_nan(float a, float b) {
     if (a != a) return a;
     if (b != b) return b;
     return a < b ? a : b;
-}
-__device__ __forceinline__ float max_nan(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return a > b ? a : b;
 }
 
 __device__ __forceinline__ float fgsm_elem(float x, float g, float eps, float lo, float hi) {
@@ -1077,11 +1073,7 @@ __global__ __launch_bounds__(kBlock) void ce2_loss_grad_kernel(const float *__re
 // host-side helpers
 // ---------------------------------------------------------------------------------------------------------
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int tiles_per_row(int64_t T) { return (int)ceil_div(T, kTile); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 struct RowWs {
     float *p0;
@@ -1227,11 +1219,6 @@ inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
 
-#define ADV_REQUIRE(cond) \
-    do {                  \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
 // Launch a row kernel over all B rows in slabs of <= 65535 rows; `ARGS` may use `b0` (first row of the slab).
 #define ADV_LAUNCH_ROWS(KERNEL, VECFLAG, B, T, st, ...)                                          \
     do {                                                                                         \
@@ -1276,9 +1263,9 @@ size_t advstep_row_workspace_bytes(int64_t B, int64_t T) {
 
 int advstep_minmax_normalize_f32(const float *x, float *x01, float *mn, float *mx, int64_t B, int64_t T, void *ws,
                                  size_t ws_bytes, advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && x01 && mn && mx && x != x01);
+    ADVSTEP_REQUIRE(x && x01 && mn && mx && x != x01);
     RowWs w;
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
@@ -1292,9 +1279,9 @@ int advstep_minmax_normalize_f32(const float *x, float *x01, float *mn, float *m
 
 int advstep_minmax_revert_f32(const float *x01, const float *mn, const float *mx, float *out, int64_t B, int64_t T,
                               advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x01 && mn && mx && out);
+    ADVSTEP_REQUIRE(x01 && mn && mx && out);
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x01, out});
     ADV_LAUNCH_ROWS(minmax_revert_kernel, vec, B, T, st, x01 + b0 * T, mn + b0, mx + b0, out + b0 * T, T);
@@ -1303,25 +1290,25 @@ int advstep_minmax_revert_f32(const float *x01, const float *mn, const float *mx
 
 int advstep_fgsm_step_f32(const float *x, const float *grad, float *out, int64_t n, float eps, float lo, float hi,
                           advstep_stream_t stream) {
-    ADV_REQUIRE(n >= 0);
+    ADVSTEP_REQUIRE(n >= 0);
     if (n == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && grad && out);
+    ADVSTEP_REQUIRE(x && grad && out);
     return launch_flat<2>(x, grad, nullptr, out, n, FgsmOp{eps, lo, hi}, as_stream(stream));
 }
 
 int advstep_pgd_linf_init_noise_f32(const float *x, const float *noise, float *out, int64_t n, float lo, float hi,
                                     advstep_stream_t stream) {
-    ADV_REQUIRE(n >= 0);
+    ADVSTEP_REQUIRE(n >= 0);
     if (n == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && noise && out);
+    ADVSTEP_REQUIRE(x && noise && out);
     return launch_flat<2>(x, noise, nullptr, out, n, AddClampOp{lo, hi}, as_stream(stream));
 }
 
 int advstep_pgd_linf_init_philox_f32(const float *x, float *out, int64_t n, float eps, float lo, float hi,
                                      uint64_t seed, uint64_t offset, advstep_stream_t stream) {
-    ADV_REQUIRE(n >= 0);
+    ADVSTEP_REQUIRE(n >= 0);
     if (n == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && out);
+    ADVSTEP_REQUIRE(x && out);
     hipStream_t st = as_stream(stream);
     const bool vec = aligned16(x) && aligned16(out);
     const int64_t n4 = vec ? n / 4 : 0;
@@ -1344,18 +1331,18 @@ int advstep_pgd_linf_init_philox_f32(const float *x, float *out, int64_t n, floa
 
 int advstep_pgd_linf_step_f32(const float *adv, const float *grad, const float *orig, float *out, int64_t n,
                               float alpha, float eps, float lo, float hi, advstep_stream_t stream) {
-    ADV_REQUIRE(n >= 0);
+    ADVSTEP_REQUIRE(n >= 0);
     if (n == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(adv && grad && orig && out);
+    ADVSTEP_REQUIRE(adv && grad && orig && out);
     return launch_flat<3>(adv, grad, orig, out, n, PgdLinfOp{alpha, eps, lo, hi}, as_stream(stream));
 }
 
 int advstep_pgd_l2_init_noise_f32(const float *x, const float *normal, const float *r, float *out, int64_t B,
                                   int64_t T, float eps, float lo, float hi, void *ws, size_t ws_bytes,
                                   advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && normal && r && out);
+    ADVSTEP_REQUIRE(x && normal && r && out);
     RowWs w;
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
@@ -1370,10 +1357,10 @@ int advstep_pgd_l2_init_noise_f32(const float *x, const float *normal, const flo
 int advstep_pgd_l2_init_philox_f32(const float *x, float *out, int64_t B, int64_t T, float eps, float lo, float hi,
                                    uint64_t seed, uint64_t offset, void *ws, size_t ws_bytes,
                                    advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && out);
-    ADV_REQUIRE(B <= kMaxRowsPerLaunch);  // the Philox counter carries the absolute row index
+    ADVSTEP_REQUIRE(x && out);
+    ADVSTEP_REQUIRE(B <= kMaxRowsPerLaunch);  // the Philox counter carries the absolute row index
     RowWs w;
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
@@ -1405,9 +1392,9 @@ int advstep_pgd_l2_init_philox_f32(const float *x, float *out, int64_t B, int64_
 int advstep_pgd_l2_step_f32(const float *adv, const float *grad, const float *orig, float *out, int64_t B, int64_t T,
                             float alpha, float eps, float eps_div, float lo, float hi, float *gnorm, float *dnorm,
                             void *ws, size_t ws_bytes, advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(adv && grad && orig && out);
+    ADVSTEP_REQUIRE(adv && grad && orig && out);
     RowWs w;
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
@@ -1443,7 +1430,7 @@ int advstep_pgd_l2_step_f32(const float *adv, const float *grad, const float *or
 
 int advstep_pgd_l2_repaired_rows(const void *ws, size_t ws_bytes, int64_t B, int64_t T, int *count,
                                  advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0 && count);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && count);
     if (B == 0 || T == 0) return hipMemsetAsync(count, 0, sizeof(int), as_stream(stream)) == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH;
     if (!ws || !aligned16(ws) || ws_bytes < row_ws_bytes(B, T)) return ADVSTEP_EWORKSPACE;
     RowWs w;
@@ -1453,17 +1440,17 @@ int advstep_pgd_l2_repaired_rows(const void *ws, size_t ws_bytes, int64_t B, int
 }
 
 int advstep_cw_init_w_f32(const float *x, float *w, int64_t n, advstep_stream_t stream) {
-    ADV_REQUIRE(n >= 0);
+    ADVSTEP_REQUIRE(n >= 0);
     if (n == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(x && w);
+    ADVSTEP_REQUIRE(x && w);
     return launch_flat<1>(x, nullptr, nullptr, w, n, CwInitOp{}, as_stream(stream));
 }
 
 int advstep_cw_tanh_sqdist_f32(const float *w, const float *x, float *adv, float *l2, int64_t B, int64_t T, void *ws,
                                size_t ws_bytes, advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(w && x && adv && l2);
+    ADVSTEP_REQUIRE(w && x && adv && l2);
     RowWs wsp;
     if (!carve_ws(ws, ws_bytes, B, T, &wsp)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
@@ -1477,9 +1464,9 @@ int advstep_cw_tanh_sqdist_f32(const float *w, const float *x, float *adv, float
 int advstep_cw_adam_step_f32(float *w, float *m, float *v, const float *x, const float *grad_adv, int64_t n,
                              int64_t step, double lr, double beta1, double beta2, double adam_eps,
                              advstep_stream_t stream) {
-    ADV_REQUIRE(n >= 0 && step >= 1);
+    ADVSTEP_REQUIRE(n >= 0 && step >= 1);
     if (n == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(w && m && v && x && grad_adv);
+    ADVSTEP_REQUIRE(w && m && v && x && grad_adv);
     const double bc1 = 1.0 - pow(beta1, (double)step);
     const double bc2 = 1.0 - pow(beta2, (double)step);
     AdamScalars s;
@@ -1511,9 +1498,9 @@ int advstep_cw_adam_step_f32(float *w, float *m, float *v, const float *x, const
 
 int advstep_cw_best_update_f32(const float *adv, const float *mask, float *best, int64_t B, int64_t T,
                                advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    ADV_REQUIRE(adv && mask && best);
+    ADVSTEP_REQUIRE(adv && mask && best);
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, best});
     ADV_LAUNCH_ROWS(cw_best_update_kernel, vec, B, T, st, adv + b0 * T, mask + b0, best + b0 * T, T);
@@ -1522,8 +1509,8 @@ int advstep_cw_best_update_f32(const float *adv, const float *mask, float *best,
 
 int advstep_ce2_loss_grad_f32(const float *z, const int64_t *labels, float *dz, float *loss, int64_t B, float scale,
                               advstep_stream_t stream) {
-    ADV_REQUIRE(B >= 1);
-    ADV_REQUIRE(z && labels && dz && loss);
+    ADVSTEP_REQUIRE(B >= 1);
+    ADVSTEP_REQUIRE(z && labels && dz && loss);
     hipLaunchKernelGGL(ce2_loss_grad_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), z, labels, dz, loss, B,
                        scale);
     return status_after_launch();

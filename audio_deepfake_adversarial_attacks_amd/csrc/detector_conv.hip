@@ -17,15 +17,11 @@
 #include <stdlib.h>
 
 #include "advstep_detector.h"
+#include "advstep_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
 
 __device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
@@ -227,8 +223,6 @@ __global__ __launch_bounds__(kBlock) void fewout_grad_kernel(const float *__rest
 // The same gradient with a thread owning a 2x4 block of positions (W % 4 == 0): a window row is one 16-byte load (columns
 // 4 tq .. 4 tq + 3, contiguous across lanes) plus the two edge columns, 12 load instructions per channel for 8 outputs instead of
 // 32 — the 2x2 version is bound by the texture path (lanes 8 bytes apart, 16 dword loads per channel and tile), not by HBM.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <int ROWS>
 __global__ __launch_bounds__(kBlock) void fewout_grad4_kernel(const float *__restrict__ g1, const float *__restrict__ w3,
                                                               const float *__restrict__ gp, const uint8_t *__restrict__ sel,

@@ -15,15 +15,11 @@
 #include <stdint.h>
 
 #include "advstep_detector.h"
+#include "advstep_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---- per-channel affine + activation: grid (N * C planes, tiles of 4 x 256 float4 per plane) -------------------------------
 constexpr int kVecPerThread = 4;

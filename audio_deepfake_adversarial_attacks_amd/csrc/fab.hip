@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "advstep_fab.h"
+#include "advstep_common.h"
 
 namespace {
 
@@ -24,10 +25,6 @@ constexpr int kRow = 1024;       // threads per row workgroup
 constexpr int kRowWaves = kRow / 64;
 constexpr int kMaxNewton = 64;   // the iteration is finite (<= number of breakpoints); in practice 3-8 passes
 constexpr float kBig = 1e12f;
-
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 struct Sum {
     __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
@@ -564,19 +561,14 @@ inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < 65535 ? rows 
 
 }  // namespace
 
-#define FAB_REQUIRE(cond) \
-    do {                  \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
 extern "C" {
 
 int advstep_fab_hyperplane_f32(const float *gz, const float *x, const float *z, const int64_t *labels, float *wscale,
                                float *b, float *gnorm, float *gdot, int64_t B, int64_t T, int norm_kind,
                                advstep_stream_t stream) {
-    FAB_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (B == 0) return ADVSTEP_OK;
-    FAB_REQUIRE(gz && x && ((z == nullptr) == (labels == nullptr)) && (!z || (wscale && b)));
+    ADVSTEP_REQUIRE(gz && x && ((z == nullptr) == (labels == nullptr)) && (!z || (wscale && b)));
     const bool vec = (T % 4 == 0) && aligned16(gz) && aligned16(x);
     if (vec)
         hipLaunchKernelGGL(fab_hyperplane_kernel<true>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), gz, x, z, labels,
@@ -590,9 +582,9 @@ int advstep_fab_hyperplane_f32(const float *gz, const float *x, const float *z, 
 int advstep_fab_projection_f32(const float *t, const float *w, const float *wscale, const float *b, float *d,
                                float *dnorm, int64_t R, int64_t w_rows, int64_t T, int norm_kind,
                                advstep_stream_t stream) {
-    FAB_REQUIRE(R >= 0 && T >= 0 && w_rows >= 0 && norm_kind >= 0 && norm_kind <= 2);
+    ADVSTEP_REQUIRE(R >= 0 && T >= 0 && w_rows >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (R == 0) return ADVSTEP_OK;
-    FAB_REQUIRE(t && w && b && d && d != t && d != w && w_rows >= 1 && T >= 1 && T < (int64_t(1) << 24));
+    ADVSTEP_REQUIRE(t && w && b && d && d != t && d != w && w_rows >= 1 && T >= 1 && T < (int64_t(1) << 24));
     const bool vec = (T % 4 == 0) && aligned16(t) && aligned16(w) && aligned16(d);
     const dim3 grid(grid_rows(R)), block(kRow);
     hipStream_t st = as_stream(stream);
@@ -612,9 +604,9 @@ int advstep_fab_projection_f32(const float *t, const float *w, const float *wsca
 int advstep_fab_combine_f32(const float *x1, const float *x0, const float *d1, const float *d2, const float *n1,
                             const float *n2, float *out, int64_t B, int64_t T, float eta, float alpha_max,
                             advstep_stream_t stream) {
-    FAB_REQUIRE(B >= 0 && T >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    FAB_REQUIRE(x1 && x0 && d1 && d2 && n1 && n2 && out);
+    ADVSTEP_REQUIRE(x1 && x0 && d1 && d2 && n1 && n2 && out);
     const bool vec = (T % 4 == 0) && aligned16(x1) && aligned16(x0) && aligned16(d1) && aligned16(d2) && aligned16(out);
     if (vec)
         hipLaunchKernelGGL(fab_combine_kernel<true>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), x1, x0, d1, d2, n1,
@@ -627,9 +619,9 @@ int advstep_fab_combine_f32(const float *x1, const float *x0, const float *d1, c
 
 int advstep_fab_backward_step_f32(float *x1, const float *x0, float *adv, float *res2, const uint8_t *is_adv, int64_t B,
                                   int64_t T, float beta, int norm_kind, advstep_stream_t stream) {
-    FAB_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (B == 0) return ADVSTEP_OK;
-    FAB_REQUIRE(x1 && x0 && adv && res2 && is_adv);
+    ADVSTEP_REQUIRE(x1 && x0 && adv && res2 && is_adv);
     const bool vec = (T % 4 == 0) && aligned16(x1) && aligned16(x0) && aligned16(adv);
     if (vec)
         hipLaunchKernelGGL(fab_backward_step_kernel<true>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), x1, x0, adv,

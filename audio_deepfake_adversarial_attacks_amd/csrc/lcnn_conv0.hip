@@ -25,58 +25,12 @@
 #include <stdlib.h>
 
 #include "advstep_lcnn.h"
+#include "advstep_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int K = 5, KK = 25, PAD = 2;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-
-__device__ __forceinline__ bool mfm_takes_b(float a, float b) { return !(a != a) && !(a >= b); }
-
-// same selection rule as lcnn_mfm.hip::pool_select
-__device__ __forceinline__ float pool_select(float a00, float b00, float a01, float b01, float a10, float b10,
-                                             float a11, float b11, int &code) {
-    const bool t00 = mfm_takes_b(a00, b00), t01 = mfm_takes_b(a01, b01);
-    const bool t10 = mfm_takes_b(a10, b10), t11 = mfm_takes_b(a11, b11);
-    const float m00 = t00 ? b00 : a00, m01 = t01 ? b01 : a01, m10 = t10 ? b10 : a10, m11 = t11 ? b11 : a11;
-    float best = -INFINITY;
-    int pos = 0;
-    bool tb = t00;
-    if (m00 > best || m00 != m00) { best = m00; pos = 0; tb = t00; }
-    if (m01 > best || m01 != m01) { best = m01; pos = 1; tb = t01; }
-    if (m10 > best || m10 != m10) { best = m10; pos = 2; tb = t10; }
-    if (m11 > best || m11 != m11) { best = m11; pos = 3; tb = t11; }
-    code = ((int)tb << 2) | pos;
-    return best;
-}
-
-// The same selection in 4 + 15 instead of ~33 vector instructions (round 3): gfx950's v_maximum3_f32 propagates NaN, so the
-// maximum of the 8 candidates is the pooled value whenever no candidate is NaN, and the winner's code is the FIRST candidate
-// in the reference's scan order (a00, b00, a01, b01, a10, b10, a11, b11: `a` keeps ties inside a position, the earlier position
-// keeps ties between positions) that equals it.  A NaN among the candidates (best != best) takes the step-by-step rule above.
-// (A tie between -0 and +0 returns +0 where the scan returns the first: convolution outputs, not bit-compared.)
-__device__ __forceinline__ float pool_select_fast(float a00, float b00, float a01, float b01, float a10, float b10,
-                                                  float a11, float b11, int &code) {
-    const float best = __builtin_elementwise_maximum(
-        __builtin_elementwise_maximum(__builtin_elementwise_maximum(a00, b00), __builtin_elementwise_maximum(a01, b01)),
-        __builtin_elementwise_maximum(__builtin_elementwise_maximum(a10, b10), __builtin_elementwise_maximum(a11, b11)));
-    if (best != best) return pool_select(a00, b00, a01, b01, a10, b10, a11, b11, code);
-    int c = 7;
-    c = a11 == best ? 3 : c;
-    c = b10 == best ? 6 : c;
-    c = a10 == best ? 2 : c;
-    c = b01 == best ? 5 : c;
-    c = a01 == best ? 1 : c;
-    c = b00 == best ? 4 : c;
-    c = a00 == best ? 0 : c;
-    code = c;
-    return best;
-}
 
 __global__ __launch_bounds__(kBlock) void conv5_mfm_pool2_forward_kernel(const float *__restrict__ x,
                                                                          const float *__restrict__ weight,
@@ -416,23 +370,16 @@ inline bool conv0_cells_enabled() {
     return !(e && e[0] == 'g');
 }
 
-constexpr int64_t kMaxGridY = 65535;
-
 }  // namespace
-
-#define CONV0_REQUIRE(cond) \
-    do {                    \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
 
 extern "C" {
 
 int advstep_conv5_mfm_pool2_forward_f32(const float *x, const float *weight, const float *bias, float *y, uint8_t *idx,
                                         int64_t N, int64_t C, int64_t H, int64_t W, advstep_stream_t stream) {
-    CONV0_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
     const int64_t Ho = H / 2, Wo = W / 2;
     if (N == 0 || C == 0 || Ho == 0 || Wo == 0) return ADVSTEP_OK;
-    CONV0_REQUIRE(x && weight && y && idx && N <= kMaxGridY && C <= 4096 && H * W <= INT32_MAX);
+    ADVSTEP_REQUIRE(x && weight && y && idx && N <= kMaxGridY && C <= 4096 && H * W <= INT32_MAX);
     const dim3 grid((unsigned)ceil_div(Ho * Wo, kBlock), (unsigned)N);
     hipLaunchKernelGGL(conv5_mfm_pool2_forward_kernel, grid, dim3(kBlock), 0, as_stream(stream), x, weight, bias, y, idx,
                        (int)C, (int)H, (int)W);
@@ -441,13 +388,13 @@ int advstep_conv5_mfm_pool2_forward_f32(const float *x, const float *weight, con
 
 int advstep_conv5_mfm_pool2_backward_f32(const float *gy, const uint8_t *idx, const float *weight, float *gx, int64_t N,
                                          int64_t C, int64_t H, int64_t W, advstep_stream_t stream) {
-    CONV0_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
-    CONV0_REQUIRE(gx && N <= kMaxGridY && C <= 96 && H * W <= INT32_MAX);   // 2 C bordered 7x7 tables must fit 64 KB of LDS
+    ADVSTEP_REQUIRE(gx && N <= kMaxGridY && C <= 96 && H * W <= INT32_MAX);   // 2 C bordered 7x7 tables must fit 64 KB of LDS
     hipStream_t st = as_stream(stream);
     if (C == 0 || H / 2 == 0 || W / 2 == 0)
         return hipMemsetAsync(gx, 0, (size_t)N * H * W * sizeof(float), st) == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH;
-    CONV0_REQUIRE(gy && idx && weight);
+    ADVSTEP_REQUIRE(gy && idx && weight);
     const int64_t Wp = (W + 1) / 2, Hp = (H + 1) / 2;
     if (conv0_cells_enabled() && Wp <= kCellsMaxWidth && W % 2 == 0 && (reinterpret_cast<uintptr_t>(gx) & 7u) == 0 &&
         C * (H / 2) * (W / 2) < (1 << 27)) {

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "advstep_lcnn.h"
+#include "advstep_common.h"
 
 namespace {
 
@@ -37,11 +38,6 @@ constexpr int kPixPerBlock = 128;    // 32 pixels per wave
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-
-__device__ __forceinline__ bool mfm_takes_b(float a, float b) { return !(a != a) && !(a >= b); }
 __device__ __forceinline__ int mfma_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // Selection format.  Channel c of a pixel lives in the forward lane half h = (c >> 2) & 1 of that pixel, bit
@@ -315,8 +311,6 @@ __global__ __launch_bounds__(kBlock) void conv1x1_mfm_backward_kernel(const floa
     }
 }
 
-constexpr int64_t kMaxGridY = 65535;
-
 template <typename K>
 void opt_in_lds(K kernel, size_t bytes) {
     if (bytes > 48 * 1024)
@@ -367,11 +361,6 @@ void launch_bwd(const float *gy, const uint8_t *sel, const float *w, const float
 
 }  // namespace
 
-#define C11_REQUIRE(cond) \
-    do {                  \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
 extern "C" {
 
 int advstep_conv1x1_mfm_supported(int64_t Cin) { return Cin == 32 || Cin == 48 || Cin == 64; }
@@ -384,10 +373,10 @@ size_t advstep_conv1x1_mfm_sel_bytes(int64_t N, int64_t C, int64_t P) {
 int advstep_conv1x1_mfm_forward_f32(const float *x, const float *weight, const float *bias, const float *bn_mean,
                                     const float *bn_invstd, float *y, void *sel, int64_t N, int64_t Cin, int64_t C,
                                     int64_t P, advstep_stream_t stream) {
-    C11_REQUIRE(N >= 0 && C >= 0 && P >= 0 && advstep_conv1x1_mfm_supported(Cin));
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && P >= 0 && advstep_conv1x1_mfm_supported(Cin));
     if (N == 0 || C == 0 || P == 0) return ADVSTEP_OK;
-    C11_REQUIRE(x && weight && y && sel && N <= kMaxGridY && C <= 64 && ((reinterpret_cast<uintptr_t>(sel) & 3u) == 0));
-    C11_REQUIRE((bn_mean == nullptr) == (bn_invstd == nullptr));
+    ADVSTEP_REQUIRE(x && weight && y && sel && N <= kMaxGridY && C <= 64 && ((reinterpret_cast<uintptr_t>(sel) & 3u) == 0));
+    ADVSTEP_REQUIRE((bn_mean == nullptr) == (bn_invstd == nullptr));
     auto *s32 = static_cast<uint8_t *>(sel);
     hipStream_t st = as_stream(stream);
     const bool two = C > 32;
@@ -410,14 +399,14 @@ int advstep_conv1x1_mfm_forward_f32(const float *x, const float *weight, const f
 
 int advstep_conv1x1_mfm_backward_f32(const float *gy, const void *sel, const float *weight, const float *gscale, float *gx,
                                      int64_t N, int64_t Cin, int64_t C, int64_t P, advstep_stream_t stream) {
-    C11_REQUIRE(N >= 0 && C >= 0 && P >= 0 && advstep_conv1x1_mfm_supported(Cin));
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && P >= 0 && advstep_conv1x1_mfm_supported(Cin));
     if (N == 0 || P == 0) return ADVSTEP_OK;
-    C11_REQUIRE(gx && N <= kMaxGridY && C <= 64);
+    ADVSTEP_REQUIRE(gx && N <= kMaxGridY && C <= 64);
     hipStream_t st = as_stream(stream);
     if (C == 0)
         return hipMemsetAsync(gx, 0, (size_t)N * Cin * P * sizeof(float), st) == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH;
-    C11_REQUIRE(gy && sel && weight);
-    C11_REQUIRE((reinterpret_cast<uintptr_t>(sel) & 3u) == 0);
+    ADVSTEP_REQUIRE(gy && sel && weight);
+    ADVSTEP_REQUIRE((reinterpret_cast<uintptr_t>(sel) & 3u) == 0);
     auto *s32 = static_cast<const uint8_t *>(sel);
     switch (Cin) {
         case 32: launch_bwd<32, 1>(gy, s32, weight, gscale, gx, N, C, P, st); break;

@@ -18,18 +18,11 @@
 #include <stdlib.h>
 
 #include "advstep_lcnn.h"
+#include "advstep_common.h"
 
 namespace {
 
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding global access
-// (s_waitcnt vmcnt(0)): inside the step loops that put each step's stores — and the prefetch of the next step's inputs —
-// on the critical path of a 25-step recurrence.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // gx (T, B, D, 4H), w_hh (D, 4H, H), out (T, B, D*H), gates (T, B, D, 4H), cell (T, B, D, H)
 template <int H>
@@ -91,8 +84,6 @@ __global__ __launch_bounds__(4 * H) void lstm_forward_kernel(const float *__rest
         lds_barrier();
     }
 }
-
-typedef float f32x2_l __attribute__((ext_vector_type(2)));
 
 // dout (T, B, D*H) -> dgx (T, B, D, 4H): gradient w.r.t. the gate pre-activations (what the projection GEMM consumes)
 template <int H>
@@ -190,11 +181,11 @@ __global__ __launch_bounds__(4 * H) void lstm_backward_kernel(const float *__res
 #pragma unroll
         for (int jj = 0; jj < H / 4; ++jj) gv[jj] = *reinterpret_cast<const float4 *>(&dg_s[q * H + 4 * jj]);
         __builtin_amdgcn_sched_barrier(0);
-        f32x2_l s01 = {0.0f, 0.0f}, s23 = {0.0f, 0.0f};
+        f32x2 s01 = {0.0f, 0.0f}, s23 = {0.0f, 0.0f};
 #pragma unroll
         for (int jj = 0; jj < H / 4; ++jj) {
-            s01 = __builtin_elementwise_fma((f32x2_l){gv[jj].x, gv[jj].y}, (f32x2_l){w[4 * jj], w[4 * jj + 1]}, s01);
-            s23 = __builtin_elementwise_fma((f32x2_l){gv[jj].z, gv[jj].w}, (f32x2_l){w[4 * jj + 2], w[4 * jj + 3]}, s23);
+            s01 = __builtin_elementwise_fma((f32x2){gv[jj].x, gv[jj].y}, (f32x2){w[4 * jj], w[4 * jj + 1]}, s01);
+            s23 = __builtin_elementwise_fma((f32x2){gv[jj].z, gv[jj].w}, (f32x2){w[4 * jj + 2], w[4 * jj + 3]}, s23);
         }
         part[tid] = (s01.x + s01.y) + (s23.x + s23.y);
         const Coef nxt = reduce(raw);            // values loaded during the previous step
@@ -271,20 +262,15 @@ __global__ __launch_bounds__(256) void lcnn_tail_unpack_add_kernel(const float *
 
 }  // namespace
 
-#define LSTM_REQUIRE(cond) \
-    do {                   \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
 extern "C" {
 
 int advstep_lstm_supported(int64_t H) { return H == 80; }
 
 int advstep_lstm_forward_f32(const float *gx, const float *w_hh, float *out, float *gates, float *cell, int64_t T,
                              int64_t B, int64_t D, int64_t H, advstep_stream_t stream) {
-    LSTM_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
+    ADVSTEP_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
     if (T == 0 || B == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(gx && w_hh && out && gates && cell && T <= INT32_MAX && B <= INT32_MAX);
+    ADVSTEP_REQUIRE(gx && w_hh && out && gates && cell && T <= INT32_MAX && B <= INT32_MAX);
     hipLaunchKernelGGL(lstm_forward_kernel<80>, dim3((unsigned)B, (unsigned)D), dim3(320), 0, as_stream(stream), gx, w_hh,
                        out, gates, cell, (int)T, (int)B, (int)D);
     return status_after_launch();
@@ -292,9 +278,9 @@ int advstep_lstm_forward_f32(const float *gx, const float *w_hh, float *out, flo
 
 int advstep_lstm_backward_f32(const float *dout, const float *w_hh, const float *gates, const float *cell, float *dgx,
                               int64_t T, int64_t B, int64_t D, int64_t H, advstep_stream_t stream) {
-    LSTM_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
+    ADVSTEP_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
     if (T == 0 || B == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(dout && w_hh && gates && cell && dgx && T <= INT32_MAX && B <= INT32_MAX);
+    ADVSTEP_REQUIRE(dout && w_hh && gates && cell && dgx && T <= INT32_MAX && B <= INT32_MAX);
     hipLaunchKernelGGL(lstm_backward_kernel<80>, dim3((unsigned)B, (unsigned)D), dim3(320), 0, as_stream(stream), dout,
                        w_hh, gates, cell, dgx, (int)T, (int)B, (int)D, (int64_t)B * D * H, (int64_t)D * H,
                        static_cast<const float *>(nullptr));
@@ -303,9 +289,9 @@ int advstep_lstm_backward_f32(const float *dout, const float *w_hh, const float 
 
 int advstep_lstm_backward_bcast_f32(const float *dout_row, const float *w_hh, const float *gates, const float *cell,
                                     float *dgx, int64_t T, int64_t B, int64_t D, int64_t H, advstep_stream_t stream) {
-    LSTM_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
+    ADVSTEP_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
     if (T == 0 || B == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(dout_row && w_hh && gates && cell && dgx && T <= INT32_MAX && B <= INT32_MAX);
+    ADVSTEP_REQUIRE(dout_row && w_hh && gates && cell && dgx && T <= INT32_MAX && B <= INT32_MAX);
     hipLaunchKernelGGL(lstm_backward_kernel<80>, dim3((unsigned)B, (unsigned)D), dim3(320), 0, as_stream(stream), dout_row,
                        w_hh, gates, cell, dgx, (int)T, (int)B, (int)D, (int64_t)0, (int64_t)D * H, static_cast<const float *>(nullptr));
     return status_after_launch();
@@ -313,19 +299,19 @@ int advstep_lstm_backward_bcast_f32(const float *dout_row, const float *w_hh, co
 
 int advstep_lstm_backward_outer_f32(const float *dz, const float *row, const float *w_hh, const float *gates, const float *cell,
                                     float *dgx, int64_t T, int64_t B, int64_t D, int64_t H, advstep_stream_t stream) {
-    LSTM_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
+    ADVSTEP_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_lstm_supported(H));
     if (T == 0 || B == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(dz && row && w_hh && gates && cell && dgx && T <= INT32_MAX && B <= INT32_MAX);
+    ADVSTEP_REQUIRE(dz && row && w_hh && gates && cell && dgx && T <= INT32_MAX && B <= INT32_MAX);
     hipLaunchKernelGGL(lstm_backward_kernel<80>, dim3((unsigned)B, (unsigned)D), dim3(320), 0, as_stream(stream), row, w_hh, gates,
                        cell, dgx, (int)T, (int)B, (int)D, (int64_t)0, (int64_t)0, dz);
     return status_after_launch();
 }
 
 int advstep_lcnn_tail_pack_f32(const float *x4, float *xt, int64_t B, int64_t C, int64_t T, int64_t W, advstep_stream_t stream) {
-    LSTM_REQUIRE(B >= 0 && C >= 0 && T >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && C >= 0 && T >= 0 && W >= 0);
     const int64_t total = B * C * T * W;
     if (total == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(x4 && xt && B <= INT32_MAX && C <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX);
+    ADVSTEP_REQUIRE(x4 && xt && B <= INT32_MAX && C <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX);
     const int64_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(lcnn_tail_pack_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, as_stream(stream), x4,
                        xt, (int)B, (int)C, (int)T, (int)W);
@@ -334,9 +320,9 @@ int advstep_lcnn_tail_pack_f32(const float *x4, float *xt, int64_t B, int64_t C,
 
 int advstep_lcnn_tail_forward_f32(const float *a, const float *xt, const float *w, const float *bias, float *z, int64_t T,
                                   int64_t B, int64_t F, advstep_stream_t stream) {
-    LSTM_REQUIRE(T >= 1 && B >= 0 && F >= 1 && F <= 256);
+    ADVSTEP_REQUIRE(T >= 1 && B >= 0 && F >= 1 && F <= 256);
     if (B == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(a && xt && w && z && T <= INT32_MAX && B <= INT32_MAX);
+    ADVSTEP_REQUIRE(a && xt && w && z && T <= INT32_MAX && B <= INT32_MAX);
     hipLaunchKernelGGL(lcnn_tail_forward_kernel, dim3((unsigned)B), dim3(256), 0, as_stream(stream), a, xt, w, bias, z, (int)T,
                        (int)B, (int)F);
     return status_after_launch();
@@ -344,10 +330,10 @@ int advstep_lcnn_tail_forward_f32(const float *a, const float *xt, const float *
 
 int advstep_lcnn_tail_unpack_add_f32(const float *dxt, const float *g0, float *dx4, int64_t B, int64_t C, int64_t T, int64_t W,
                                      advstep_stream_t stream) {
-    LSTM_REQUIRE(B >= 0 && C >= 0 && T >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && C >= 0 && T >= 0 && W >= 0);
     const int64_t total = B * C * T * W;
     if (total == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(dxt && g0 && dx4 && B <= INT32_MAX && C <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX);
+    ADVSTEP_REQUIRE(dxt && g0 && dx4 && B <= INT32_MAX && C <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX);
     const int64_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(lcnn_tail_unpack_add_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                        as_stream(stream), dxt, g0, static_cast<const float *>(nullptr), dx4, (int)B, (int)C, (int)T, (int)W);
@@ -356,10 +342,10 @@ int advstep_lcnn_tail_unpack_add_f32(const float *dxt, const float *g0, float *d
 
 int advstep_lcnn_tail_unpack_add_outer_f32(const float *dxt, const float *dz, const float *row, float *dx4, int64_t B, int64_t C,
                                            int64_t T, int64_t W, advstep_stream_t stream) {
-    LSTM_REQUIRE(B >= 0 && C >= 0 && T >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(B >= 0 && C >= 0 && T >= 0 && W >= 0);
     const int64_t total = B * C * T * W;
     if (total == 0) return ADVSTEP_OK;
-    LSTM_REQUIRE(dxt && dz && row && dx4 && B <= INT32_MAX && C <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX);
+    ADVSTEP_REQUIRE(dxt && dz && row && dx4 && B <= INT32_MAX && C <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX);
     const int64_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(lcnn_tail_unpack_add_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                        as_stream(stream), dxt, row, dz, dx4, (int)B, (int)C, (int)T, (int)W);

@@ -19,19 +19,12 @@
 #include <stdint.h>
 
 #include "advstep_lcnn.h"
+#include "advstep_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kGroupsPerThread = 4;  // MFM: float4 groups per thread
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-
-// at::native::MaxOps combine for two candidates at indices 0 (a) and 1 (b): true when b is selected.
-__device__ __forceinline__ bool mfm_takes_b(float a, float b) { return !(a != a) && !(a >= b); }
 
 // ---------------------------------------------------------------------------------------------------------
 // MFM alone: per sample, P = C*HW outputs, G = ceil(P / 4) groups; thread = one group of 4 outputs
@@ -190,24 +183,6 @@ __global__ __launch_bounds__(kBlock) void mfm_backward_kernel(const float *__res
 // MFM + MaxPool2d(2, 2)
 // ---------------------------------------------------------------------------------------------------------
 
-// One pooled output from its 2x2 window of (a, b) pairs, in ATen's order: MFM per position, then the pool scan
-// (0,0), (0,1), (1,0), (1,1) with  take = (v > best || isnan(v)),  best = -inf initially.
-__device__ __forceinline__ float pool_select(float a00, float b00, float a01, float b01, float a10, float b10,
-                                             float a11, float b11, int &code) {
-    const bool t00 = mfm_takes_b(a00, b00), t01 = mfm_takes_b(a01, b01);
-    const bool t10 = mfm_takes_b(a10, b10), t11 = mfm_takes_b(a11, b11);
-    const float m00 = t00 ? b00 : a00, m01 = t01 ? b01 : a01, m10 = t10 ? b10 : a10, m11 = t11 ? b11 : a11;
-    float best = -INFINITY;
-    int pos = 0;
-    bool tb = t00;
-    if (m00 > best || m00 != m00) { best = m00; pos = 0; tb = t00; }
-    if (m01 > best || m01 != m01) { best = m01; pos = 1; tb = t01; }
-    if (m10 > best || m10 != m10) { best = m10; pos = 2; tb = t10; }
-    if (m11 > best || m11 != m11) { best = m11; pos = 3; tb = t11; }
-    code = ((int)tb << 2) | pos;
-    return best;
-}
-
 // VEC path (W % 4 == 0, 16-byte aligned planes): thread = (c, ho, wq) -> two pooled outputs from four float4 loads.
 __global__ __launch_bounds__(kBlock) void mfm_pool2_forward_vec_kernel(const float *__restrict__ x,
                                                                        const float *__restrict__ bias,
@@ -358,14 +333,7 @@ __global__ __launch_bounds__(kBlock) void mfm_pool2_backward_scalar_kernel(const
         gscale ? gy[n * items + i] * gscale[c] : gy[n * items + i];
 }
 
-constexpr int64_t kMaxGridY = 65535;
-
 }  // namespace
-
-#define LCNN_REQUIRE(cond) \
-    do {                   \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
 
 extern "C" {
 
@@ -376,9 +344,9 @@ size_t advstep_mfm_sel_bytes(int64_t N, int64_t C, int64_t HW) {
 
 int advstep_mfm_forward_f32(const float *x, const float *bias, const float *bn_mean, const float *bn_invstd, float *y,
                             uint8_t *sel, int64_t N, int64_t C, int64_t HW, advstep_stream_t stream) {
-    LCNN_REQUIRE(N >= 0 && C >= 0 && HW >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && HW >= 0);
     if (N == 0 || C == 0 || HW == 0) return ADVSTEP_OK;
-    LCNN_REQUIRE(x && y && sel && N <= kMaxGridY);
+    ADVSTEP_REQUIRE(x && y && sel && N <= kMaxGridY);
     const int64_t P = C * HW, G = ceil_div(P, 4);
     const dim3 grid((unsigned)ceil_div(G, kBlock * kGroupsPerThread), (unsigned)N);
     if (P % 4 == 0 && aligned16(x) && aligned16(y))
@@ -390,9 +358,9 @@ int advstep_mfm_forward_f32(const float *x, const float *bias, const float *bn_m
 
 int advstep_mfm_backward_f32(const float *gy, const uint8_t *sel, const float *gscale, float *gx, int64_t N, int64_t C,
                              int64_t HW, advstep_stream_t stream) {
-    LCNN_REQUIRE(N >= 0 && C >= 0 && HW >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && HW >= 0);
     if (N == 0 || C == 0 || HW == 0) return ADVSTEP_OK;
-    LCNN_REQUIRE(gy && sel && gx && N <= kMaxGridY);
+    ADVSTEP_REQUIRE(gy && sel && gx && N <= kMaxGridY);
     const int64_t P = C * HW, G = ceil_div(P, 4);
     const dim3 grid((unsigned)ceil_div(G, kBlock * kGroupsPerThread), (unsigned)N);
     if (P % 4 == 0 && aligned16(gy) && aligned16(gx))
@@ -405,10 +373,10 @@ int advstep_mfm_backward_f32(const float *gy, const uint8_t *sel, const float *g
 int advstep_mfm_pool2_forward_f32(const float *x, const float *bias, const float *bn_mean, const float *bn_invstd,
                                   float *y, uint8_t *idx, int64_t N, int64_t C, int64_t H, int64_t W,
                                   advstep_stream_t stream) {
-    LCNN_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
     const int64_t Ho = H / 2, Wo = W / 2;
     if (N == 0 || C == 0 || Ho == 0 || Wo == 0) return ADVSTEP_OK;
-    LCNN_REQUIRE(x && y && idx && N <= kMaxGridY && C <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX);
+    ADVSTEP_REQUIRE(x && y && idx && N <= kMaxGridY && C <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX);
     hipStream_t st = as_stream(stream);
     if (W % 4 == 0 && aligned16(x) && ((reinterpret_cast<uintptr_t>(y) & 7u) == 0) &&
         ((reinterpret_cast<uintptr_t>(idx) & 1u) == 0)) {
@@ -424,16 +392,16 @@ int advstep_mfm_pool2_forward_f32(const float *x, const float *bias, const float
 
 int advstep_mfm_pool2_backward_f32(const float *gy, const uint8_t *idx, const float *gscale, float *gx, int64_t N,
                                    int64_t C, int64_t H, int64_t W, advstep_stream_t stream) {
-    LCNN_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
     if (N == 0 || C == 0 || H == 0 || W == 0) return ADVSTEP_OK;
-    LCNN_REQUIRE(gx && N <= kMaxGridY && C <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX);
+    ADVSTEP_REQUIRE(gx && N <= kMaxGridY && C <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX);
     hipStream_t st = as_stream(stream);
     const int64_t Ho = H / 2, Wo = W / 2;
     if (Ho == 0 || Wo == 0) {  // nothing was pooled: the whole gradient is zero
         return hipMemsetAsync(gx, 0, (size_t)N * 2 * C * H * W * sizeof(float), st) == hipSuccess ? ADVSTEP_OK
                                                                                                  : ADVSTEP_ELAUNCH;
     }
-    LCNN_REQUIRE(gy && idx);
+    ADVSTEP_REQUIRE(gy && idx);
     if (W % 4 == 0 && aligned16(gx) && ((reinterpret_cast<uintptr_t>(gy) & 7u) == 0) &&
         ((reinterpret_cast<uintptr_t>(idx) & 1u) == 0)) {
         const int64_t items = C * Ho * (W / 4);

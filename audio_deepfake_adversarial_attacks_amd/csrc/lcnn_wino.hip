@@ -33,6 +33,18 @@
 
 #include "advstep_detector.h"
 #include "advstep_lcnn.h"
+#include "advstep_common.h"
+
+// Build-time switches (tools/build_variant.sh SOURCE -DNAME=...):
+// WINO_GLDS: the STREAM kernels copy weight chunks global -> LDS by LDS-DMA rather than through registers (wino3x3_kernel's
+// copy_chunk); by default only the compact-source (SRC == 1) instantiations do.  Expands inside the kernel template, whose
+// parameter SRC it names.
+#ifndef WINO_GLDS
+#define WINO_GLDS (SRC == 1)
+#endif
+#ifndef WINO_TIMING_NT1          // timing-only builds (tools/build_variant.sh ... -DWINO_TIMING_NT1=1): the last slice ALWAYS as one
+#define WINO_TIMING_NT1 0       // accumulator tile, i.e. rows 16..31 of a 17..32-row slice dropped (wrong results) - what SpecRNet's
+#endif                          // 20-row layers would cost if their 12 dead rows were free (VERDICT r05 item 5)
 
 namespace {
 
@@ -40,55 +52,6 @@ constexpr int kWaves = 8, kThreads = kWaves * 64;
 constexpr int kChunkCin = 16;                         // input channels per LDS chunk
 constexpr int kChunkFloats = 16 * kChunkCin * 32;     // [xi][cin][16 j][2 m] = 32 KB
 constexpr int kMaxResident = 4;                       // chunks kept in LDS when K <= 64
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-__device__ __forceinline__ bool mfm_takes_b(float a, float b) { return !(a != a) && !(a >= b); }
-
-// same selection rule as lcnn_mfm.hip::pool_select
-__device__ __forceinline__ float pool_select(float a00, float b00, float a01, float b01, float a10, float b10,
-                                             float a11, float b11, int &code) {
-    const bool t00 = mfm_takes_b(a00, b00), t01 = mfm_takes_b(a01, b01);
-    const bool t10 = mfm_takes_b(a10, b10), t11 = mfm_takes_b(a11, b11);
-    const float m00 = t00 ? b00 : a00, m01 = t01 ? b01 : a01, m10 = t10 ? b10 : a10, m11 = t11 ? b11 : a11;
-    float best = -INFINITY;
-    int pos = 0;
-    bool tb = t00;
-    if (m00 > best || m00 != m00) { best = m00; pos = 0; tb = t00; }
-    if (m01 > best || m01 != m01) { best = m01; pos = 1; tb = t01; }
-    if (m10 > best || m10 != m10) { best = m10; pos = 2; tb = t10; }
-    if (m11 > best || m11 != m11) { best = m11; pos = 3; tb = t11; }
-    code = ((int)tb << 2) | pos;
-    return best;
-}
-
-// The same selection in 4 + 15 instead of ~33 vector instructions (round 3): gfx950's v_maximum3_f32 propagates NaN, so the
-// maximum of the 8 candidates is the pooled value whenever no candidate is NaN, and the winner's code is the FIRST candidate
-// in the reference's scan order (a00, b00, a01, b01, a10, b10, a11, b11: `a` keeps ties inside a position, the earlier position
-// keeps ties between positions) that equals it.  A NaN among the candidates (best != best) takes the step-by-step rule above.
-// (A tie between -0 and +0 returns +0 where the scan returns the first: convolution outputs, not bit-compared.)
-__device__ __forceinline__ float pool_select_fast(float a00, float b00, float a01, float b01, float a10, float b10,
-                                                  float a11, float b11, int &code) {
-    const float best = __builtin_elementwise_maximum(
-        __builtin_elementwise_maximum(__builtin_elementwise_maximum(a00, b00), __builtin_elementwise_maximum(a01, b01)),
-        __builtin_elementwise_maximum(__builtin_elementwise_maximum(a10, b10), __builtin_elementwise_maximum(a11, b11)));
-    if (best != best) return pool_select(a00, b00, a01, b01, a10, b10, a11, b11, code);
-    int c = 7;
-    c = a11 == best ? 3 : c;
-    c = b10 == best ? 6 : c;
-    c = a10 == best ? 2 : c;
-    c = b01 == best ? 5 : c;
-    c = a01 == best ? 1 : c;
-    c = b00 == best ? 4 : c;
-    c = a00 == best ? 0 : c;
-    code = c;
-    return best;
-}
 
 // ---- weight transform: U = G g G^T into the chunked layout ------------------------------------------------------------
 // mode 0 (forward, max-feature-map pairs): output row (slice, j, m) = conv channel m * C + slice * 16 + j, g = weight.
@@ -285,10 +248,7 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
     // and 170 -> 167 us; the dense-source ones get SLOWER (276 -> 287 us: with a DMA in flight hipcc waits vmcnt(0) at the next
     // use of an ordinary load, which drains their patch prefetch), so they keep the register path.  The DMA's completion is waited
     // for (vmcnt(0)) before the barrier that publishes the chunk.  The LDS destination of a wave-instruction is a wave-uniform
-    // base + lane x 16 B, which is exactly this copy's layout.
-#ifndef WINO_GLDS
-#define WINO_GLDS (SRC == 1)
-#endif
+    // base + lane x 16 B, which is exactly this copy's layout.  WINO_GLDS (top of the file) selects it.
     auto copy_chunk = [&](int chunk, int buf) {
         const float4 *src = reinterpret_cast<const float4 *>(Usl + (int64_t)chunk * kChunkFloats);
         float4 *dst = reinterpret_cast<float4 *>(u_s + buf * kChunkFloats);
@@ -868,9 +828,6 @@ int launch_wino(const float *x, const uint8_t *xsel, const float *U, const float
     int full = slices;
     if constexpr (EPI == 0 || EPI == 3 || EPI == 5 || EPI == 6) {
         const int live_last = (int)(Cout - (int64_t)(slices - 1) * 32);
-#ifndef WINO_TIMING_NT1          // timing-only builds (tools/build_variant.sh ... -DWINO_TIMING_NT1=1): the last slice ALWAYS as one
-#define WINO_TIMING_NT1 0       // accumulator tile, i.e. rows 16..31 of a 17..32-row slice dropped (wrong results) - what SpecRNet's
-#endif                          // 20-row layers would cost if their 12 dead rows were free (VERDICT r05 item 5)
         if ((live_last <= 16 || WINO_TIMING_NT1) && half_slice_enabled()) {
             full = slices - 1;
             if (stream) wodd ? go(wino3x3_kernel<EPI, true, SRC, 1, GEN, SRC == 0>, 1, slices - 1) : go(wino3x3_kernel<EPI, true, SRC, 1, GEN>, 1, slices - 1);
@@ -897,11 +854,6 @@ int launch_wino(const float *x, const uint8_t *xsel, const float *U, const float
 
 }  // namespace
 
-#define WINO_REQUIRE(cond) \
-    do {                   \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
 extern "C" {
 
 int advstep_conv3x3_supported(int64_t Cin, int64_t Cout) {
@@ -917,8 +869,8 @@ size_t advstep_conv3x3_prepared_floats(int64_t Cin, int64_t Cout, int mode) {
 
 int advstep_conv3x3_prepare_f32(const float *weight, const float *gscale, float *U, int64_t Cin, int64_t Cout, int mode,
                                 advstep_stream_t stream) {
-    WINO_REQUIRE(weight && U && advstep_conv3x3_supported(Cin, Cout) && mode >= 0 && mode <= 2);
-    WINO_REQUIRE(gscale == nullptr || mode != 0);
+    ADVSTEP_REQUIRE(weight && U && advstep_conv3x3_supported(Cin, Cout) && mode >= 0 && mode <= 2);
+    ADVSTEP_REQUIRE(gscale == nullptr || mode != 0);
     const int K = (int)(mode == 0 ? Cin : Cout);
     const int slices = (int)(mode == 0 ? ceil_div(Cout / 2, 16) : ceil_div(Cin, 32));
     const int total = slices * 32 * K;
@@ -930,10 +882,10 @@ int advstep_conv3x3_prepare_f32(const float *weight, const float *gscale, float 
 int advstep_conv3x3_mfm_pool2_forward_f32(const float *x, const float *U, const float *bias, const float *bn_mean,
                                           const float *bn_invstd, float *y, uint8_t *idx, int64_t N, int64_t Cin, int64_t C,
                                           int64_t H, int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
     if (N == 0 || H / 2 == 0 || W / 2 == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(x && U && y && idx && (bn_mean == nullptr) == (bn_invstd == nullptr));
-    WINO_REQUIRE((uint64_t)N * Cin * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(x && U && y && idx && (bn_mean == nullptr) == (bn_invstd == nullptr));
+    ADVSTEP_REQUIRE((uint64_t)N * Cin * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
     return launch_wino<1, 0>(x, nullptr, U, bias, bn_mean, bn_invstd, y, idx, N, Cin, H, W, C, (int)ceil_div(C, 16),
                              as_stream(stream));
 }
@@ -946,20 +898,20 @@ size_t advstep_conv3x3_mfm_sel_bytes(int64_t N, int64_t C, int64_t H, int64_t W)
 int advstep_conv3x3_mfm_forward_f32(const float *x, const float *U, const float *bias, const float *bn_mean,
                                     const float *bn_invstd, float *y, uint8_t *sel, int64_t N, int64_t Cin, int64_t C,
                                     int64_t H, int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(x && U && y && sel && (bn_mean == nullptr) == (bn_invstd == nullptr));
-    WINO_REQUIRE((uint64_t)N * Cin * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(x && U && y && sel && (bn_mean == nullptr) == (bn_invstd == nullptr));
+    ADVSTEP_REQUIRE((uint64_t)N * Cin * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
     return launch_wino<2, 0>(x, nullptr, U, bias, bn_mean, bn_invstd, y, sel, N, Cin, H, W, C, (int)ceil_div(C, 16),
                              as_stream(stream));
 }
 
 int advstep_conv3x3_mfm_backward_f32(const float *gy, const uint8_t *sel, const float *gscale, float *gout, int64_t N,
                                      int64_t C, int64_t H, int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
+    ADVSTEP_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0);
     const int64_t total = N * C * H * W;
     if (total == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(gy && sel && gout);
+    ADVSTEP_REQUIRE(gy && sel && gout);
     const int64_t blocks = ceil_div(total, 256);
     hipLaunchKernelGGL(wino_mfm_backward_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                        as_stream(stream), gy, sel, gscale, gout, (int)C, (int)H, (int)W, total);
@@ -968,24 +920,24 @@ int advstep_conv3x3_mfm_backward_f32(const float *gy, const uint8_t *sel, const 
 
 int advstep_conv3x3_backward_data_f32(const float *gout, const float *U, float *gx, int64_t N, int64_t Cin, int64_t Cout,
                                       int64_t H, int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, Cout));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, Cout));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(gout && U && gx);
-    WINO_REQUIRE((uint64_t)N * Cout * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(gout && U && gx);
+    ADVSTEP_REQUIRE((uint64_t)N * Cout * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
     return launch_wino<0, 0>(gout, nullptr, U, nullptr, nullptr, nullptr, gx, nullptr, N, Cout, H, W, Cin,
                              (int)ceil_div(Cin, 32), as_stream(stream));
 }
 
 int advstep_conv3x3_mfm_pool2_backward_f32(const float *gy, const uint8_t *idx, const float *U, float *gx, int64_t N,
                                            int64_t Cin, int64_t C, int64_t H, int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(gx);
+    ADVSTEP_REQUIRE(gx);
     if (H / 2 == 0 || W / 2 == 0)
         return hipMemsetAsync(gx, 0, (size_t)N * Cin * H * W * sizeof(float), as_stream(stream)) == hipSuccess ? ADVSTEP_OK
                                                                                                                : ADVSTEP_ELAUNCH;
-    WINO_REQUIRE(gy && idx && U);
-    WINO_REQUIRE((uint64_t)N * C * (H / 2) * (W / 2) < (1ull << 29) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(gy && idx && U);
+    ADVSTEP_REQUIRE((uint64_t)N * C * (H / 2) * (W / 2) < (1ull << 29) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
     return launch_wino<0, 1>(gy, idx, U, nullptr, nullptr, nullptr, gx, nullptr, N, 2 * C, H, W, Cin, (int)ceil_div(Cin, 32),
                              as_stream(stream));
 }
@@ -1003,7 +955,7 @@ size_t advstep_resconv_prepared_floats(int64_t K1, int64_t K2, int64_t rows) {
 
 int advstep_resconv_prepare_f32(const float *w3, const float *w1, const float *rscale, const float *kscale, float *U,
                                 int64_t rows, int64_t K1, int64_t K2, int transpose, advstep_stream_t stream) {
-    WINO_REQUIRE(w3 && U && advstep_resconv_supported(K1, K2, rows) && (K2 == 0 || w1) && (transpose == 0 || transpose == 1));
+    ADVSTEP_REQUIRE(w3 && U && advstep_resconv_supported(K1, K2, rows) && (K2 == 0 || w1) && (transpose == 0 || transpose == 1));
     const int slices = (int)ceil_div(rows, 32), chunks = (int)ceil_div(K1 + K2, kChunkCin);
     const int total = slices * 32 * chunks * kChunkCin;
     hipLaunchKernelGGL(wino_prepare_plain_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(stream), w3, w1,
@@ -1013,16 +965,16 @@ int advstep_resconv_prepare_f32(const float *w3, const float *w1, const float *r
 
 static int resconv_check(const float *x1, const float *x2, const float *U, const void *y, int64_t N, int64_t K1, int64_t K2,
                          int64_t rows, int64_t H, int64_t W) {
-    WINO_REQUIRE(x1 && U && y && (K2 == 0 || x2));
-    WINO_REQUIRE((uint64_t)N * (K1 > K2 ? K1 : K2) * H * W * 4 < (1ull << 31) && (uint64_t)N * rows * H * W * 4 < (1ull << 33) &&
-                 (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(x1 && U && y && (K2 == 0 || x2));
+    ADVSTEP_REQUIRE((uint64_t)N * (K1 > K2 ? K1 : K2) * H * W * 4 < (1ull << 31) && (uint64_t)N * rows * H * W * 4 < (1ull << 33) &&
+                    (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
     return ADVSTEP_OK;
 }
 
 int advstep_resconv_forward_act_f32(const float *x1, const float *x2, const float *U, const float *shift, float slope, float *y,
                                     uint8_t *act, int64_t N, int64_t K1, int64_t K2, int64_t rows, int64_t H, int64_t W,
                                     advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K1, K2, rows));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K1, K2, rows));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
     if (const int st = resconv_check(x1, x2, U, y, N, K1, K2, rows, H, W)) return st;
     const int64_t K = (K1 + K2 <= 8) ? 8 : ceil_div(K1 + K2, 4) * 4;      // at least two k-steps; an odd count is fine
@@ -1039,9 +991,9 @@ int advstep_resconv_forward_f32(const float *x1, const float *x2, const float *U
 int advstep_resconv_pool2_forward_f32(const float *x1, const float *x2, const float *U, const float *bias, float *y,
                                       uint8_t *sel, int64_t N, int64_t K1, int64_t K2, int64_t rows, int64_t H, int64_t W,
                                       advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K1, K2, rows));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K1, K2, rows));
     if (N == 0 || H / 2 == 0 || W / 2 == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(sel);
+    ADVSTEP_REQUIRE(sel);
     if (const int st = resconv_check(x1, x2, U, y, N, K1, K2, rows, H, W)) return st;
     const int64_t K = (K1 + K2 <= 8) ? 8 : ceil_div(K1 + K2, 4) * 4;      // at least two k-steps; an odd count is fine
     return launch_wino<4, 0, true>(x1, nullptr, U, bias, nullptr, nullptr, y, sel, N, K, H, W, rows, (int)ceil_div(rows, 32),
@@ -1050,15 +1002,15 @@ int advstep_resconv_pool2_forward_f32(const float *x1, const float *x2, const fl
 
 static int pooled_grad(const float *gy, const uint8_t *sel, const float *U, const float *h, const uint8_t *act, float slope,
                        float *g, int64_t N, int64_t K, int64_t rows, int64_t H, int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K, 0, rows));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K, 0, rows));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(g);
+    ADVSTEP_REQUIRE(g);
     if (H / 2 == 0 || W / 2 == 0)
         return hipMemsetAsync(g, 0, (size_t)N * rows * H * W * sizeof(float), as_stream(stream)) == hipSuccess ? ADVSTEP_OK
                                                                                                                 : ADVSTEP_ELAUNCH;
-    WINO_REQUIRE(gy && sel && U);
-    WINO_REQUIRE((uint64_t)N * K * (H / 2) * (W / 2) < (1ull << 29) && (uint64_t)N * rows * H * W * 4 < (1ull << 33) &&
-                 (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(gy && sel && U);
+    ADVSTEP_REQUIRE((uint64_t)N * K * (H / 2) * (W / 2) < (1ull << 29) && (uint64_t)N * rows * H * W * 4 < (1ull << 33) &&
+                    (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
     const int64_t Kp = K <= 8 ? 8 : ceil_div(K, 4) * 4;
     const GenArgs ga{nullptr, (int)K, (int)K, slope, 0, 0, 0};
     if (act)
@@ -1074,9 +1026,9 @@ static int pooled_grad(const float *gy, const uint8_t *sel, const float *U, cons
 int advstep_resconv_pool2_forward_few_f32(const float *x1, const float *x2, const float *U, const float *wd, const float *bias,
                                           float *y, uint8_t *sel, int64_t N, int64_t K1, int64_t K2, int64_t rows, int64_t H,
                                           int64_t W, advstep_stream_t stream) {
-    WINO_REQUIRE(N >= 0 && H >= 0 && W >= 0 && (K2 == 1 || K2 == 2) && advstep_resconv_supported(K1, 0, rows));
+    ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && (K2 == 1 || K2 == 2) && advstep_resconv_supported(K1, 0, rows));
     if (N == 0 || H / 2 == 0 || W / 2 == 0) return ADVSTEP_OK;
-    WINO_REQUIRE(sel && x2 && wd);
+    ADVSTEP_REQUIRE(sel && x2 && wd);
     if (const int st = resconv_check(x1, nullptr, U, y, N, K1, 0, rows, H, W)) return st;
     const int64_t K = K1 <= 8 ? 8 : ceil_div(K1, 4) * 4;
     return launch_wino<7, 0, true>(x1, nullptr, U, bias, wd, nullptr, y, sel, N, K, H, W, rows, (int)ceil_div(rows, 32),

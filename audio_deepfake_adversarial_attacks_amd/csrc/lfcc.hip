@@ -7,23 +7,12 @@
 #include <stdint.h>
 
 #include "advstep_frontend.h"
+#include "advstep_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kFrames = 64;   // frames per projection tile (one wave per coefficient chunk)
-constexpr float kAmin = 1e-10f;
-constexpr float kDbScale = 4.342944819032518f;  // 10 / ln(10)
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-
-__device__ __forceinline__ float max_nan(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return a > b ? a : b;
-}
 
 __device__ __forceinline__ float block_max(float v, float *lds) {
 #pragma unroll
@@ -43,11 +32,6 @@ __device__ __forceinline__ float block_sum(float v, float *lds) {
     float r = lds[0];
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += lds[w];
     return r;
-}
-
-// d/d band of 10*log10(clamp(band, amin)), band recovered from its dB value
-__device__ __forceinline__ float dlog_of_db(float db) {
-    return (db > -100.0f) ? kDbScale / expf(db * 0.23025850929940457f) : 0.0f;
 }
 
 // Layouts (the STFT's native one: torch.stft returns a (B, F, NF) VIEW of a (B, NF, F) buffer): everything here is
@@ -222,7 +206,6 @@ __global__ __launch_bounds__(kBlock) void lfcc_project_backward_kernel(const flo
 // Specialised for M = 128, K = 80 (LFCC); other sizes use the VALU kernels above.
 // ---------------------------------------------------------------------------------------------------------
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kLfccM = 128, kLfccK = 80;
 constexpr int kPTile = 64, kPThreads = 256;                          // frames / threads per workgroup
 constexpr int kBandPitch = kLfccM + 4, kCepPitch = kLfccK + 4;       // 132, 84 words
@@ -561,14 +544,7 @@ __global__ __launch_bounds__(kBlock) void stft_overlap_add_kernel(const float *_
     dx[b * T + t] = acc;
 }
 
-constexpr int64_t kMaxGridY = 65535;
-
 }  // namespace
-
-#define LFCC_REQUIRE(cond) \
-    do {                   \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
 
 extern "C" {
 
@@ -579,10 +555,10 @@ size_t advstep_lfcc_block_count(int64_t B, int64_t M, int64_t NF) {
 
 int advstep_lfcc_bands_f32(const float *spec, const int32_t *fb_start, const float *fb_w, int64_t span, float *band_db,
                            float *block_max, int64_t B, int64_t F, int64_t M, int64_t NF, advstep_stream_t stream) {
-    LFCC_REQUIRE(B >= 0 && F >= 0 && M >= 0 && NF >= 0 && span >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && F >= 0 && M >= 0 && NF >= 0 && span >= 1);
     if (B == 0 || M == 0 || NF == 0) return ADVSTEP_OK;
-    LFCC_REQUIRE(spec && fb_start && fb_w && band_db && block_max && B <= kMaxGridY && M * NF <= INT32_MAX &&
-                 F * NF <= INT32_MAX);
+    ADVSTEP_REQUIRE(spec && fb_start && fb_w && band_db && block_max && B <= kMaxGridY && M * NF <= INT32_MAX &&
+                    F * NF <= INT32_MAX);
     const dim3 grid((unsigned)ceil_div(M * NF, kBlock), (unsigned)B);
     hipLaunchKernelGGL(lfcc_bands_kernel, grid, dim3(kBlock), 0, as_stream(stream),
                        reinterpret_cast<const float2 *>(spec), fb_start, fb_w, (int)span, band_db, block_max, (int)F,
@@ -591,16 +567,16 @@ int advstep_lfcc_bands_f32(const float *spec, const int32_t *fb_start, const flo
 }
 
 int advstep_lfcc_reduce_max_f32(const float *block_max, int64_t n, float *stats, advstep_stream_t stream) {
-    LFCC_REQUIRE(n >= 1 && block_max && stats);
+    ADVSTEP_REQUIRE(n >= 1 && block_max && stats);
     hipLaunchKernelGGL(lfcc_reduce_max_kernel, dim3(1), dim3(1024), 0, as_stream(stream), block_max, n, stats);
     return status_after_launch();
 }
 
 int advstep_lfcc_project_f32(const float *band_db, const float *dct, float *stats, float top_db, float *out, int64_t B,
                              int64_t M, int64_t NF, int64_t K, advstep_stream_t stream) {
-    LFCC_REQUIRE(B >= 0 && M >= 0 && M <= kMaxBands && NF >= 0 && (K == 80 || K == 40 || K == 20));
+    ADVSTEP_REQUIRE(B >= 0 && M >= 0 && M <= kMaxBands && NF >= 0 && (K == 80 || K == 40 || K == 20));
     if (B == 0 || NF == 0) return ADVSTEP_OK;
-    LFCC_REQUIRE(band_db && dct && stats && out && B <= kMaxGridY && M <= INT32_MAX && NF <= INT32_MAX);
+    ADVSTEP_REQUIRE(band_db && dct && stats && out && B <= kMaxGridY && M <= INT32_MAX && NF <= INT32_MAX);
     const dim3 grid((unsigned)ceil_div(NF, kFrames), (unsigned)B);
     hipStream_t st = as_stream(stream);
     if (K == 80)
@@ -618,7 +594,7 @@ size_t advstep_lfcc_project_fragment_floats(int64_t M, int64_t K) {
 
 int advstep_lfcc_project_prepare_f32(const float *dct, int64_t M, int64_t K, float *frag, advstep_stream_t stream) {
     if (!(M == kLfccM && K == kLfccK)) return ADVSTEP_OK;          // no matrix-core path for this size: nothing to prepare
-    LFCC_REQUIRE(dct && frag && (reinterpret_cast<uintptr_t>(frag) & 15u) == 0);
+    ADVSTEP_REQUIRE(dct && frag && (reinterpret_cast<uintptr_t>(frag) & 15u) == 0);
     hipLaunchKernelGGL(lfcc_project_prepare_kernel, dim3((unsigned)ceil_div(2 * kFragFloats, kBlock)), dim3(kBlock), 0,
                        as_stream(stream), dct, frag);
     return status_after_launch();
@@ -627,13 +603,13 @@ int advstep_lfcc_project_prepare_f32(const float *dct, int64_t M, int64_t K, flo
 int advstep_lfcc_max_project_f32(const float *band_db, const float *dct, const float *frag, const float *block_max, int64_t n,
                                  float *stats, float top_db, float *out, int64_t B, int64_t M, int64_t NF, int64_t K,
                                  advstep_stream_t stream) {
-    LFCC_REQUIRE(n >= 1 && block_max && stats);
+    ADVSTEP_REQUIRE(n >= 1 && block_max && stats);
     if (!(K == kLfccK && M == kLfccM) || !frag || B <= 0 || NF <= 0 || n > INT32_MAX) {      // other sizes: the two launches
         const int st = advstep_lfcc_reduce_max_f32(block_max, n, stats, stream);
         return st != ADVSTEP_OK ? st : advstep_lfcc_project_f32(band_db, dct, stats, top_db, out, B, M, NF, K, stream);
     }
-    LFCC_REQUIRE(band_db && out && B * NF <= INT32_MAX && (reinterpret_cast<uintptr_t>(frag) & 15u) == 0 &&
-                 (reinterpret_cast<uintptr_t>(band_db) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0);
+    ADVSTEP_REQUIRE(band_db && out && B * NF <= INT32_MAX && (reinterpret_cast<uintptr_t>(frag) & 15u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(band_db) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0);
     // every workgroup reduces the block maxima itself: fine for the fused STFT kernel's 26 per utterance (13 KB at B = 128), not for
     // advstep_lfcc_bands_f32's 202 per utterance (100 KB x 808 workgroups) - those are reduced by one launch first and the
     // projection is handed stats[0] as a one-entry array (which it then leaves alone)
@@ -651,9 +627,9 @@ int advstep_lfcc_max_project_f32(const float *band_db, const float *dct, const f
 int advstep_lfcc_project_backward_f32(const float *dout, const float *dct, const float *band_db, float *stats,
                                       float top_db, float *dband, int64_t B, int64_t M, int64_t NF, int64_t K,
                                       advstep_stream_t stream) {
-    LFCC_REQUIRE(B >= 0 && M >= 0 && M <= kMaxBands && NF >= 0 && (K == 80 || K == 40 || K == 20));
+    ADVSTEP_REQUIRE(B >= 0 && M >= 0 && M <= kMaxBands && NF >= 0 && (K == 80 || K == 40 || K == 20));
     if (B == 0 || NF == 0 || M == 0) return ADVSTEP_OK;
-    LFCC_REQUIRE(dout && dct && band_db && stats && dband && B <= kMaxGridY && M <= INT32_MAX && NF <= INT32_MAX);
+    ADVSTEP_REQUIRE(dout && dct && band_db && stats && dband && B <= kMaxGridY && M <= INT32_MAX && NF <= INT32_MAX);
     const dim3 grid((unsigned)ceil_div(NF, kFrames), (unsigned)B);
     hipStream_t st = as_stream(stream);
     if (K == 80)
@@ -668,15 +644,15 @@ int advstep_lfcc_project_backward_f32(const float *dout, const float *dct, const
 int advstep_lfcc_project_backward_zero_f32(const float *dout, const float *dct, const float *frag, const float *band_db,
                                            float *stats, float top_db, float *dband, int64_t B, int64_t M, int64_t NF,
                                            int64_t K, float *zero, int64_t zero_n, advstep_stream_t stream) {
-    LFCC_REQUIRE(zero_n >= 0 && (zero || zero_n == 0));
+    ADVSTEP_REQUIRE(zero_n >= 0 && (zero || zero_n == 0));
     if (!(K == kLfccK && M == kLfccM) || !frag || B <= 0 || NF <= 0) {             // other sizes: a memset node + the plain call
         if (zero_n > 0 && hipMemsetAsync(zero, 0, (size_t)zero_n * sizeof(float), as_stream(stream)) != hipSuccess)
             return ADVSTEP_ELAUNCH;
         return advstep_lfcc_project_backward_f32(dout, dct, band_db, stats, top_db, dband, B, M, NF, K, stream);
     }
-    LFCC_REQUIRE(dout && band_db && stats && dband && B * NF <= INT32_MAX && (reinterpret_cast<uintptr_t>(frag) & 15u) == 0 &&
-                 (reinterpret_cast<uintptr_t>(dout) & 15u) == 0 && (reinterpret_cast<uintptr_t>(band_db) & 15u) == 0 &&
-                 (reinterpret_cast<uintptr_t>(dband) & 15u) == 0);
+    ADVSTEP_REQUIRE(dout && band_db && stats && dband && B * NF <= INT32_MAX && (reinterpret_cast<uintptr_t>(frag) & 15u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(dout) & 15u) == 0 && (reinterpret_cast<uintptr_t>(band_db) & 15u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(dband) & 15u) == 0);
     hipLaunchKernelGGL(lfcc_project_backward_mfma_kernel, dim3((unsigned)ceil_div(B * NF, kPTile)), dim3(kPThreads), 0,
                        as_stream(stream), dout, frag, band_db, stats, top_db, dband, B * NF, zero_n > 0 ? zero : nullptr, zero_n);
     return status_after_launch();
@@ -684,9 +660,9 @@ int advstep_lfcc_project_backward_zero_f32(const float *dout, const float *dct, 
 
 int advstep_lfcc_floor_fixup_f32(const float *band_db, const float *stats, float *dband, int64_t n,
                                  advstep_stream_t stream) {
-    LFCC_REQUIRE(n >= 0);
+    ADVSTEP_REQUIRE(n >= 0);
     if (n == 0) return ADVSTEP_OK;
-    LFCC_REQUIRE(band_db && stats && dband);
+    ADVSTEP_REQUIRE(band_db && stats && dband);
     const int64_t blocks = ceil_div(n, kBlock);
     hipLaunchKernelGGL(lfcc_floor_fixup_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kBlock), 0,
                        as_stream(stream), band_db, stats, dband, n);
@@ -696,9 +672,9 @@ int advstep_lfcc_floor_fixup_f32(const float *band_db, const float *stats, float
 int advstep_lfcc_bands_backward_f32(const float *dband, const float *spec, const int32_t *fbt_start, const float *fbt_w,
                                     int64_t span_t, float *dspec, int64_t B, int64_t F, int64_t M, int64_t NF,
                                     int hermitian_half, advstep_stream_t stream) {
-    LFCC_REQUIRE(B >= 0 && F >= 0 && M >= 0 && NF >= 0 && span_t >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && F >= 0 && M >= 0 && NF >= 0 && span_t >= 1);
     if (B == 0 || F == 0 || NF == 0) return ADVSTEP_OK;
-    LFCC_REQUIRE(dband && spec && fbt_start && fbt_w && dspec && B <= kMaxGridY && F * NF <= INT32_MAX);
+    ADVSTEP_REQUIRE(dband && spec && fbt_start && fbt_w && dspec && B <= kMaxGridY && F * NF <= INT32_MAX);
     const dim3 grid((unsigned)ceil_div(F * NF, kBlock), (unsigned)B);
     hipLaunchKernelGGL(lfcc_bands_backward_kernel, grid, dim3(kBlock), 0, as_stream(stream), dband,
                        reinterpret_cast<const float2 *>(spec), fbt_start, fbt_w, (int)span_t,
@@ -708,11 +684,11 @@ int advstep_lfcc_bands_backward_f32(const float *dband, const float *spec, const
 
 int advstep_stft_frames_f32(const float *x, const float *window, float *frames, int64_t B, int64_t T, int64_t NF,
                             int64_t hop, int64_t nfft, advstep_stream_t stream) {
-    LFCC_REQUIRE(B >= 0 && T >= 0 && NF >= 0 && hop >= 1 && nfft >= 4 && nfft % 4 == 0);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && NF >= 0 && hop >= 1 && nfft >= 4 && nfft % 4 == 0);
     if (B == 0 || NF == 0) return ADVSTEP_OK;
     const int64_t pad = nfft / 2;
-    LFCC_REQUIRE(x && window && frames && B <= kMaxGridY && T > pad && (NF - 1) * hop + nfft - pad <= T + pad &&
-                 T + nfft <= INT32_MAX && ((reinterpret_cast<uintptr_t>(frames) & 15u) == 0));
+    ADVSTEP_REQUIRE(x && window && frames && B <= kMaxGridY && T > pad && (NF - 1) * hop + nfft - pad <= T + pad &&
+                    T + nfft <= INT32_MAX && ((reinterpret_cast<uintptr_t>(frames) & 15u) == 0));
     const dim3 grid((unsigned)ceil_div(NF * (nfft / 4), kBlock), (unsigned)B);
     hipLaunchKernelGGL(stft_frames_kernel, grid, dim3(kBlock), 0, as_stream(stream), x, window, frames, (int)T, (int)NF,
                        (int)hop, (int)nfft, (int)pad);
@@ -721,10 +697,10 @@ int advstep_stft_frames_f32(const float *x, const float *window, float *frames, 
 
 int advstep_stft_overlap_add_f32(const float *dframes, const float *window, float *dx, int64_t B, int64_t T, int64_t NF,
                                  int64_t hop, int64_t nfft, advstep_stream_t stream) {
-    LFCC_REQUIRE(B >= 0 && T >= 0 && NF >= 0 && hop >= 1 && nfft >= 4);
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && NF >= 0 && hop >= 1 && nfft >= 4);
     if (B == 0 || T == 0) return ADVSTEP_OK;
     const int64_t pad = nfft / 2;
-    LFCC_REQUIRE(dframes && window && dx && B <= kMaxGridY && T > pad && T + nfft <= INT32_MAX);
+    ADVSTEP_REQUIRE(dframes && window && dx && B <= kMaxGridY && T > pad && T + nfft <= INT32_MAX);
     const dim3 grid((unsigned)ceil_div(T, kBlock), (unsigned)B);
     hipLaunchKernelGGL(stft_overlap_add_kernel, grid, dim3(kBlock), 0, as_stream(stream), dframes, window, dx, (int)T,
                        (int)NF, (int)hop, (int)nfft, (int)pad);

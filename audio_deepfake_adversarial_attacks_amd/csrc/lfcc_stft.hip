@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "advstep_frontend.h"
+#include "advstep_common.h"
 
 namespace {
 
@@ -30,15 +31,6 @@ constexpr int kBins = kN + 1;      // one-sided spectrum
 constexpr int kWavesPerBlock = 4;
 constexpr int kThreads = kWavesPerBlock * 64;
 constexpr int kFramesPerBlockBwd = 4;   // one per wave: 35 KB of LDS per workgroup = 4 workgroups (16 waves) per CU
-constexpr float kAmin = 1e-10f;
-// d/d band of 10 log10(clamp(band, amin)), band recovered from its dB value (the same function as in lfcc.hip)
-__device__ __forceinline__ float dlog_of_db(float db) {
-    return (db > -100.0f) ? 4.342944819032518f / expf(db * 0.23025850929940457f) : 0.0f;
-}
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
@@ -52,12 +44,6 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ float max_nan(float a, float b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return a > b ? a : b;
 }
 
 // ---- round 4: the 256-point transform as 16 x 16 with the 16-point transforms in REGISTERS --------------------------------
@@ -1442,34 +1428,24 @@ __global__ __launch_bounds__(kThreads) void stft_mel_backward_out_reg_kernel(con
     }
 }
 
-constexpr int64_t kMaxGridY = 65535;
-
 // ADVSTEP_STFT_REG=0 (read per call): the radix-4 in-LDS kernels of rounds 1 - 3 for the LFCC pair (A/B measurements)
 inline bool reg_fft_enabled() {
     const char *e = getenv("ADVSTEP_STFT_REG");
     return !(e && e[0] == '0');
 }
 
-}  // namespace
-
-#define STFT_REQUIRE(cond) \
-    do {                   \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
-namespace {
 // band_db / stats: null, or the dB rows and the statistics the floor fix-up needs (see the kernel); dx_is_zero: the caller
 // (advstep_lfcc_project_backward_zero_f32) has already zero-filled dx on this stream
 int stft_bands_backward_launch(const float *x, const float *window, const float *dband, const int32_t *fbt_start, const float *fbt_w,
                                int64_t span_t, float *dx, int64_t B, int64_t T, int64_t NF, int64_t hop, int64_t nfft, int64_t M,
                                const float *band_db, const float *stats, int dx_is_zero, advstep_stream_t stream) {
-    STFT_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span_t >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span_t >= 1);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    STFT_REQUIRE(x && window && dband && fbt_start && fbt_w && dx && B <= kMaxGridY);
-    STFT_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop && span_t <= kMaxSpanT && M <= kMaxBands);
+    ADVSTEP_REQUIRE(x && window && dband && fbt_start && fbt_w && dx && B <= kMaxGridY);
+    ADVSTEP_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop && span_t <= kMaxSpanT && M <= kMaxBands);
     // a sample may be reached by at most two workgroups (two-operand float atomics commute): a workgroup's frames must
     // advance by at least the overlap between neighbouring workgroups' ranges
-    STFT_REQUIRE(kFramesPerBlockBwd * hop >= kNfft - hop);
+    ADVSTEP_REQUIRE(kFramesPerBlockBwd * hop >= kNfft - hop);
     hipStream_t st = as_stream(stream);
     if (!dx_is_zero && hipMemsetAsync(dx, 0, (size_t)B * T * sizeof(float), st) != hipSuccess) return ADVSTEP_ELAUNCH;
     const bool reg = reg_fft_enabled();
@@ -1510,15 +1486,15 @@ int advstep_stft_bands_supported(int64_t nfft, int64_t hop, int64_t T) {
 int advstep_stft_bands_f32(const float *x, const float *window, const int32_t *fb_start, const float *fb_w, int64_t span,
                            float *band_db, float *block_max, int64_t B, int64_t T, int64_t NF, int64_t hop, int64_t nfft,
                            int64_t M, advstep_stream_t stream) {
-    STFT_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span >= 1);
     if (B == 0 || NF == 0 || M == 0) return ADVSTEP_OK;
-    STFT_REQUIRE(x && window && fb_start && fb_w && band_db && block_max && B <= kMaxGridY);
-    STFT_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
+    ADVSTEP_REQUIRE(x && window && fb_start && fb_w && band_db && block_max && B <= kMaxGridY);
+    ADVSTEP_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
     if (reg_fft_enabled() && span <= kRegSpan && M <= kMaxBands) {
         // the unused tail of block_max (sized for the radix-4 kernel's 16-frame workgroups) must not hold garbage: the
         // reduction over it reads advstep_stft_bands_block_count entries
         const int64_t blocks32 = ceil_div(NF, kBandsFramesPerBlock), blocks16 = ceil_div(NF, kFramesPerBlockFwd);
-        STFT_REQUIRE(B * blocks16 <= INT32_MAX);
+        ADVSTEP_REQUIRE(B * blocks16 <= INT32_MAX);
         const dim3 grid((unsigned)blocks32, (unsigned)B);
         hipLaunchKernelGGL(stft_bands_reg_kernel, grid, dim3(kThreads), 0, as_stream(stream), x, window, fb_start, fb_w, (int)span,
                            band_db, block_max, (int)T, (int)NF, (int)hop, (int)M, (int)(B * (blocks16 - blocks32)));
@@ -1541,7 +1517,7 @@ int advstep_stft_bands_backward_fixup_f32(const float *x, const float *window, f
                                           const float *stats, const int32_t *fbt_start, const float *fbt_w, int64_t span_t,
                                           float *dx, int dx_is_zero, int64_t B, int64_t T, int64_t NF, int64_t hop,
                                           int64_t nfft, int64_t M, advstep_stream_t stream) {
-    STFT_REQUIRE(band_db && stats);
+    ADVSTEP_REQUIRE(band_db && stats);
     if (!reg_fft_enabled()) {                 // the radix-4 kernels have no folded fix-up: its own launch, on dband in place
         if (B > 0 && NF > 0 && M > 0) {
             const int st = advstep_lfcc_floor_fixup_f32(band_db, stats, dband, B * NF * M, stream);
@@ -1557,10 +1533,10 @@ int advstep_stft_bands_backward_fixup_f32(const float *x, const float *window, f
 int advstep_stft_mel_f32(const float *x, const float *window, const int32_t *fb_start, const float *fb_w, int64_t span,
                          float *out, int64_t B, int64_t T, int64_t NF, int64_t hop, int64_t nfft, int64_t M,
                          advstep_stream_t stream) {
-    STFT_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span >= 1);
     if (B == 0 || NF == 0 || M == 0) return ADVSTEP_OK;
-    STFT_REQUIRE(x && window && fb_start && fb_w && out && B <= kMaxGridY && M <= kMelMax && span <= kMelMaxSpan);
-    STFT_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
+    ADVSTEP_REQUIRE(x && window && fb_start && fb_w && out && B <= kMaxGridY && M <= kMelMax && span <= kMelMaxSpan);
+    ADVSTEP_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
     hipStream_t st = as_stream(stream);
     if (reg_fft_enabled() && span <= kMelRegSpan) {
         const size_t lds_reg = sizeof(LdsMelReg);
@@ -1585,12 +1561,12 @@ int advstep_stft_mel_backward_f32(const float *x, const float *window, const flo
                                   const float *fb_w, int64_t span, const int32_t *fbt_start, const float *fbt_w,
                                   int64_t span_t, float *dx, int64_t B, int64_t T, int64_t NF, int64_t hop, int64_t nfft,
                                   int64_t M, advstep_stream_t stream) {
-    STFT_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span >= 1 && span_t >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span >= 1 && span_t >= 1);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    STFT_REQUIRE(x && window && dout && fb_start && fb_w && fbt_start && fbt_w && dx && B <= kMaxGridY && M <= kMelMax &&
-                 span <= kMelMaxSpan && span_t <= kMaxSpanT);
-    STFT_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
-    STFT_REQUIRE(kFramesPerBlockBwd * hop >= kNfft - hop);
+    ADVSTEP_REQUIRE(x && window && dout && fb_start && fb_w && fbt_start && fbt_w && dx && B <= kMaxGridY && M <= kMelMax &&
+                    span <= kMelMaxSpan && span_t <= kMaxSpanT);
+    ADVSTEP_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
+    ADVSTEP_REQUIRE(kFramesPerBlockBwd * hop >= kNfft - hop);
     hipStream_t st = as_stream(stream);
     if (hipMemsetAsync(dx, 0, (size_t)B * T * sizeof(float), st) != hipSuccess) return ADVSTEP_ELAUNCH;
     const size_t lds = sizeof(LdsMelBwd);
@@ -1609,11 +1585,11 @@ int advstep_stft_mel_backward_f32(const float *x, const float *window, const flo
 int advstep_stft_mel_backward_from_output_f32(const float *window, const float *dout, const float *out, const int32_t *fbt_start,
                                               const float *fbt_w, int64_t span_t, float *dx, int64_t B, int64_t T, int64_t NF,
                                               int64_t hop, int64_t nfft, int64_t M, advstep_stream_t stream) {
-    STFT_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span_t >= 1);
+    ADVSTEP_REQUIRE(B >= 0 && NF >= 0 && M >= 0 && span_t >= 1);
     if (B == 0 || T == 0) return ADVSTEP_OK;
-    STFT_REQUIRE(window && dout && out && fbt_start && fbt_w && dx && B <= kMaxGridY && M <= kMelMax && span_t <= kMaxSpanT);
-    STFT_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
-    STFT_REQUIRE(kFramesPerBlockBwd * hop >= kNfft - hop);
+    ADVSTEP_REQUIRE(window && dout && out && fbt_start && fbt_w && dx && B <= kMaxGridY && M <= kMelMax && span_t <= kMaxSpanT);
+    ADVSTEP_REQUIRE(advstep_stft_bands_supported(nfft, hop, T) && NF == 1 + T / hop);
+    ADVSTEP_REQUIRE(kFramesPerBlockBwd * hop >= kNfft - hop);
     hipStream_t st = as_stream(stream);
     if (hipMemsetAsync(dx, 0, (size_t)B * T * sizeof(float), st) != hipSuccess) return ADVSTEP_ELAUNCH;
     if (reg_fft_enabled()) {

@@ -16,14 +16,9 @@
 #include <stdint.h>
 
 #include "advstep_lcnn.h"
+#include "advstep_common.h"
 
 namespace {
-
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-
-// workgroup barrier that orders LDS traffic only (see lcnn_lstm.hip)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // gx (T, B, D, 3H), w_hh (D, 3H, H), b_hh (D, 3H), out (T, B, D*H), saved (T, B, D, 4H) = r, z, n, a_n
 template <int H>
@@ -160,20 +155,15 @@ __global__ __launch_bounds__(3 * H) void gru_backward_kernel(const float *__rest
 
 }  // namespace
 
-#define GRU_REQUIRE(cond) \
-    do {                  \
-        if (!(cond)) return ADVSTEP_EINVAL; \
-    } while (0)
-
 extern "C" {
 
 int advstep_gru_supported(int64_t H) { return H == 64; }
 
 int advstep_gru_forward_f32(const float *gx, const float *w_hh, const float *b_hh, float *out, float *saved, int64_t T,
                             int64_t B, int64_t D, int64_t H, advstep_stream_t stream) {
-    GRU_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_gru_supported(H));
+    ADVSTEP_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_gru_supported(H));
     if (T == 0 || B == 0) return ADVSTEP_OK;
-    GRU_REQUIRE(gx && w_hh && b_hh && out && saved && T <= INT32_MAX && B <= 65535);
+    ADVSTEP_REQUIRE(gx && w_hh && b_hh && out && saved && T <= INT32_MAX && B <= 65535);
     hipLaunchKernelGGL(gru_forward_kernel<64>, dim3((unsigned)B, (unsigned)D), dim3(192), 0, as_stream(stream), gx, w_hh,
                        b_hh, out, saved, (int)T, (int)B, (int)D);
     return status_after_launch();
@@ -181,9 +171,9 @@ int advstep_gru_forward_f32(const float *gx, const float *w_hh, const float *b_h
 
 int advstep_gru_backward_f32(const float *dout, const float *w_hh, const float *saved, const float *out, float *dgx,
                              int64_t T, int64_t B, int64_t D, int64_t H, advstep_stream_t stream) {
-    GRU_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_gru_supported(H));
+    ADVSTEP_REQUIRE(T >= 0 && B >= 0 && (D == 1 || D == 2) && advstep_gru_supported(H));
     if (T == 0 || B == 0) return ADVSTEP_OK;
-    GRU_REQUIRE(dout && w_hh && saved && out && dgx && T <= INT32_MAX && B <= 65535);
+    ADVSTEP_REQUIRE(dout && w_hh && saved && out && dgx && T <= INT32_MAX && B <= 65535);
     hipLaunchKernelGGL(gru_backward_kernel<64>, dim3((unsigned)B, (unsigned)D), dim3(192), 0, as_stream(stream), dout,
                        w_hh, saved, out, dgx, (int)T, (int)B, (int)D);
     return status_after_launch();

@@ -14,16 +14,12 @@
 #include <stdint.h>
 
 #include "advstep_dataset.h"
+#include "advstep_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kPerThread = 4;
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float decode(const float *p, int64_t i) { return p[i]; }
 // torchaudio.load(normalize=True) for 16-bit PCM: sample / 2^15 (exact in float32)
