@@ -2,9 +2,10 @@
 
 `torch.fft.rfft` / `irfft` on ROCm clone their input first (hipFFT may overwrite it; the c2r transform always does),
 which costs two 106 MB device copies per PGD iteration at B = 128.  The frontend's FFT inputs are scratch tensors it
-owns, so it can hand them to hipFFT as they are.  Plans are cached per (device, batch, n_fft, direction) and always
-execute on torch's current stream.  If the hipFFT handle cannot be created the callers fall back to torch.fft — the
-same library underneath, only with the defensive copies."""
+owns, so it can hand them to hipFFT as they are.  Plans are cached per (device, launch stream, batch, n_fft, direction)
+and execute on that stream: a plan's work area (if rocFFT gives it one) is never shared by two streams that run at the
+same time, such as the two lanes of evaluation.generate_attacks.  If the hipFFT handle cannot be created the callers
+fall back to torch.fft — the same library underneath, only with the defensive copies."""
 from __future__ import annotations
 
 import ctypes
@@ -16,7 +17,7 @@ import torch
 _HIPFFT_R2C, _HIPFFT_C2R = 0x2A, 0x2C
 _lib: Optional[ctypes.CDLL] = None
 _lib_failed = False
-_plans: Dict[Tuple[int, int, int, int], ctypes.c_void_p] = {}
+_plans: Dict[Tuple[int, int, int, int, int], ctypes.c_void_p] = {}     # (device, stream handle, batch, n_fft, kind)
 
 
 def _load() -> Optional[ctypes.CDLL]:
@@ -46,11 +47,11 @@ def _load() -> Optional[ctypes.CDLL]:
     return None
 
 
-def _plan(device: torch.device, batch: int, nfft: int, kind: int) -> Optional[ctypes.c_void_p]:
+def _plan(device: torch.device, stream: int, batch: int, nfft: int, kind: int) -> Optional[ctypes.c_void_p]:
     lib = _load()
     if lib is None:
         return None
-    key = (device.index if device.index is not None else torch.cuda.current_device(), batch, nfft, kind)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), stream, batch, nfft, kind)
     plan = _plans.get(key)
     if plan is None:
         handle = ctypes.c_void_p()
@@ -67,11 +68,11 @@ def rfft_into(frames: torch.Tensor, spec_real: torch.Tensor) -> bool:
     """frames (batch, nfft) f32 contiguous -> spec_real (batch, nfft//2+1, 2) f32 (interleaved complex), unnormalised.
     `frames` may be overwritten.  Returns False when hipFFT is unavailable (caller falls back to torch.fft)."""
     batch, nfft = frames.shape
-    plan = _plan(frames.device, batch, nfft, _HIPFFT_R2C)
+    stream = torch.cuda.current_stream(frames.device).cuda_stream
+    plan = _plan(frames.device, stream, batch, nfft, _HIPFFT_R2C)
     if plan is None:
         return False
     with torch.cuda.device(frames.device):
-        stream = torch.cuda.current_stream(frames.device).cuda_stream
         ok = _lib.hipfftSetStream(plan, stream) == 0 and _lib.hipfftExecR2C(plan, frames.data_ptr(), spec_real.data_ptr()) == 0
     return ok
 
@@ -79,10 +80,10 @@ def rfft_into(frames: torch.Tensor, spec_real: torch.Tensor) -> bool:
 def irfft_into(spec_real: torch.Tensor, frames: torch.Tensor) -> bool:
     """spec_real (batch, nfft//2+1, 2) -> frames (batch, nfft), unnormalised c2r; `spec_real` IS overwritten."""
     batch, nfft = frames.shape
-    plan = _plan(frames.device, batch, nfft, _HIPFFT_C2R)
+    stream = torch.cuda.current_stream(frames.device).cuda_stream
+    plan = _plan(frames.device, stream, batch, nfft, _HIPFFT_C2R)
     if plan is None:
         return False
     with torch.cuda.device(frames.device):
-        stream = torch.cuda.current_stream(frames.device).cuda_stream
         ok = _lib.hipfftSetStream(plan, stream) == 0 and _lib.hipfftExecC2R(plan, spec_real.data_ptr(), frames.data_ptr()) == 0
     return ok

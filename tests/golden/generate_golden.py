@@ -808,8 +808,41 @@ def main(out_dir=None):
         print(f"{p.name}: {p.stat().st_size / 1e6:.2f} MB")
 
 
+# ---- fixtures of CPUs without AVX-512 ----------------------------------------------------------------------------------------
+# The reference's CPU results are bit-exact only for one set of torch CPU kernels: oneDNN, MKL and ATen pick AVX-512 or AVX2 code
+# paths by CPU, and the two round differently.  The committed fixtures are the AVX-512 ones; for the fixtures the bit-exact CPU
+# tests read, <name>_avx2.npz holds the arrays that come out differently when the reference runs on the AVX2 paths, as the XOR
+# of their bit patterns with the committed array (exact, and it compresses: the two differ in low mantissa bits).  Recipe:
+#   ATEN_CPU_CAPABILITY=avx2 DNNL_MAX_CPU_ISA=AVX2 MKL_ENABLE_INSTRUCTIONS=AVX2 python tests/golden/generate_golden.py --out DIR
+#   python tests/golden/generate_golden.py --isa-overlay DIR avx2
+# tests/helpers.py::golden_for_this_cpu applies it where torch runs its AVX2 kernels.
+ISA_OVERLAY_FIXTURES = ("fgsm", "pgd_linf", "pgd_l2", "cw", "trainer", "lcnn_body", "specrnet_body", "rawnet3_body")
+
+
+def write_isa_overlay(regenerated_dir, tag):
+    for name in ISA_OVERLAY_FIXTURES:
+        new, old = np.load(Path(regenerated_dir) / f"{name}.npz"), np.load(HERE / f"{name}.npz")
+        assert set(new.files) == set(old.files), name
+        out = {}
+        for k in old.files:
+            a, b = new[k], old[k]
+            if a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes():
+                continue
+            assert a.shape == b.shape, (name, k)
+            if a.dtype.kind in "fiu" and a.dtype == b.dtype:
+                u = np.dtype(f"u{a.itemsize}")
+                out[k] = a.view(u) ^ b.view(u)
+            else:                                       # text (training logs): the value itself
+                out["raw__" + k] = a
+        if out:
+            np.savez_compressed(HERE / f"{name}_{tag}.npz", **out)
+            print(f"{name}_{tag}.npz: {len(out)} arrays, {(HERE / f'{name}_{tag}.npz').stat().st_size / 1e6:.2f} MB")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["frontends_batch_floor"]:      # third-party code only: does not need the reference tree
+    if sys.argv[1:2] == ["--isa-overlay"]:             # the overlay of a recipe run on other CPU kernels (see above)
+        write_isa_overlay(sys.argv[2], sys.argv[3])
+    elif sys.argv[1:] == ["frontends_batch_floor"]:    # third-party code only: does not need the reference tree
         gen_frontends_batch_floor()
     elif sys.argv[1:] == ["attack_save"]:              # one fixture, same set-up as main()
         _import_reference()

@@ -1,6 +1,29 @@
 """Shared test helpers: the surrogate detector of the golden fixtures and small generators."""
+from pathlib import Path
+
 import numpy as np
 import torch
+
+GOLDEN = Path(__file__).resolve().parent / "golden"
+
+
+def golden_for_this_cpu(golden, name: str) -> dict:
+    """golden(name) as the reference computes it with the CPU kernels torch runs here.  The committed fixtures were recorded on
+    the AVX-512 code paths; where torch runs its AVX2 kernels, <name>_avx2.npz (tests/golden/generate_golden.py, "fixtures of
+    CPUs without AVX-512") supplies the arrays that round differently there, as the XOR of their bit patterns."""
+    g = golden(name)
+    overlay = GOLDEN / f"{name}_avx2.npz"
+    if torch.backends.cpu.get_cpu_capability() != "AVX2" or not overlay.exists():
+        return g
+    g = dict(g)
+    with np.load(overlay) as ov:
+        for k in ov.files:
+            if k.startswith("raw__"):
+                g[k[len("raw__"):]] = ov[k]
+            else:
+                base = g[k]
+                g[k] = (base.view(ov[k].dtype) ^ ov[k]).view(base.dtype)
+    return g
 
 
 class Surrogate(torch.nn.Module):

@@ -253,7 +253,8 @@ def test_specrnet_uses_fused_mel_frontend(cuda, monkeypatch):
 
 
 def test_fused_mfcc_matches_torch_chain(cuda, monkeypatch):
-    """MFCC = the LFCC structure with a 128-band mel filterbank (up to 6 bands per bin): same fused kernels."""
+    """MFCC = the LFCC structure with a 128-band mel filterbank (at most 2 bands per bin, like the linear bank): same fused
+    kernels.  Banks with more bands per bin: tests/test_gpu_frontend_f64.py."""
     from audio_deepfake_adversarial_attacks_amd.frontends import MFCC
     fe = MFCC().to(cuda)
     gen = torch.Generator().manual_seed(21)

@@ -177,3 +177,28 @@ def test_two_batches_in_flight_give_the_same_scores(cuda, fresh_graphs):
     # the default for a graph-replayed attack is two in flight
     default, g3 = evaluate(None)
     assert g3 == 2 and torch.equal(torch.as_tensor(default["scores"]["y_pred"]), torch.as_tensor(one["scores"]["y_pred"]))
+
+
+def test_two_batches_in_flight_with_hipfft_plans_give_the_same_scores(cuda, fresh_graphs, monkeypatch):
+    """ADVSTEP_INLDS_FFT=0: the frontend's FFTs run through the direct hipFFT plans (fft_plans.py), which are keyed by launch
+    stream, so the two lanes never share a plan or its work area: scores bit-identical to one batch at a time."""
+    from audio_deepfake_adversarial_attacks_amd import fft_plans, torchattacks
+    from audio_deepfake_adversarial_attacks_amd.datasets.synthetic import SyntheticDetectionDataset
+    from audio_deepfake_adversarial_attacks_amd.evaluation import generate_attacks
+    monkeypatch.setenv("ADVSTEP_INLDS_FFT", "0")
+    cfg = {"data": {"seed": 42}, "checkpoint": {"path": ""},
+           "model": {"name": "lcnn", "parameters": {"frontend_algorithm": ["lfcc"], "input_channels": 1}}}
+
+    def evaluate(in_flight):
+        torch.manual_seed(5)
+        fresh_graphs.clear()
+        return generate_attacks([None, None, None], cfg, str(cuda), attack_model_config=cfg, attack_method=torchattacks.PGD,
+                                attack_params={"eps": 0.003, "steps": 4}, batch_size=4, dataset=SyntheticDetectionDataset(24),
+                                share_weights=True, shuffle=False, num_workers=0, return_scores=True, in_flight=in_flight)
+
+    one = evaluate(1)
+    two = evaluate(2)
+    streams = {key[1] for key in fft_plans._plans}
+    assert len(streams) >= 2                              # the plans the lanes ran are their own
+    for k in ("y_pred", "y_pred_label", "y"):
+        assert torch.equal(torch.as_tensor(one["scores"][k]), torch.as_tensor(two["scores"][k])), k

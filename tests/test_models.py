@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from audio_deepfake_adversarial_attacks_amd.models import lcnn, models, rawnet3, sincfb, specrnet
+from tests.helpers import golden_for_this_cpu
 
 T = torch.from_numpy
 
@@ -31,7 +32,7 @@ def attack_mode(model):
 
 
 def test_lcnn_body_equals_reference(golden):
-    g = golden("lcnn_body")
+    g = golden_for_this_cpu(golden, "lcnn_body")
     body = lcnn.BaseLCNN(input_channels=1, num_coefficients=80).eval()
     body.load_state_dict(sd_of(g), strict=True)           # the reference's key names
     spec = T(g["spec"])
@@ -59,7 +60,7 @@ def test_lcnn_state_dict_layout():
 
 
 def test_specrnet_body_equals_reference(golden):
-    g = golden("specrnet_body")
+    g = golden_for_this_cpu(golden, "specrnet_body")
     body = specrnet.BaseSpecRNet(specrnet.get_config(2), device="cpu").eval()
     body.load_state_dict(sd_of(g), strict=True)
     with torch.no_grad():
@@ -180,7 +181,7 @@ def rawnet3_like_fixture(g):
 def test_rawnet3_body_equals_reference(golden):
     """src/models/rawnet3.py:81-137 (+ Bottle2neck / AFMS :161-274): logits and the attack-mode gradient w.r.t. the
     tensor leaving conv1, bit for bit."""
-    g = golden("rawnet3_body")
+    g = golden_for_this_cpu(golden, "rawnet3_body")
     model = rawnet3_like_fixture(g)
     model.conv1.h = T(g["h"])
     with torch.no_grad():

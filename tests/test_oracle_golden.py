@@ -6,7 +6,7 @@ import torch
 
 from oracle import attacks as OA
 from oracle import kernels as K
-from tests.helpers import surrogate_from
+from tests.helpers import golden_for_this_cpu, surrogate_from
 
 T = torch.from_numpy
 
@@ -130,20 +130,20 @@ def test_philox_random_start_statistics():
 # ---- whole attacks: oracle/attacks.py (torch ops in the reference's order) == reference, bit for bit --------------------
 
 def test_whole_attacks_bit_identical_to_reference(golden):
-    g = golden("fgsm")
+    g = golden_for_this_cpu(golden, "fgsm")
     m = surrogate_from(g)
     for e, eps in (("e0005", 0.0005), ("e00075", 0.00075), ("e001", 0.001)):
         with OA.attack_mode(m):
             adv = OA.fgsm(m, T(g[f"small_{e}_x"]), T(g[f"small_{e}_y"]), eps=eps)
         assert torch.equal(adv, T(g[f"small_{e}_adv"]))
-    g = golden("pgd_linf")
+    g = golden_for_this_cpu(golden, "pgd_linf")
     m = surrogate_from(g)
     for tag in ("ragged_rs", "small_nors"):
         with OA.attack_mode(m):
             adv = OA.pgd(m, T(g[tag + "_x"]), T(g[tag + "_y"]), eps=float(g[tag + "_eps"]), steps=int(g[tag + "_steps"]),
                          random_start=tag.endswith("_rs"), noise=T(g[tag + "_noise"]) if tag + "_noise" in g else None)
         assert torch.equal(adv, T(g[tag + "_adv"])), tag
-    g = golden("pgd_l2")
+    g = golden_for_this_cpu(golden, "pgd_l2")
     m = surrogate_from(g)
     for tag in ("ragged_rs", "small_nors"):
         draws = (T(g[tag + "_normal"]), T(g[tag + "_r"])) if tag + "_normal" in g else None
@@ -151,7 +151,7 @@ def test_whole_attacks_bit_identical_to_reference(golden):
             adv = OA.pgdl2(m, T(g[tag + "_x"]), T(g[tag + "_y"]), eps=float(g[tag + "_eps"]), steps=int(g[tag + "_steps"]),
                            random_start=tag.endswith("_rs"), draws=draws)
         assert torch.equal(adv, T(g[tag + "_adv"])), tag
-    g = golden("cw")
+    g = golden_for_this_cpu(golden, "cw")
     m = surrogate_from(g)
     with OA.attack_mode(m):
         best = OA.cw(m, T(g["x"]), T(g["y"]), c=float(g["c"]), steps=int(g["steps"]), lr=float(g["lr"]))

@@ -12,7 +12,7 @@ import torch
 from audio_deepfake_adversarial_attacks_amd import trainer as T
 from audio_deepfake_adversarial_attacks_amd.aa.aa_trainer_types import AdversarialGDTrainerEnum
 from oracle import torch_ops
-from tests.helpers import Surrogate, TinyDetectionSet
+from tests.helpers import Surrogate, TinyDetectionSet, golden_for_this_cpu
 
 RUNS = {
     "RANDOM": ["FGSM", "FGSM_eps00075", "FGSM_eps001"],
@@ -59,7 +59,7 @@ def _run(strategy, attacks, g):
 
 @pytest.mark.parametrize("strategy", list(RUNS))
 def test_strategy_reproduces_reference_run(golden, strategy):
-    g = golden("trainer")
+    g = golden_for_this_cpu(golden, "trainer")
     tr, trained, log = _run(strategy, RUNS[strategy], g)
     want_log = [str(m) for m in g[f"{strategy}_log"]]
     assert log == want_log, "\n".join(f"{a!r}\n{b!r}" for a, b in zip(log, want_log) if a != b)
