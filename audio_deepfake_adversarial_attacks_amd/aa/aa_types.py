@@ -32,4 +32,15 @@ class AttackEnum(Enum):
     PGDL2_40 = (torchattacks.PGDL2, {"eps": 0.1, "steps": 40})             # config 3 (alpha default 0.2)
     CW = (torchattacks.CW, {"c": 1.0, "kappa": 0, "steps": 100, "lr": 0.01})  # config 4 (cw.py:27 advises c ~ 1)
 
+    # --- additive members: APGD (step-size free), named like the PGD members above ---
+    APGD = (torchattacks.APGD, {"norm": "Linf", "eps": 0.0005, "steps": 10})
+    APGD_eps00075 = (torchattacks.APGD, {"norm": "Linf", "eps": 0.00075, "steps": 10})
+    APGD_eps001 = (torchattacks.APGD, {"norm": "Linf", "eps": 0.001, "steps": 10})
+
+    APGDL2 = (torchattacks.APGD, {"norm": "L2", "eps": 0.1, "steps": 10})
+    APGDL2_eps15 = (torchattacks.APGD, {"norm": "L2", "eps": 0.15, "steps": 10})
+    APGDL2_eps20 = (torchattacks.APGD, {"norm": "L2", "eps": 0.20, "steps": 10})
+
+    APGD100_eps003 = (torchattacks.APGD, {"norm": "Linf", "eps": 0.003, "steps": 100})  # the standard budget at PGD40_eps003's radius
+
     NO_ATTACK = (None, {})

@@ -482,3 +482,149 @@ def fab_backward_step(x1, x0, adv, res2, is_adv, beta: float, norm: str = "Linf"
         st = _lib.load().advstep_fab_backward_step_f32(x1.data_ptr(), x0.data_ptr(), adv.data_ptr(), res2.data_ptr(),
                                                        is_adv.data_ptr(), B, T, beta, _fab_kind(norm), _stream(x1.device))
     _lib.check(st, "advstep_fab_backward_step_f32")
+
+
+# ---------------------------------------------------------------------------------------------------------
+# APGD (include/advstep_apgd.h; reference adversarial_attacks/torchattacks/attacks/apgd.py:81-213)
+# ---------------------------------------------------------------------------------------------------------
+
+APGD_NORMS = {"Linf": 0, "L2": 1}
+_APGD_MODES = {"grad": 0, "start": 1, "step": 2}
+
+
+def _apgd_norm(norm: str) -> int:
+    try:
+        return APGD_NORMS[norm]
+    except KeyError:
+        raise ValueError(f"APGD norm must be 'Linf' or 'L2', got {norm!r}") from None
+
+
+def _per_row(t: torch.Tensor, name: str, B: int, dtype=torch.float32) -> torch.Tensor:
+    _require(t, name, dtype)
+    if t.numel() != B:
+        raise ValueError(f"{name} must hold one value per row ({B}), got {t.numel()}")
+    return t
+
+
+def apgd_init(x, eps: float, norm: str = "Linf", draw=None, seed: Optional[int] = None, offset: int = 0,
+              lo: float = 0.0, hi: float = 1.0, out=None):
+    """Random start of apgd.py:89-95.  `draw` = the caller's (B, T) draw (U[0, 1) for L-inf, N(0, 1) for L2) or a Philox
+    `seed`."""
+    _require(x, "x")
+    B, T = _rows(x, "x")
+    kind = _apgd_norm(norm)
+    out = _out_like(x, out)
+    with _Launch("apgd_init", x.device, tensors=(x, draw, out)):
+        ws, ws_bytes = _workspace(x.device, B, T)
+        if draw is not None:
+            _require(draw, "draw")
+            _same_shape(("x", x), ("draw", draw))
+            st = _lib.load().advstep_apgd_init_noise_f32(x.data_ptr(), draw.data_ptr(), out.data_ptr(), B, T, kind, eps, lo,
+                                                         hi, ws, ws_bytes, _stream(x.device))
+            what = "advstep_apgd_init_noise_f32"
+        else:
+            if seed is None:
+                raise ValueError("apgd_init needs either `draw` or a Philox `seed`")
+            st = _lib.load().advstep_apgd_init_philox_f32(x.data_ptr(), out.data_ptr(), B, T, kind, eps, lo, hi, seed, offset,
+                                                          ws, ws_bytes, _stream(x.device))
+            what = "advstep_apgd_init_philox_f32"
+    _lib.check(st, what)
+    return out
+
+
+def apgd_eval(z, labels, state=None, mode: str = "grad", i: int = 0):
+    """Per-row loss of cat([-z, z], 1), d(sum of losses)/dz and, for mode 'start' / 'step', the update of the per-row state
+    (`state`: acc, flags, loss_best, loss_best_last_check, reduced_last_check, loss_steps; see include/advstep_apgd.h).
+    Returns (dz shaped like z, loss (B))."""
+    _require(z, "z")
+    B = z.numel()
+    _per_row(labels, "labels", B, torch.int64)
+    m = _APGD_MODES[mode]
+    dz = torch.empty_like(z)
+    loss = torch.empty(B, dtype=torch.float32, device=z.device)
+    ptr = {}
+    if m:
+        for name, dt in (("acc", torch.uint8), ("flags", torch.uint8), ("loss_best", torch.float32),
+                         ("loss_best_last_check", torch.float32), ("reduced_last_check", torch.uint8)):
+            ptr[name] = _per_row(getattr(state, name), name, B, dt).data_ptr()
+        _require(state.loss_steps, "loss_steps")
+        if state.loss_steps.dim() != 2 or state.loss_steps.shape[1] != B or not 0 <= i < state.loss_steps.shape[0]:
+            raise ValueError(f"loss_steps {tuple(state.loss_steps.shape)} has no row {i} of {B} losses")
+        ptr["loss_steps"] = state.loss_steps.data_ptr()
+    with _Launch("apgd_eval", z.device):
+        st = _lib.load().advstep_apgd_eval_f32(z.data_ptr(), labels.data_ptr(), dz.data_ptr(), loss.data_ptr(), m, i,
+                                               ptr.get("acc"), ptr.get("flags"), ptr.get("loss_best"),
+                                               ptr.get("loss_best_last_check"), ptr.get("reduced_last_check"),
+                                               ptr.get("loss_steps"), B, _stream(z.device))
+    _lib.check(st, "advstep_apgd_eval_f32")
+    return dz, loss
+
+
+def apgd_checkpoint(state, i: int, k: int, rho: float) -> None:
+    """In place on `state`: the step-size checkpoint of apgd.py:194-211 after iteration i with window k."""
+    B = state.loss_best.numel()
+    _require(state.loss_steps, "loss_steps")
+    steps = state.loss_steps.shape[0]
+    for name, dt in (("loss_best", torch.float32), ("loss_best_last_check", torch.float32),
+                     ("reduced_last_check", torch.uint8), ("step_size", torch.float32), ("flags", torch.uint8)):
+        _per_row(getattr(state, name), name, B, dt)
+    if state.loss_steps.shape != (steps, B) or not (0 <= i < steps and k >= 1 and i - k >= -1):
+        raise ValueError(f"checkpoint at i={i}, k={k} does not fit loss_steps {tuple(state.loss_steps.shape)}")
+    with _Launch("apgd_checkpoint", state.loss_best.device):
+        st = _lib.load().advstep_apgd_checkpoint_f32(state.loss_steps.data_ptr(), steps, i, k, rho,
+                                                     state.loss_best.data_ptr(), state.loss_best_last_check.data_ptr(),
+                                                     state.reduced_last_check.data_ptr(), state.step_size.data_ptr(),
+                                                     state.flags.data_ptr(), B, _stream(state.loss_best.device))
+    _lib.check(st, "advstep_apgd_checkpoint_f32")
+
+
+def apgd_track(x_adv, grad, x_best, grad_best, x_best_adv, flags) -> None:
+    """In place, flagged rows only: fooled -> x_best_adv = x_adv; improved -> x_best = x_adv, grad_best = grad;
+    reset -> x_adv = x_best, grad = grad_best (apgd.py:178, 186-189, 207-208)."""
+    named = (("x_adv", x_adv), ("grad", grad), ("x_best", x_best), ("grad_best", grad_best), ("x_best_adv", x_best_adv))
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    B, T = _rows(x_adv, "x_adv")
+    _per_row(flags, "flags", B, torch.uint8)
+    with _Launch("apgd_track", x_adv.device):
+        st = _lib.load().advstep_apgd_track_f32(x_adv.data_ptr(), grad.data_ptr(), x_best.data_ptr(), grad_best.data_ptr(),
+                                                x_best_adv.data_ptr(), flags.data_ptr(), B, T, _stream(x_adv.device))
+    _lib.check(st, "advstep_apgd_track_f32")
+
+
+def _apgd_step_args(cur, prev, grad, x, step_size):
+    named = (("cur", cur), ("prev", prev), ("grad", grad), ("x", x))
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    B, T = _rows(cur, "cur")
+    _per_row(step_size, "step_size", B)
+    return B, T
+
+
+def apgd_linf_step(cur, prev, grad, x, step_size, eps: float, a: float, out=None):
+    """The L-inf momentum step of apgd.py:141-149; `out` may be `prev` (ping-pong)."""
+    B, T = _apgd_step_args(cur, prev, grad, x, step_size)
+    out = _out_like(cur, out)
+    with _Launch("apgd_linf_step", cur.device, tensors=(cur, prev, grad, x, out)):
+        st = _lib.load().advstep_apgd_linf_step_f32(cur.data_ptr(), prev.data_ptr(), grad.data_ptr(), x.data_ptr(),
+                                                    step_size.data_ptr(), out.data_ptr(), B, T, eps, a, _stream(cur.device))
+    _lib.check(st, "advstep_apgd_linf_step_f32")
+    return out
+
+
+def apgd_l2_step(cur, prev, grad, x, step_size, eps: float, a: float, out=None, return_norms: bool = False):
+    """The L2 momentum step of apgd.py:151-157; `out` may be `prev` (ping-pong).  return_norms: also (B, 3) =
+    ||g||, ||x1 - x||, ||x2 - x|| per row."""
+    B, T = _apgd_step_args(cur, prev, grad, x, step_size)
+    out = _out_like(cur, out)
+    norms = torch.empty((B, 3), dtype=torch.float32, device=cur.device)
+    # compulsory traffic: grad x4, cur x3, x x3, prev x2, out x1 (four row passes that recompute rather than store)
+    with _Launch("apgd_l2_step", cur.device, tensors=(grad,) * 4 + (cur,) * 3 + (x,) * 3 + (prev,) * 2 + (out,)):
+        ws, ws_bytes = _workspace(cur.device, B, T)
+        st = _lib.load().advstep_apgd_l2_step_f32(cur.data_ptr(), prev.data_ptr(), grad.data_ptr(), x.data_ptr(),
+                                                  step_size.data_ptr(), out.data_ptr(), norms.data_ptr(), B, T, eps, a, ws,
+                                                  ws_bytes, _stream(cur.device))
+    _lib.check(st, "advstep_apgd_l2_step_f32")
+    return (out, norms) if return_norms else out
