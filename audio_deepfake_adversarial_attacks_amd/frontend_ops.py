@@ -3,7 +3,8 @@
 backward, written frame-major so LCNN's first block reads it without a transpose copy.
 
 `lfcc_tail(spec, tables, dct, top_db)` takes torch.stft's complex output (B, F, NF) and returns (B, K, NF) — a view of
-a contiguous (B, NF, K) buffer.  Numerically it follows frontends.LFCC (this repository's restatement of torchaudio's
+a contiguous (B, NF, K) buffer; `lfcc_from_waveform` starts from the waveform; `fused_cepstrum` chooses between them for
+frontends.LFCC and frontends.MFCC.  Numerically it follows frontends.LFCC (this repository's restatement of torchaudio's
 LFCC) to float rounding, including torchaudio's gradient path through `amax` (floored gradients flow to the batch
 maximum); tests/test_gpu_frontend_ops.py.  HIP tensors only."""
 from __future__ import annotations
@@ -18,9 +19,16 @@ from .hip_ops import _Launch, _stream
 from .lcnn_ops import _IdKeyed
 
 
-def _direct_fft_enabled() -> bool:
-    """ADVSTEP_DIRECT_FFT=0 routes the frontend's FFTs through torch.fft (A/B measurements); default on."""
-    return os.environ.get("ADVSTEP_DIRECT_FFT", "1") != "0"
+def enabled(switch: str) -> bool:
+    """The frontend's A/B switches, each on unless set to "0" and read at call time (tests flip them; torchattacks/graphed.py
+    keys its captures on the environment):
+      ADVSTEP_FUSED_LFCC=0           LFCC / MFCC run the plain torch op chain;
+      ADVSTEP_FUSED_STFT=0           torch.stft (pad + strided frames + clone) in front of the fused LFCC tail;
+      ADVSTEP_INLDS_FFT=0            framing kernel + hipFFT + filterbank kernel instead of the in-LDS FFT kernels;
+      ADVSTEP_DIRECT_FFT=0           that path's FFTs through torch.fft instead of the direct hipFFT plans;
+      ADVSTEP_FUSED_MEL=0            the mel-spec frontend runs the plain torch op chain;
+      ADVSTEP_MEL_BWD_FROM_OUTPUT=0  the mel-spec backward recomputes the spectrum from the waveform."""
+    return os.environ.get(switch, "1") != "0"
 
 
 class FilterbankTables(NamedTuple):
@@ -108,206 +116,138 @@ def _rearm(ctx, stats: torch.Tensor) -> None:
     ctx.backward_calls += 1
 
 
-class _LfccTail(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, spec, tables: FilterbankTables, dct, top_db: float):
-        if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
-            raise _lib.AdvstepError("lfcc_tail needs a complex64 (B, F, NF) STFT on a HIP device (no CPU fallback)")
-        B, F, NF = spec.shape
-        sn = spec.transpose(1, 2)
-        if not sn.is_contiguous():       # torch.stft's native layout is already (B, NF, F)
-            sn = sn.contiguous()
-        sr = torch.view_as_real(sn)      # (B, NF, F, 2) float32
-        M, K = dct.shape
-        dev = spec.device
-        lib = _lib.load()
-        band_db = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
-        nblk = lib.advstep_lfcc_block_count(B, M, NF)
-        block_max = torch.empty(max(nblk, 1), dtype=torch.float32, device=dev)
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-        out = torch.empty((B, NF, K), dtype=torch.float32, device=dev)
-        frag = dct_fragments(dct)
-        with _Launch("lfcc_forward", dev):
-            st = lib.advstep_lfcc_bands_f32(sr.data_ptr(), tables.fb_start.data_ptr(), tables.fb_w.data_ptr(), tables.span,
-                                            band_db.data_ptr(), block_max.data_ptr(), B, F, M, NF, _stream(dev))
-            _lib.check(st, "advstep_lfcc_bands_f32")
-            st = lib.advstep_lfcc_max_project_f32(band_db.data_ptr(), dct.data_ptr(), _ptr(frag), block_max.data_ptr(), nblk,
-                                                  stats.data_ptr(), top_db, out.data_ptr(), B, M, NF, K, _stream(dev))
-            _lib.check(st, "advstep_lfcc_max_project_f32")
-        ctx.save_for_backward(sr, band_db, dct, tables.fbt_start, tables.fbt_w)
-        ctx.stats, ctx.frag = stats, frag
-        ctx.meta = (B, F, NF, M, K, tables.span_t, float(top_db))
-        ctx.backward_calls = 0
-        ctx.ties_in_backward = frag is not None and M == 128 and K == 80
-        return out.transpose(1, 2)
+class _Lfcc(torch.autograd.Function):
+    """The LFCC frontend from one of three spectrum sources, then the same two launches each way: [filterbank + dB] ->
+    [batch max + floor + DCT]; backward: [DCT^T + floor mask + dB' + tie count] -> [floor fix-up + filterbank^T].
+      "tail":   `x` is torch.stft's complex output (B, F, NF); the gradient returned is complex.
+      "frames": `x` is the waveform (B, T): framing kernel -> hipFFT r2c in front, hipFFT c2r -> overlap-add kernel behind
+                (torch.fft with ADVSTEP_DIRECT_FFT=0).  No padded copy, no strided-frame clone, no index_add.
+      "fused":  `x` is the waveform, the STFT inside the kernels: framing + FFT + power join the filterbank launch, and the
+                backward's second launch is [floor fix-up + filterbank^T + spectrum recomputed + inverse FFT + window +
+                overlap-add], with dx zero-filled by the first."""
 
     @staticmethod
-    def backward(ctx, gout):
-        sr, band_db, dct, fbt_start, fbt_w = ctx.saved_tensors
-        stats, frag = ctx.stats, ctx.frag
-        B, F, NF, M, K, span_t, top_db = ctx.meta
-        dev = gout.device
-        go = gout.transpose(1, 2).contiguous()     # (B, NF, K); a no-op when the consumer is frame-major
-        lib = _lib.load()
-        dband = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
-        dspec = torch.empty((B, NF, F, 2), dtype=torch.float32, device=dev)
-        _rearm(ctx, stats)
-        with _Launch("lfcc_backward", dev):
-            st = lib.advstep_lfcc_project_backward_zero_f32(go.data_ptr(), dct.data_ptr(), _ptr(frag),
-                                                            band_db.data_ptr(), stats.data_ptr(), top_db, dband.data_ptr(), B, M, NF,
-                                                            K, 0, 0, _stream(dev))
-            _lib.check(st, "advstep_lfcc_project_backward_zero_f32")
-            st = lib.advstep_lfcc_floor_fixup_f32(band_db.data_ptr(), stats.data_ptr(), dband.data_ptr(), band_db.numel(),
-                                                  _stream(dev))
-            _lib.check(st, "advstep_lfcc_floor_fixup_f32")
-            st = lib.advstep_lfcc_bands_backward_f32(dband.data_ptr(), sr.data_ptr(), fbt_start.data_ptr(),
-                                                     fbt_w.data_ptr(), span_t, dspec.data_ptr(), B, F, M, NF, 0,
-                                                     _stream(dev))
-            _lib.check(st, "advstep_lfcc_bands_backward_f32")
-        return torch.view_as_complex(dspec).transpose(1, 2), None, None, None
-
-
-class _LfccFromWaveform(torch.autograd.Function):
-    """The whole LFCC frontend: framing kernel -> rocFFT r2c -> tail kernels; backward: tail kernels -> rocFFT c2r ->
-    overlap-add kernel.  No padded copy, no strided-frame clone, no index_add."""
-
-    @staticmethod
-    def forward(ctx, x, window, hop, tables: FilterbankTables, dct, top_db: float):
-        B, T = x.shape
-        nfft = window.numel()
-        NF = 1 + T // hop
-        F = nfft // 2 + 1
+    def forward(ctx, source: str, x, window, hop, tables: FilterbankTables, dct, top_db: float):
+        fused = source == "fused"
         M, K = dct.shape
         dev = x.device
         lib = _lib.load()
-        frames = torch.empty((B, NF, nfft), dtype=torch.float32, device=dev)
-        with _Launch("stft_frames", dev):
-            st = lib.advstep_stft_frames_f32(x.data_ptr(), window.data_ptr(), frames.data_ptr(), B, T, NF, hop, nfft,
-                                             _stream(dev))
-        _lib.check(st, "advstep_stft_frames_f32")
-        sr = torch.empty((B, NF, F, 2), dtype=torch.float32, device=dev)      # interleaved complex spectrum
-        if not (_direct_fft_enabled() and fft_plans.rfft_into(frames.view(B * NF, nfft), sr.view(B * NF, F, 2))):
-            sr = torch.view_as_real(torch.fft.rfft(frames, dim=-1))           # same library, plus a defensive input clone
-        del frames
+        if source == "tail":
+            B, F, NF = x.shape
+            T = nfft = None
+            sn = x.transpose(1, 2)
+            if not sn.is_contiguous():       # torch.stft's native layout is already (B, NF, F)
+                sn = sn.contiguous()
+            spec = torch.view_as_real(sn)    # (B, NF, F, 2) float32
+        else:
+            B, T = x.shape
+            nfft = window.numel()
+            NF, F = 1 + T // hop, nfft // 2 + 1
+            spec = x if fused else _frames_rfft(x, window, hop, NF)
         band_db = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
-        nblk = lib.advstep_lfcc_block_count(B, M, NF)
+        nblk = lib.advstep_stft_bands_block_count(B, NF) if fused else lib.advstep_lfcc_block_count(B, M, NF)
         block_max = torch.empty(max(nblk, 1), dtype=torch.float32, device=dev)
         stats = torch.empty(4, dtype=torch.float32, device=dev)
         out = torch.empty((B, NF, K), dtype=torch.float32, device=dev)
         frag = dct_fragments(dct)
-        with _Launch("lfcc_forward", dev):
-            st = lib.advstep_lfcc_bands_f32(sr.data_ptr(), tables.fb_start.data_ptr(), tables.fb_w.data_ptr(), tables.span,
-                                            band_db.data_ptr(), block_max.data_ptr(), B, F, M, NF, _stream(dev))
-            _lib.check(st, "advstep_lfcc_bands_f32")
-            st = lib.advstep_lfcc_max_project_f32(band_db.data_ptr(), dct.data_ptr(), _ptr(frag), block_max.data_ptr(), nblk,
-                                                  stats.data_ptr(), top_db, out.data_ptr(), B, M, NF, K, _stream(dev))
-            _lib.check(st, "advstep_lfcc_max_project_f32")
-        ctx.save_for_backward(sr, band_db, dct, tables.fbt_start, tables.fbt_w, window)
-        ctx.stats, ctx.frag = stats, frag
-        ctx.meta = (B, T, F, NF, M, K, tables.span_t, float(top_db), hop, nfft)
-        ctx.backward_calls = 0
-        ctx.ties_in_backward = frag is not None and M == 128 and K == 80
-        return out.transpose(1, 2)
-
-    @staticmethod
-    def backward(ctx, gout):
-        sr, band_db, dct, fbt_start, fbt_w, window = ctx.saved_tensors
-        stats, frag = ctx.stats, ctx.frag
-        B, T, F, NF, M, K, span_t, top_db, hop, nfft = ctx.meta
-        dev = gout.device
-        go = gout.transpose(1, 2).contiguous()
-        lib = _lib.load()
-        dband = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
-        dspec = torch.empty((B, NF, F, 2), dtype=torch.float32, device=dev)
-        _rearm(ctx, stats)
-        with _Launch("lfcc_backward", dev):
-            st = lib.advstep_lfcc_project_backward_zero_f32(go.data_ptr(), dct.data_ptr(), _ptr(frag),
-                                                            band_db.data_ptr(), stats.data_ptr(), top_db, dband.data_ptr(), B, M, NF,
-                                                            K, 0, 0, _stream(dev))
-            _lib.check(st, "advstep_lfcc_project_backward_zero_f32")
-            st = lib.advstep_lfcc_floor_fixup_f32(band_db.data_ptr(), stats.data_ptr(), dband.data_ptr(), band_db.numel(),
-                                                  _stream(dev))
-            _lib.check(st, "advstep_lfcc_floor_fixup_f32")
-            st = lib.advstep_lfcc_bands_backward_f32(dband.data_ptr(), sr.data_ptr(), fbt_start.data_ptr(),
-                                                     fbt_w.data_ptr(), span_t, dspec.data_ptr(), B, F, M, NF, 1,
-                                                     _stream(dev))
-            _lib.check(st, "advstep_lfcc_bands_backward_f32")
-        # gradient of the one-sided real FFT = unnormalised c2r inverse of the pre-scaled half spectrum
-        dframes = torch.empty((B, NF, nfft), dtype=torch.float32, device=dev)
-        if not (_direct_fft_enabled() and fft_plans.irfft_into(dspec.view(B * NF, F, 2), dframes.view(B * NF, nfft))):
-            dframes = torch.fft.irfft(torch.view_as_complex(dspec), n=nfft, dim=-1, norm="forward").contiguous()
-        dx = torch.empty((B, T), dtype=torch.float32, device=dev)
-        with _Launch("stft_overlap_add", dev):
-            st = lib.advstep_stft_overlap_add_f32(dframes.data_ptr(), window.data_ptr(), dx.data_ptr(), B, T, NF, hop, nfft,
-                                                  _stream(dev))
-        _lib.check(st, "advstep_stft_overlap_add_f32")
-        return dx, None, None, None, None, None
-
-
-def _inlds_fft_enabled() -> bool:
-    """ADVSTEP_INLDS_FFT=0 keeps framing kernel + hipFFT + filterbank kernel (A/B measurements); default: the fused
-    in-LDS FFT kernels of csrc/lfcc_stft.hip."""
-    return os.environ.get("ADVSTEP_INLDS_FFT", "1") != "0"
-
-
-class _LfccFromWaveformFused(torch.autograd.Function):
-    """The whole LFCC frontend with the STFT inside the kernels, two launches each way: [framing + FFT + power + filterbank + dB]
-    -> [batch max + floor + DCT]; backward: [DCT^T + floor + zero fill of dx] -> [floor fix-up + filterbank^T + spectrum
-    recomputed + inverse FFT + window + overlap-add]."""
-
-    @staticmethod
-    def forward(ctx, x, window, hop, tables: FilterbankTables, dct, top_db: float):
-        B, T = x.shape
-        nfft = window.numel()
-        NF = 1 + T // hop
-        M, K = dct.shape
-        dev = x.device
-        lib = _lib.load()
-        band_db = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
-        nblk = lib.advstep_stft_bands_block_count(B, NF)
-        block_max = torch.empty(max(nblk, 1), dtype=torch.float32, device=dev)
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-        out = torch.empty((B, NF, K), dtype=torch.float32, device=dev)
-        frag = dct_fragments(dct)
-        with _Launch("lfcc_forward", dev, tensors=(x, band_db, band_db, out)):     # waveform in, band rows out + back in, cepstra out
-            st = lib.advstep_stft_bands_f32(x.data_ptr(), window.data_ptr(), tables.fb_start.data_ptr(), tables.fb_w.data_ptr(),
-                                            tables.span, band_db.data_ptr(), block_max.data_ptr(), B, T, NF, hop, nfft, M,
-                                            _stream(dev))
-            _lib.check(st, "advstep_stft_bands_f32")
+        # bytes on the fused path: waveform in, band rows out + back in, cepstra out
+        with _Launch("lfcc_forward", dev, tensors=(x, band_db, band_db, out) if fused else ()):
+            if fused:
+                st = lib.advstep_stft_bands_f32(x.data_ptr(), window.data_ptr(), tables.fb_start.data_ptr(),
+                                                tables.fb_w.data_ptr(), tables.span, band_db.data_ptr(), block_max.data_ptr(),
+                                                B, T, NF, hop, nfft, M, _stream(dev))
+                _lib.check(st, "advstep_stft_bands_f32")
+            else:
+                st = lib.advstep_lfcc_bands_f32(spec.data_ptr(), tables.fb_start.data_ptr(), tables.fb_w.data_ptr(),
+                                                tables.span, band_db.data_ptr(), block_max.data_ptr(), B, F, M, NF, _stream(dev))
+                _lib.check(st, "advstep_lfcc_bands_f32")
             # batch maximum + floor + DCT: one launch (every workgroup reduces the block maxima itself)
             st = lib.advstep_lfcc_max_project_f32(band_db.data_ptr(), dct.data_ptr(), _ptr(frag), block_max.data_ptr(), nblk,
                                                   stats.data_ptr(), top_db, out.data_ptr(), B, M, NF, K, _stream(dev))
             _lib.check(st, "advstep_lfcc_max_project_f32")
-        ctx.save_for_backward(x, band_db, dct, tables.fbt_start, tables.fbt_w, window)
-        ctx.stats, ctx.frag = stats, frag
-        ctx.meta = (B, T, NF, M, K, tables.span_t, float(top_db), hop, nfft)
+        ctx.save_for_backward(spec, band_db, dct, tables.fbt_start, tables.fbt_w, window)
+        ctx.stats, ctx.frag = stats, frag      # not saved tensors: see _rearm
+        ctx.meta = (source, B, T, F, NF, M, K, tables.span_t, float(top_db), hop, nfft)
         ctx.backward_calls = 0
         ctx.ties_in_backward = frag is not None and M == 128 and K == 80
         return out.transpose(1, 2)
 
     @staticmethod
     def backward(ctx, gout):
-        x, band_db, dct, fbt_start, fbt_w, window = ctx.saved_tensors
+        spec, band_db, dct, fbt_start, fbt_w, window = ctx.saved_tensors
         stats, frag = ctx.stats, ctx.frag
-        B, T, NF, M, K, span_t, top_db, hop, nfft = ctx.meta
+        source, B, T, F, NF, M, K, span_t, top_db, hop, nfft = ctx.meta
+        fused = source == "fused"
         dev = gout.device
-        go = gout.transpose(1, 2).contiguous()
+        go = gout.transpose(1, 2).contiguous()     # (B, NF, K); a no-op when the consumer is frame-major
         lib = _lib.load()
         dband = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
-        dx = torch.empty((B, T), dtype=torch.float32, device=dev)
+        if fused:
+            dx = torch.empty((B, T), dtype=torch.float32, device=dev)
+        else:
+            dspec = torch.empty((B, NF, F, 2), dtype=torch.float32, device=dev)
         _rearm(ctx, stats)
-        with _Launch("lfcc_backward", dev, tensors=(go, band_db, dband, dband, x, dx, dx)):
-            # two launches: [DCT^T + floor mask + dB' + tie count; zero-fills dx] -> [floor fix-up folded into the band-gradient
-            # load + filterbank^T + FFT pair + overlap-add]
-            st = lib.advstep_lfcc_project_backward_zero_f32(go.data_ptr(), dct.data_ptr(), _ptr(frag),
-                                                            band_db.data_ptr(), stats.data_ptr(), top_db, dband.data_ptr(), B, M, NF,
-                                                            K, dx.data_ptr(), dx.numel(), _stream(dev))
+        with _Launch("lfcc_backward", dev, tensors=(go, band_db, dband, dband, spec, dx, dx) if fused else ()):
+            # on the fused path this also zero-fills dx, which the overlap-add of the second launch accumulates into
+            st = lib.advstep_lfcc_project_backward_zero_f32(go.data_ptr(), dct.data_ptr(), _ptr(frag), band_db.data_ptr(),
+                                                            stats.data_ptr(), top_db, dband.data_ptr(), B, M, NF, K,
+                                                            dx.data_ptr() if fused else 0, dx.numel() if fused else 0,
+                                                            _stream(dev))
             _lib.check(st, "advstep_lfcc_project_backward_zero_f32")
-            st = lib.advstep_stft_bands_backward_fixup_f32(x.data_ptr(), window.data_ptr(), dband.data_ptr(), band_db.data_ptr(),
-                                                           stats.data_ptr(), fbt_start.data_ptr(), fbt_w.data_ptr(), span_t,
-                                                           dx.data_ptr(), 1, B, T, NF, hop, nfft, M, _stream(dev))
-            _lib.check(st, "advstep_stft_bands_backward_fixup_f32")
-        return dx, None, None, None, None, None
+            if fused:
+                st = lib.advstep_stft_bands_backward_fixup_f32(spec.data_ptr(), window.data_ptr(), dband.data_ptr(),
+                                                               band_db.data_ptr(), stats.data_ptr(), fbt_start.data_ptr(),
+                                                               fbt_w.data_ptr(), span_t, dx.data_ptr(), 1, B, T, NF, hop, nfft,
+                                                               M, _stream(dev))
+                _lib.check(st, "advstep_stft_bands_backward_fixup_f32")
+            else:
+                st = lib.advstep_lfcc_floor_fixup_f32(band_db.data_ptr(), stats.data_ptr(), dband.data_ptr(),
+                                                      band_db.numel(), _stream(dev))
+                _lib.check(st, "advstep_lfcc_floor_fixup_f32")
+                # hermitian_half on the frames path: its c2r inverse takes the pre-scaled half spectrum
+                st = lib.advstep_lfcc_bands_backward_f32(dband.data_ptr(), spec.data_ptr(), fbt_start.data_ptr(),
+                                                         fbt_w.data_ptr(), span_t, dspec.data_ptr(), B, F, M, NF,
+                                                         int(source == "frames"), _stream(dev))
+                _lib.check(st, "advstep_lfcc_bands_backward_f32")
+        if source == "tail":
+            return None, torch.view_as_complex(dspec).transpose(1, 2), None, None, None, None, None
+        if source == "frames":
+            dx = _irfft_overlap_add(dspec, window, hop, T)
+        return None, dx, None, None, None, None, None
+
+
+def _frames_rfft(x: torch.Tensor, window: torch.Tensor, hop: int, NF: int) -> torch.Tensor:
+    """Framing kernel -> one-sided r2c FFT: (B, T) -> the interleaved complex spectrum (B, NF, F, 2)."""
+    B, T = x.shape
+    nfft = window.numel()
+    F = nfft // 2 + 1
+    dev = x.device
+    frames = torch.empty((B, NF, nfft), dtype=torch.float32, device=dev)
+    with _Launch("stft_frames", dev):
+        st = _lib.load().advstep_stft_frames_f32(x.data_ptr(), window.data_ptr(), frames.data_ptr(), B, T, NF, hop, nfft,
+                                                 _stream(dev))
+    _lib.check(st, "advstep_stft_frames_f32")
+    sr = torch.empty((B, NF, F, 2), dtype=torch.float32, device=dev)
+    if not (enabled("ADVSTEP_DIRECT_FFT") and fft_plans.rfft_into(frames.view(B * NF, nfft), sr.view(B * NF, F, 2))):
+        sr = torch.view_as_real(torch.fft.rfft(frames, dim=-1))           # same library, plus a defensive input clone
+    return sr
+
+
+def _irfft_overlap_add(dspec: torch.Tensor, window: torch.Tensor, hop: int, T: int) -> torch.Tensor:
+    """The adjoint of _frames_rfft: spectrum gradient (B, NF, F, 2) -> waveform gradient (B, T)."""
+    B, NF, F, _ = dspec.shape
+    nfft = window.numel()
+    dev = dspec.device
+    # gradient of the one-sided real FFT = unnormalised c2r inverse of the pre-scaled half spectrum
+    dframes = torch.empty((B, NF, nfft), dtype=torch.float32, device=dev)
+    if not (enabled("ADVSTEP_DIRECT_FFT") and fft_plans.irfft_into(dspec.view(B * NF, F, 2), dframes.view(B * NF, nfft))):
+        dframes = torch.fft.irfft(torch.view_as_complex(dspec), n=nfft, dim=-1, norm="forward").contiguous()
+    dx = torch.empty((B, T), dtype=torch.float32, device=dev)
+    with _Launch("stft_overlap_add", dev):
+        st = _lib.load().advstep_stft_overlap_add_f32(dframes.data_ptr(), window.data_ptr(), dx.data_ptr(), B, T, NF, hop,
+                                                      nfft, _stream(dev))
+    _lib.check(st, "advstep_stft_overlap_add_f32")
+    return dx
 
 
 def lfcc_from_waveform(x: torch.Tensor, window_nfft: torch.Tensor, hop: int, tables: FilterbankTables, dct: torch.Tensor,
@@ -315,9 +255,34 @@ def lfcc_from_waveform(x: torch.Tensor, window_nfft: torch.Tensor, hop: int, tab
     """Waveform (B, T) -> LFCC (B, K, 1 + T // hop); `window_nfft` is the analysis window zero-padded (centred) to n_fft."""
     if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
         raise _lib.AdvstepError("lfcc_from_waveform needs a float32 (B, T) waveform on a HIP device (no CPU fallback)")
-    if _inlds_fft_enabled() and _lib.load().advstep_stft_bands_supported(window_nfft.numel(), hop, x.shape[1]):
-        return _LfccFromWaveformFused.apply(x.contiguous(), window_nfft, hop, tables, dct, top_db)
-    return _LfccFromWaveform.apply(x.contiguous(), window_nfft, hop, tables, dct, top_db)
+    inlds = enabled("ADVSTEP_INLDS_FFT") and _lib.load().advstep_stft_bands_supported(window_nfft.numel(), hop, x.shape[1])
+    return _Lfcc.apply("fused" if inlds else "frames", x.contiguous(), window_nfft, hop, tables, dct, top_db)
+
+
+def lfcc_tail(spec: torch.Tensor, tables: FilterbankTables, dct: torch.Tensor, top_db: float = 80.0) -> torch.Tensor:
+    """Complex STFT (B, F, NF) -> LFCC (B, K, NF) (view of a frame-major buffer)."""
+    if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
+        raise _lib.AdvstepError("lfcc_tail needs a complex64 (B, F, NF) STFT on a HIP device (no CPU fallback)")
+    return _Lfcc.apply("tail", spec, None, None, tables, dct, top_db)
+
+
+def fused_cepstrum(x: torch.Tensor, window_nfft, hop: int, tables, dct: torch.Tensor, top_db: float) -> Optional[torch.Tensor]:
+    """Waveform (B, T) -> filterbank -> dB -> DCT of its power STFT through the fused kernels (LFCC, or MFCC with a mel bank),
+    or None where none applies and the caller runs the torch op chain.  `window_nfft` and `tables` are the caller's cached
+    derivations of its buffers, passed as zero-argument callables so that they are built only once a kernel applies."""
+    M, K = dct.shape
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and enabled("ADVSTEP_FUSED_LFCC")
+            and M <= 128 and K in (20, 40, 80)):
+        return None
+    tables, window = tables(), window_nfft()
+    nfft = window.numel()
+    if x.shape[1] > nfft // 2 and nfft % 4 == 0 and enabled("ADVSTEP_FUSED_STFT"):
+        # framing, FFT, filterbank, dB in one kernel; floor + DCT in another (and two more on the way back)
+        return lfcc_from_waveform(x, window, hop, tables, dct, top_db)
+    # (torch.stft pads a window shorter than n_fft the same way)
+    spec = torch.stft(x, n_fft=nfft, hop_length=hop, window=window, center=True, pad_mode="reflect", normalized=False,
+                      onesided=True, return_complex=True)
+    return lfcc_tail(spec, tables, dct, top_db)
 
 
 class _MelSpecFromWaveform(torch.autograd.Function):
@@ -336,7 +301,7 @@ class _MelSpecFromWaveform(torch.autograd.Function):
                                                   tables.fb_w.data_ptr(), tables.span, out.data_ptr(), B, T, NF, hop, nfft, M,
                                                   _stream(dev))
         _lib.check(st, "advstep_stft_mel_f32")
-        ctx.from_output = os.environ.get("ADVSTEP_MEL_BWD_FROM_OUTPUT", "1") != "0"
+        ctx.from_output = enabled("ADVSTEP_MEL_BWD_FROM_OUTPUT")
         ctx.save_for_backward(out if ctx.from_output else x, window, tables.fb_start, tables.fb_w, tables.fbt_start, tables.fbt_w)
         ctx.meta = (B, T, NF, M, tables.span, tables.span_t, hop, nfft)
         return out
@@ -374,7 +339,3 @@ def mel_spec_from_waveform(x: torch.Tensor, window_nfft: torch.Tensor, hop: int,
         raise _lib.AdvstepError("mel_spec_from_waveform needs a float32 (B, T) waveform on a HIP device (no CPU fallback)")
     return _MelSpecFromWaveform.apply(x.contiguous(), window_nfft, hop, tables)
 
-
-def lfcc_tail(spec: torch.Tensor, tables: FilterbankTables, dct: torch.Tensor, top_db: float = 80.0) -> torch.Tensor:
-    """Complex STFT (B, F, NF) -> LFCC (B, K, NF) (view of a frame-major buffer)."""
-    return _LfccTail.apply(spec, tables, dct, top_db)

@@ -26,23 +26,7 @@ from typing import Callable, List, Union
 import torch
 from torch import nn
 
-def _fused_stft_enabled() -> bool:
-    """ADVSTEP_FUSED_STFT=0 keeps torch.stft (pad + strided frames + clone) in front of the fused LFCC tail."""
-    import os
-    return os.environ.get("ADVSTEP_FUSED_STFT", "1") != "0"
-
-
-def _fused_mel_enabled() -> bool:
-    """ADVSTEP_FUSED_MEL=0 keeps the plain torch op chain of the mel-spec frontend on the GPU; default on."""
-    import os
-    return os.environ.get("ADVSTEP_FUSED_MEL", "1") != "0"
-
-
-def _fused_lfcc_enabled() -> bool:
-    """ADVSTEP_FUSED_LFCC=0 keeps the plain torch op chain on the GPU (A/B measurements); default on."""
-    import os
-    return os.environ.get("ADVSTEP_FUSED_LFCC", "1") != "0"
-
+from . import frontend_ops
 
 # values from FakeAVCeleb paper (frontends.py:6-9)
 SAMPLING_RATE = 16_000
@@ -127,42 +111,34 @@ class Spectrogram(nn.Module):
         return spec.abs().pow(2.0)
 
 
+def _cached(owner, name: str, src: torch.Tensor, derive: Callable, device=None):
+    """derive(), cached on `owner` as attribute `name` until `src` moves or changes, or is wanted on another `device` (default:
+    src's)."""
+    key = (src.data_ptr(), src._version, str(src.device if device is None else device))
+    hit = getattr(owner, name, None)
+    if hit is None or hit[0] != key:
+        hit = (key, derive())
+        setattr(owner, name, hit)
+    return hit[1]
+
+
 def _cached_tables(owner, fb: torch.Tensor):
     """Sparse filterbank tables for the fused kernels, cached on `owner` until `fb` moves or changes."""
-    key = (fb.data_ptr(), fb._version, str(fb.device))
-    if getattr(owner, "_tables_key", None) != key:
-        from . import frontend_ops
-        owner._tables_key, owner._tables_val = key, frontend_ops.filterbank_tables(fb)
-    return owner._tables_val
+    return _cached(owner, "_tables_cache", fb, lambda: frontend_ops.filterbank_tables(fb))
+
+
+def _centred(w: torch.Tensor, n_fft: int) -> torch.Tensor:
+    """`w` zero-padded (centred) to n_fft, as torch.stft applies a window shorter than n_fft."""
+    out = torch.zeros(n_fft, dtype=w.dtype, device=w.device)
+    left = (n_fft - w.numel()) // 2
+    out[left:left + w.numel()] = w
+    return out
 
 
 def _cached_window_nfft(owner, spectrogram) -> torch.Tensor:
-    """The analysis window zero-padded (centred) to n_fft, as torch.stft applies it; cached on `owner`."""
+    """The analysis window zero-padded (centred) to n_fft; cached on `owner`."""
     w = spectrogram.window
-    key = (w.data_ptr(), w._version, str(w.device))
-    if getattr(owner, "_wpad_key", None) != key:
-        n_fft = spectrogram.n_fft
-        left = (n_fft - w.numel()) // 2
-        padded = torch.zeros(n_fft, dtype=w.dtype, device=w.device)
-        padded[left:left + w.numel()] = w.detach()
-        owner._wpad_key, owner._wpad_val = key, padded
-    return owner._wpad_val
-
-
-def _fused_cepstrum(owner, waveform, spectrogram, fb, dct_mat, top_db):
-    """filterbank -> dB -> DCT of the power STFT through the fused kernels, or None when they do not apply."""
-    if not (waveform.is_cuda and waveform.dim() == 2 and waveform.dtype == torch.float32 and _fused_lfcc_enabled()
-            and dct_mat.shape[0] <= 128 and dct_mat.shape[1] in (20, 40, 80)):
-        return None
-    from . import frontend_ops
-    sg = spectrogram
-    tables = _cached_tables(owner, fb)
-    if waveform.shape[1] > sg.n_fft // 2 and sg.n_fft % 4 == 0 and _fused_stft_enabled():
-        # framing, FFT, filterbank, dB in one kernel; floor + DCT in another (and two more on the way back)
-        return frontend_ops.lfcc_from_waveform(waveform, _cached_window_nfft(owner, sg), sg.hop_length, tables, dct_mat, top_db)
-    spec = torch.stft(waveform, n_fft=sg.n_fft, hop_length=sg.hop_length, win_length=sg.win_length, window=sg.window,
-                      center=True, pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
-    return frontend_ops.lfcc_tail(spec, tables, dct_mat, top_db)
+    return _cached(owner, "_window_cache", w, lambda: _centred(w.detach(), spectrogram.n_fft))
 
 
 class LFCC(nn.Module):
@@ -184,7 +160,8 @@ class LFCC(nn.Module):
         return _cached_window_nfft(self, self.Spectrogram)
 
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
-        fused = _fused_cepstrum(self, waveform, self.Spectrogram, self.filter_mat, self.dct_mat, self.top_db)
+        fused = frontend_ops.fused_cepstrum(waveform, self._window_nfft, self.Spectrogram.hop_length, self._tables, self.dct_mat,
+                                            self.top_db)
         if fused is not None:     # SURVEY.md section 8-f2; written frame-major for LCNN's first block
             return fused
         spec = self.Spectrogram(waveform)                                               # (B, 257, frames)
@@ -228,10 +205,16 @@ class MFCC(nn.Module):
         self.MelSpectrogram = MelSpectrogram(sample_rate, n_fft, win_length, hop_length)
         self.register_buffer("dct_mat", create_dct(n_mfcc, 128, "ortho"))
 
+    def _tables(self):
+        return _cached_tables(self, self.MelSpectrogram.mel_scale.fb)
+
+    def _window_nfft(self):
+        return _cached_window_nfft(self, self.MelSpectrogram.spectrogram)
+
     def forward(self, waveform):
         # same structure as LFCC (power STFT -> filterbank -> dB -> DCT) with a mel filterbank: same fused kernels
-        fused = _fused_cepstrum(self, waveform, self.MelSpectrogram.spectrogram, self.MelSpectrogram.mel_scale.fb,
-                                self.dct_mat, self.top_db)
+        fused = frontend_ops.fused_cepstrum(waveform, self._window_nfft, self.MelSpectrogram.spectrogram.hop_length,
+                                            self._tables, self.dct_mat, self.top_db)
         if fused is not None:
             return fused
         mel = amplitude_to_db_power(self.MelSpectrogram(waveform), self.top_db)
@@ -251,18 +234,13 @@ class MelSpecFrontend(nn.Module):
 
     def _fused_state(self, device):
         """Sparse mel tables + the rectangular window zero-padded (centred) to n_fft, cached per device."""
-        key = (self.mel_scale.fb.data_ptr(), self.mel_scale.fb._version, str(device))
-        if getattr(self, "_fused_key", None) != key:
-            from . import frontend_ops
-            left = (N_FFT - self.win_length) // 2
-            window = torch.zeros(N_FFT, dtype=torch.float32, device=device)
-            window[left:left + self.win_length] = 1.0
-            self._fused_key, self._fused_val = key, (frontend_ops.filterbank_tables(self.mel_scale.fb), window)
-        return self._fused_val
+        def derive():
+            window = _centred(torch.ones(self.win_length, dtype=torch.float32, device=device), N_FFT)
+            return frontend_ops.filterbank_tables(self.mel_scale.fb), window
+        return _cached(self, "_fused_cache", self.mel_scale.fb, derive, device)
 
     def forward(self, audio: torch.Tensor) -> torch.Tensor:
-        if audio.is_cuda and audio.dim() == 2 and audio.dtype == torch.float32 and _fused_mel_enabled():
-            from . import frontend_ops
+        if audio.is_cuda and audio.dim() == 2 and audio.dtype == torch.float32 and frontend_ops.enabled("ADVSTEP_FUSED_MEL"):
             tables, window = self._fused_state(audio.device)
             if frontend_ops.mel_spec_supported(N_FFT, self.hop_length, audio.shape[1], self.mel_scale.fb.shape[1], tables.span,
                                                tables.span_t):
