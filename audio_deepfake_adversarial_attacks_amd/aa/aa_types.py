@@ -43,4 +43,19 @@ class AttackEnum(Enum):
 
     APGD100_eps003 = (torchattacks.APGD, {"norm": "Linf", "eps": 0.003, "steps": 100})  # the standard budget at PGD40_eps003's radius
 
+    # --- additive members: the momentum attacks made for transfer, named like the PGD members above; alpha = eps / steps, the
+    # setting of the MI-FGSM paper (the classes' 2/255 default is 15x these radii and would fill the ball at the first step) ---
+    MIFGSM = (torchattacks.MIFGSM, {"eps": 0.0005, "alpha": 0.0005 / 10, "steps": 10, "decay": 1.0})
+    MIFGSM_eps00075 = (torchattacks.MIFGSM, {"eps": 0.00075, "alpha": 0.00075 / 10, "steps": 10, "decay": 1.0})
+    MIFGSM_eps001 = (torchattacks.MIFGSM, {"eps": 0.001, "alpha": 0.001 / 10, "steps": 10, "decay": 1.0})
+
+    NIFGSM = (torchattacks.NIFGSM, {"eps": 0.0005, "alpha": 0.0005 / 10, "steps": 10, "decay": 1.0})
+    NIFGSM_eps00075 = (torchattacks.NIFGSM, {"eps": 0.00075, "alpha": 0.00075 / 10, "steps": 10, "decay": 1.0})
+    NIFGSM_eps001 = (torchattacks.NIFGSM, {"eps": 0.001, "alpha": 0.001 / 10, "steps": 10, "decay": 1.0})
+
+    VMIFGSM = (torchattacks.VMIFGSM, {"eps": 0.0005, "alpha": 0.0005 / 10, "steps": 10, "decay": 1.0, "N": 20, "beta": 1.5})
+    VNIFGSM = (torchattacks.VNIFGSM, {"eps": 0.0005, "alpha": 0.0005 / 10, "steps": 10, "decay": 1.0, "N": 20, "beta": 1.5})
+
+    MIFGSM40_eps003 = (torchattacks.MIFGSM, {"eps": 0.003, "alpha": 0.003 / 40, "steps": 40, "decay": 1.0})  # PGD40_eps003's radius
+
     NO_ATTACK = (None, {})

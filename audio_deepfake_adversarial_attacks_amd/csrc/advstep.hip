@@ -58,15 +58,6 @@ __device__ __forceinline__ float pgd_linf_elem(float a, float g, float x, float 
 // Philox4x32-10 streams (the generator itself is in advstep_common.h): the same stream on the CPU oracle and on the device.
 // ---------------------------------------------------------------------------------------------------------
 
-// 4 uniforms in [-eps, eps): u * (eps - (-eps)) + (-eps)
-__device__ __forceinline__ float4 philox_uniform4(uint64_t q, uint64_t seed, uint64_t offset, float eps) {
-    const Quad r = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32),
-                                 (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float from = -eps, range = eps - from;
-    return make_float4(u01(r.v[0]) * range + from, u01(r.v[1]) * range + from, u01(r.v[2]) * range + from,
-                       u01(r.v[3]) * range + from);
-}
-
 __device__ __forceinline__ float f4_get(const float4 &v, int k) {
     return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
 }

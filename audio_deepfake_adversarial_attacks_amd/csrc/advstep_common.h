@@ -140,6 +140,15 @@ __device__ __forceinline__ float u01_open0(uint32_t bits) {  // (0, 1]
     return (float)((bits >> 8) + 1u) * 5.9604644775390625e-08f;
 }
 
+// 4 uniforms in [-eps, eps) for quad q of the flat buffer, as Tensor.uniform_(-eps, eps) forms them: u * (eps - (-eps)) + (-eps)
+__device__ __forceinline__ float4 philox_uniform4(uint64_t q, uint64_t seed, uint64_t offset, float eps) {
+    const Quad r = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32),
+                                 (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float from = -eps, range = eps - from;
+    return make_float4(u01(r.v[0]) * range + from, u01(r.v[1]) * range + from, u01(r.v[2]) * range + from,
+                       u01(r.v[3]) * range + from);
+}
+
 // 4 standard normals for quad q of row b (Box-Muller on two uniform pairs).
 __device__ __forceinline__ float4 philox_normal4(uint32_t q, uint32_t b, uint64_t seed, uint64_t offset) {
     const Quad r = philox4x32_10(q, b, (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed,

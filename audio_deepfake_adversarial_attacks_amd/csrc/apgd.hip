@@ -14,12 +14,9 @@
 
 #include "advstep_apgd.h"
 #include "advstep_common.h"
+#include "row_tiles.h"
 
 namespace {
-
-constexpr int kVecs = 4;                           // float4 per thread per stream
-constexpr int kTileVec = kWgThreads * kVecs;       // float4 per workgroup tile
-static_assert(kTileVec * 4 == kWsRowTile, "one workspace partial per tile");
 
 constexpr int kNormLinf = 0, kNormL2 = 1;
 constexpr uint8_t kFooled = 1, kImproved = 2, kReset = 4;
@@ -37,39 +34,6 @@ __device__ __forceinline__ float ball_box(float v, float x, float eps) {
 }
 __device__ __forceinline__ float softplusf(float t) { return (t > 0.0f ? t : 0.0f) + log1pf(expf(-fabsf(t))); }
 
-// ---- tiles: float4 q of the row; VEC = rows are float4-addressable -----------------------------------------------------
-
-__device__ __forceinline__ int64_t quad_of(int tile, int j) { return (int64_t)tile * kTileVec + j * kWgThreads + threadIdx.x; }
-
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float *row, int64_t T, int64_t q, float fill) {
-    const int64_t s = q * 4;
-    if (VEC) return (s < T) ? reinterpret_cast<const float4 *>(row)[q] : make_float4(fill, fill, fill, fill);
-    return make_float4(s + 0 < T ? row[s + 0] : fill, s + 1 < T ? row[s + 1] : fill, s + 2 < T ? row[s + 2] : fill,
-                       s + 3 < T ? row[s + 3] : fill);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *row, int64_t T, int64_t q, float4 v) {
-    const int64_t s = q * 4;
-    if (VEC) {
-        if (s < T) reinterpret_cast<float4 *>(row)[q] = v;
-        return;
-    }
-    if (s + 0 < T) row[s + 0] = v.x;
-    if (s + 1 < T) row[s + 1] = v.y;
-    if (s + 2 < T) row[s + 2] = v.z;
-    if (s + 3 < T) row[s + 3] = v.w;
-}
-
-__device__ __forceinline__ float &lane(float4 &v, int k) { return reinterpret_cast<float *>(&v)[k]; }
-
-// Re-reduce the C partials of one row in a fixed order (every workgroup of the row does the same).
-__device__ __forceinline__ float row_sum(const float *__restrict__ part, int C, float *lds) {
-    float v = 0.0f;
-    for (int i = threadIdx.x; i < C; i += kWgThreads) v += part[i];
-    return wg_sum(v, lds);
-}
 __device__ __forceinline__ float row_max(const float *__restrict__ part, int C, float *lds) {
     float v = part[0];
     for (int i = threadIdx.x; i < C; i += kWgThreads) v = max_nan(v, part[i]);
@@ -376,20 +340,6 @@ __global__ __launch_bounds__(kWgThreads) void apgd_l2_pass_kernel(const float *_
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-
-inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
-    if (T % 4 != 0) return false;
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    return true;
-}
-
-inline bool overlaps(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bytes && y < x + bytes;
-}
-
-inline dim3 row_grid(int64_t B, int64_t T) { return dim3((unsigned)ws_tiles_per_row(T), (unsigned)B); }
 
 template <bool PHILOX>
 int apgd_init(const float *x, const float *draw, float *out, int64_t B, int64_t T, int norm, float eps, float lo, float hi,

@@ -13,6 +13,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   pgd_l2_init / pgd_l2_step          .../attacks/pgdl2.py:55-62, 78-88
   cw_*                               .../attacks/cw.py:57, 72-77, 87-103
   ce2_loss_grad                      .../attacks/pgd.py:62,50,68 (and the same lines of fgsm.py / pgdl2.py)
+  mi_step / vt_*                     .../attacks/mifgsm.py:70-76, nifgsm.py:56,67-71, vmifgsm.py:77-101
 """
 from __future__ import annotations
 
@@ -628,3 +629,82 @@ def apgd_l2_step(cur, prev, grad, x, step_size, eps: float, a: float, out=None, 
                                                   ws_bytes, _stream(cur.device))
     _lib.check(st, "advstep_apgd_l2_step_f32")
     return (out, norms) if return_norms else out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# momentum attacks (include/advstep_momentum.h; reference .../attacks/mifgsm.py:70-76, nifgsm.py:56,67-71,
+# vmifgsm.py:77-101, vnifgsm.py:65,78-102)
+# ---------------------------------------------------------------------------------------------------------
+
+def mi_step(adv, grad, orig, momentum, alpha: float, eps: float, decay: float, v=None, nes_out=None,
+            nes_scale: float = 0.0, lo: float = 0.0, hi: float = 1.0, out=None, return_mean: bool = False):
+    """One whole momentum update: a = grad (+ v); m' = a / mean_T |a| + momentum * decay (momentum IN PLACE);
+    out = clamp(orig + clamp(adv + alpha * sign(m') - orig, -eps, eps), lo, hi); nes_out = out + nes_scale * m' when given.
+    `out` may be `adv`.  return_mean: also the (B) row means of |a|."""
+    named = [("adv", adv), ("grad", grad), ("orig", orig), ("momentum", momentum)]
+    if v is not None:
+        named.append(("v", v))
+    if nes_out is not None:
+        named.append(("nes_out", nes_out))
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    B, T = _rows(adv, "adv")
+    out = _out_like(adv, out)
+    gmean = torch.empty(B, dtype=torch.float32, device=adv.device) if return_mean else None
+    # compulsory traffic: grad twice, momentum in and back, adv, orig, out (+ v twice, + nes_out)
+    with _Launch("mi_step", adv.device, tensors=(grad, grad, momentum, momentum, adv, orig, out, v, v, nes_out)):
+        ws, ws_bytes = _workspace(adv.device, B, T)
+        st = _lib.load().advstep_mi_step_f32(adv.data_ptr(), grad.data_ptr(), v.data_ptr() if v is not None else None,
+                                             orig.data_ptr(), momentum.data_ptr(), out.data_ptr(),
+                                             nes_out.data_ptr() if nes_out is not None else None, B, T, alpha, eps, decay,
+                                             nes_scale, lo, hi, gmean.data_ptr() if return_mean else None, ws, ws_bytes,
+                                             _stream(adv.device))
+    _lib.check(st, "advstep_mi_step_f32")
+    return (out, gmean) if return_mean else out
+
+
+def vt_neighbor(adv, bound: float, draw=None, seed: Optional[int] = None, offset: int = 0, out=None):
+    """A variance-tuning neighbour of vmifgsm.py:84-85: adv + U(-bound, bound), not clamped.  `draw` (the caller's draw) or a
+    Philox `seed`; neighbour j of iteration i of an attack call takes offset = i * N + j."""
+    _require(adv, "adv")
+    out = _out_like(adv, out)
+    if draw is not None:
+        _require(draw, "draw")
+        _same_shape(("adv", adv), ("draw", draw))
+        with _Launch("vt_neighbor", adv.device, tensors=(adv, draw, out)):
+            st = _lib.load().advstep_vt_neighbor_noise_f32(adv.data_ptr(), draw.data_ptr(), out.data_ptr(), adv.numel(),
+                                                           _stream(adv.device))
+        _lib.check(st, "advstep_vt_neighbor_noise_f32")
+    else:
+        if seed is None:
+            raise ValueError("vt_neighbor needs either `draw` or a Philox `seed`")
+        with _Launch("vt_neighbor", adv.device, tensors=(adv, out)):
+            st = _lib.load().advstep_vt_neighbor_philox_f32(adv.data_ptr(), out.data_ptr(), adv.numel(), bound, seed, offset,
+                                                            _stream(adv.device))
+        _lib.check(st, "advstep_vt_neighbor_philox_f32")
+    return out
+
+
+def vt_accumulate(gv, g, first: bool) -> None:
+    """In place: gv = g when `first` (the zero-filled accumulator of vmifgsm.py:82 plus g), else gv += g."""
+    _require(gv, "gv"), _require(g, "g")
+    _same_shape(("gv", gv), ("g", g))
+    with _Launch("vt_accumulate", gv.device, tensors=(g, gv) if first else (gv, g, gv)):
+        st = _lib.load().advstep_vt_accumulate_f32(gv.data_ptr(), g.data_ptr(), gv.numel(), 1 if first else 0,
+                                                   _stream(gv.device))
+    _lib.check(st, "advstep_vt_accumulate_f32")
+
+
+def vt_variance(gv, adv_grad, N: int, out=None):
+    """vmifgsm.py:97: gv / N - adv_grad."""
+    _require(gv, "gv"), _require(adv_grad, "adv_grad")
+    _same_shape(("gv", gv), ("adv_grad", adv_grad))
+    if int(N) < 1:
+        raise ValueError(f"N must be at least 1, got {N}")
+    out = _out_like(gv, out)
+    with _Launch("vt_variance", gv.device, tensors=(gv, adv_grad, out)):
+        st = _lib.load().advstep_vt_variance_f32(gv.data_ptr(), adv_grad.data_ptr(), out.data_ptr(), gv.numel(), int(N),
+                                                 _stream(gv.device))
+    _lib.check(st, "advstep_vt_variance_f32")
+    return out

@@ -1,15 +1,20 @@
 """Attack plugin API of the hot path (reference: adversarial_attacks/torchattacks/__init__.py).
 
 The attacks the north-star path names — FGSM, PGD, PGDL2, CW — FAB (the attack that completes the
-reference's AttackEnum) and APGD (the step-size-free gradient attack of AutoAttack), with the reference's constructor
+reference's AttackEnum), APGD (the step-size-free gradient attack of AutoAttack) and the momentum attacks made for
+transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
 from .attacks.cw import CW
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
+from .attacks.mifgsm import MIFGSM
+from .attacks.nifgsm import NIFGSM
 from .attacks.pgd import PGD
 from .attacks.pgdl2 import PGDL2
+from .attacks.vmifgsm import VMIFGSM
+from .attacks.vnifgsm import VNIFGSM
 
 __version__ = "3.2.7+advstep"
-__all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD"]
+__all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM"]

@@ -1,4 +1,4 @@
-"""hipGraph replay of the iterative attacks' inner loop (PGD, PGDL2).
+"""hipGraph replay of the iterative attacks' inner loop (PGD, PGDL2, MIFGSM, NIFGSM).
 
 One attack iteration on LCNN is ~37 kernel launches (model forward + input-backward through the fused kernels, the
 closed-form loss gradient, the fused update step) of fixed shapes; launched eagerly the launching thread is busy for as
@@ -64,9 +64,9 @@ def _state_signature(model: torch.nn.Module) -> Tuple:
 
 
 class _Captured:
-    def __init__(self, attack, images, labels, target, step_fn, fused: bool):
+    def __init__(self, attack, images, labels, target, step_fn, fused: bool, step_has_state: bool = False):
         dev = images.device
-        self.fused, self.step_fn = fused, step_fn
+        self.fused = fused
         self.images = torch.empty_like(images)
         self.adv_a = torch.empty_like(images)
         self.adv_b = torch.empty_like(images)
@@ -75,12 +75,19 @@ class _Captured:
         self.images.copy_(images), self.labels.copy_(labels), self.adv_a.copy_(images)
         if target is not None:
             self.target.copy_(target)
+        # A step that owns per-call state (MI-FGSM's momentum) is never launched here, not even to warm up: only the iterations
+        # of its own call may advance that state.  (Such steps stay out of the fused form: run_iterations.)
+        warm_step = not step_has_state
+        if not warm_step:
+            self.adv_b.copy_(images)                         # the warm-up's second model pass reads it
 
         def two_iterations():
             grad, _ = attack._input_gradient(self.adv_a, self.labels, self.target)
-            step_fn(self.adv_a.detach(), grad, self.images, self.adv_b)
+            if warm_step:
+                step_fn(self.adv_a.detach(), grad, self.images, self.adv_b)
             grad, _ = attack._input_gradient(self.adv_b, self.labels, self.target)
-            step_fn(self.adv_b.detach(), grad, self.images, self.adv_a)
+            if warm_step:
+                step_fn(self.adv_b.detach(), grad, self.images, self.adv_a)
 
         # warm-up on a side stream (torch's capture protocol): builds every lazily created cache and workspace
         side = torch.cuda.Stream(dev)
@@ -114,7 +121,8 @@ class _Captured:
         # the warm-up's buffers simply leave the table with the stream.)
         self._workspaces = hip_ops.release_stream_workspaces(side.cuda_stream)
 
-    def run(self, adv, images, labels, target, pairs: int) -> torch.Tensor:
+    def run(self, adv, images, labels, target, pairs: int, step_fn: Callable) -> torch.Tensor:
+        # `step_fn` is the CURRENT call's: a closure may own per-call state, and the one of the capturing call is long done
         # (adv_a / adv_b became autograd leaves during the capture: write through detached views)
         self.images.copy_(images), self.labels.copy_(labels), self.adv_a.detach().copy_(adv)
         if target is not None:
@@ -126,16 +134,18 @@ class _Captured:
         a, b = self.adv_a.detach(), self.adv_b.detach()
         for _ in range(pairs):
             self.graph_a.replay()
-            self.step_fn(a, self.grad_a, self.images, b)       # eager, on the launch stream: bracketable (hip_ops._Launch)
+            step_fn(a, self.grad_a, self.images, b)            # eager, on the launch stream: bracketable (hip_ops._Launch)
             self.graph_b.replay()
-            self.step_fn(b, self.grad_b, self.images, a)
+            step_fn(b, self.grad_b, self.images, a)
         return a
 
 
 def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torch.Tensor, target: Optional[torch.Tensor],
-                   steps: int, step_fn: Callable, hyper: Tuple) -> torch.Tensor:
+                   steps: int, step_fn: Callable, hyper: Tuple, step_has_state: bool = False) -> torch.Tensor:
     """`steps` iterations of  adv <- step_fn(adv, grad(adv), images, out)  starting from `adv`; returns the final adv
-    (detached, own storage).  step_fn(adv, grad, images, out) must write `out` (a different buffer than `adv`)."""
+    (detached, own storage).  step_fn(adv, grad, images, out) must write `out` (a different buffer than `adv`).
+    step_has_state: the closure owns buffers of this call that it updates at every step (MI-FGSM's momentum); the legacy
+    fused form would bake the capturing call's buffers into its graph, so such attacks stay eager under it."""
     from .. import hip_ops
     ops = attack.ops
     fused = fused_form()
@@ -143,7 +153,7 @@ def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torc
     # (start_profile(..., graph_ok=True): bench.py's timed region) go with the split form, whose steps are plain launches
     profiling_allows = hip_ops._profile is None or (hip_ops._profile_graph_ok and not fused)
     use_graph = (enabled() and ops is hip_ops and profiling_allows and adv.is_cuda and steps >= 4
-                 and not torch.cuda.is_current_stream_capturing())
+                 and not torch.cuda.is_current_stream_capturing() and not (fused and step_has_state))
     done = 0
     if use_graph:
         # family: what makes two calls the same workload; state: what a capture bakes in beyond that (parameter / buffer
@@ -167,7 +177,7 @@ def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torc
                 for stale in [k for k in _SEEN if k[:len(family)] == family and k != key]:
                     del _SEEN[stale]
                 try:
-                    cap = _Captured(attack, images, labels, target, step_fn, fused)
+                    cap = _Captured(attack, images, labels, target, step_fn, fused, step_has_state)
                     if len(_GRAPHS) >= _MAX_GRAPHS:
                         _GRAPHS.pop(next(iter(_GRAPHS)))
                     _GRAPHS[key] = cap
@@ -178,7 +188,7 @@ def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torc
                                   "continuing with eager launches for this workload")
                     cap = None
         if cap is not None:
-            adv = cap.run(adv, images, labels, target, steps // 2).detach().clone()
+            adv = cap.run(adv, images, labels, target, steps // 2, step_fn).detach().clone()
             done = 2 * (steps // 2)
     spare = None
     for _ in range(steps - done):
