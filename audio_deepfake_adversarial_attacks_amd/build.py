@@ -15,7 +15,7 @@ SOURCES = [PKG / "csrc" / "advstep.hip", PKG / "csrc" / "lcnn_mfm.hip", PKG / "c
            PKG / "csrc" / "detector_conv.hip", PKG / "csrc" / "apgd.hip", PKG / "csrc" / "momentum.hip"]
 HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants (tools/gen_stft_tables.py), #included by lfcc_stft.hip
            PKG / "csrc" / "advstep_common.h",      # internal helpers #included by every source
-           PKG / "csrc" / "row_tiles.h",           # (tile, row) addressing shared by apgd.hip and momentum.hip
+           PKG / "csrc" / "row_tiles.h",           # (tile, row) addressing and partial re-reductions of every row kernel
            ROOT / "include" / "advstep.h", ROOT / "include" / "advstep_lcnn.h", ROOT / "include" / "advstep_frontend.h",
            ROOT / "include" / "advstep_fab.h", ROOT / "include" / "advstep_dataset.h", ROOT / "include" / "advstep_detector.h",
            ROOT / "include" / "advstep_apgd.h", ROOT / "include" / "advstep_momentum.h"]

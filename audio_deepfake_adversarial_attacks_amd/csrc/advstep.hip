@@ -21,27 +21,11 @@
 
 #include "advstep.h"
 #include "advstep_common.h"
+#include "row_tiles.h"
 
 namespace {
 
-constexpr int kBlock = 256;                        // 4 wave64 per workgroup
-constexpr int kVecs = 4;                           // float4 per thread per stream
-constexpr int kTileVec = kBlock * kVecs;           // 1024 float4 per workgroup tile
-constexpr int kTile = kTileVec * 4;                // 4096 floats (16 KiB) per stream per tile
 constexpr int kMaxGrid = 256 * 16;                 // flat kernels: grid-stride beyond 16 tiles per CU
-
-// ---------------------------------------------------------------------------------------------------------
-// scalar semantics shared by all kernels
-// ---------------------------------------------------------------------------------------------------------
-
-// torch.sign: (0 < g) - (g < 0); NaN and +-0 give 0.
-__device__ __forceinline__ float sgn(float g) { return (float)(0.0f < g) - (float)(g < 0.0f); }
-
-// torch.clamp(v, lo, hi) = min(max(v, lo), hi), NaN in v propagates.
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {
-    v = (v < lo) ? lo : v;
-    return (v > hi) ? hi : v;
-}
 
 __device__ __forceinline__ float fgsm_elem(float x, float g, float eps, float lo, float hi) {
     return clampf(x + eps * sgn(g), lo, hi);
@@ -55,73 +39,21 @@ __device__ __forceinline__ float pgd_linf_elem(float a, float g, float x, float 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Philox4x32-10 streams (the generator itself is in advstep_common.h): the same stream on the CPU oracle and on the device.
-// ---------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ float f4_get(const float4 &v, int k) {
-    return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// workgroup reductions (wave64 shuffles -> LDS)
-// ---------------------------------------------------------------------------------------------------------
-
-struct SumOp {
-    __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
-};
-struct MinOp {
-    __device__ __forceinline__ float operator()(float a, float b) const { return min_nan(a, b); }
-};
-struct MaxOp {
-    __device__ __forceinline__ float operator()(float a, float b) const { return max_nan(a, b); }
-};
-
-template <class Op>
-__device__ __forceinline__ float wave_reduce(float v, Op op) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// All threads of the workgroup receive the result. `lds` holds >= 4 floats; two calls in a row must use
-// different slots (or be separated by the caller) — each call ends with a barrier on its own slot.
-template <class Op>
-__device__ __forceinline__ float block_reduce(float v, Op op, float *lds) {
-    v = wave_reduce(v, op);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) lds[wave] = v;
-    __syncthreads();
-    float r = lds[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) r = op(r, lds[w]);
-    return r;
-}
-
-// Re-reduce the C per-tile partials of one row (every workgroup of the row does this; C is 16 at T = 64 600).
-template <class Op>
-__device__ __forceinline__ float reduce_partials(const float *__restrict__ part, int C, float identity, Op op,
-                                                 float *lds) {
-    float v = identity;
-    for (int i = threadIdx.x; i < C; i += kBlock) v = op(v, part[i]);
-    return block_reduce(v, op, lds);
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // flat elementwise kernels: n = B*T samples, tile-strided, float4 when all pointers are 16-byte aligned
 // ---------------------------------------------------------------------------------------------------------
 
 // Generic driver: NIN input streams, one output stream, Op applied per sample; VECS float4 per thread per stream.
 template <int NIN, int VECS, class Op>
-__global__ __launch_bounds__(kBlock) void flat_vec_kernel(const float4 *__restrict__ in0,
+__global__ __launch_bounds__(kWgThreads) void flat_vec_kernel(const float4 *__restrict__ in0,
                                                           const float4 *__restrict__ in1,
                                                           const float4 *__restrict__ in2, float4 *out, int64_t n4,
                                                           int64_t ntiles, Op op) {
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t base = tile * (kBlock * VECS) + threadIdx.x;
+        const int64_t base = tile * (kWgThreads * VECS) + threadIdx.x;
         float4 a[VECS] = {}, b[VECS] = {}, c[VECS] = {};
 #pragma unroll
         for (int j = 0; j < VECS; ++j) {
-            const int64_t i = base + (int64_t)j * kBlock;
+            const int64_t i = base + (int64_t)j * kWgThreads;
             if (i < n4) {
                 a[j] = in0[i];
                 if (NIN > 1) b[j] = in1[i];
@@ -130,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void flat_vec_kernel(const float4 *__restri
         }
 #pragma unroll
         for (int j = 0; j < VECS; ++j) {
-            const int64_t i = base + (int64_t)j * kBlock;
+            const int64_t i = base + (int64_t)j * kWgThreads;
             if (i < n4) {
                 float4 o;
                 o.x = op(a[j].x, b[j].x, c[j].x);
@@ -145,11 +77,11 @@ __global__ __launch_bounds__(kBlock) void flat_vec_kernel(const float4 *__restri
 
 // Scalar twin for the (< 4)-sample tail and for unaligned buffers: samples [begin, n).
 template <int NIN, class Op>
-__global__ __launch_bounds__(kBlock) void flat_scalar_kernel(const float *__restrict__ in0,
+__global__ __launch_bounds__(kWgThreads) void flat_scalar_kernel(const float *__restrict__ in0,
                                                              const float *__restrict__ in1,
                                                              const float *__restrict__ in2, float *out,
                                                              int64_t begin, int64_t n, Op op) {
-    for (int64_t i = begin + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    for (int64_t i = begin + (int64_t)blockIdx.x * kWgThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kWgThreads) {
         const float a = in0[i];
         const float b = NIN > 1 ? in1[i] : 0.0f;
         const float c = NIN > 2 ? in2[i] : 0.0f;
@@ -182,7 +114,7 @@ struct CwInitOp {
 };
 
 // PGD L-inf random start with in-kernel Philox: quad index == float4 index.
-__global__ __launch_bounds__(kBlock) void pgd_linf_init_philox_vec_kernel(const float4 *__restrict__ x, float4 *out,
+__global__ __launch_bounds__(kWgThreads) void pgd_linf_init_philox_vec_kernel(const float4 *__restrict__ x, float4 *out,
                                                                           int64_t n4, int64_t ntiles, float eps,
                                                                           float lo, float hi, uint64_t seed,
                                                                           uint64_t offset) {
@@ -191,12 +123,12 @@ __global__ __launch_bounds__(kBlock) void pgd_linf_init_philox_vec_kernel(const 
         float4 a[kVecs];
 #pragma unroll
         for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = base + (int64_t)j * kBlock;
+            const int64_t i = base + (int64_t)j * kWgThreads;
             if (i < n4) a[j] = x[i];
         }
 #pragma unroll
         for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = base + (int64_t)j * kBlock;
+            const int64_t i = base + (int64_t)j * kWgThreads;
             if (i < n4) {
                 const float4 nz = philox_uniform4((uint64_t)i, seed, offset, eps);
                 float4 o;
@@ -210,13 +142,13 @@ __global__ __launch_bounds__(kBlock) void pgd_linf_init_philox_vec_kernel(const 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void pgd_linf_init_philox_scalar_kernel(const float *__restrict__ x, float *out,
+__global__ __launch_bounds__(kWgThreads) void pgd_linf_init_philox_scalar_kernel(const float *__restrict__ x, float *out,
                                                                              int64_t begin, int64_t n, float eps,
                                                                              float lo, float hi, uint64_t seed,
                                                                              uint64_t offset) {
-    for (int64_t i = begin + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    for (int64_t i = begin + (int64_t)blockIdx.x * kWgThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kWgThreads) {
         const float4 nz = philox_uniform4((uint64_t)(i >> 2), seed, offset, eps);
-        out[i] = clampf(x[i] + f4_get(nz, (int)(i & 3)), lo, hi);
+        out[i] = clampf(x[i] + lane(nz, (int)(i & 3)), lo, hi);
     }
 }
 
@@ -240,7 +172,7 @@ __device__ __forceinline__ void cw_adam_elem(float &w, float &m, float &v, float
     w = w + s.neg_step * (m / denom);
 }
 
-__global__ __launch_bounds__(kBlock) void cw_adam_vec_kernel(float4 *w, float4 *m, float4 *v,
+__global__ __launch_bounds__(kWgThreads) void cw_adam_vec_kernel(float4 *w, float4 *m, float4 *v,
                                                              const float4 *__restrict__ x,
                                                              const float4 *__restrict__ gm, int64_t n4,
                                                              int64_t ntiles, AdamScalars s) {
@@ -248,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void cw_adam_vec_kernel(float4 *w, float4 *
         const int64_t base = tile * kTileVec + threadIdx.x;
 #pragma unroll 2
         for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = base + (int64_t)j * kBlock;
+            const int64_t i = base + (int64_t)j * kWgThreads;
             if (i < n4) {
                 float4 W = w[i], M = m[i], V = v[i];
                 const float4 X = x[i], G = gm[i];
@@ -264,11 +196,11 @@ __global__ __launch_bounds__(kBlock) void cw_adam_vec_kernel(float4 *w, float4 *
     }
 }
 
-__global__ __launch_bounds__(kBlock) void cw_adam_scalar_kernel(float *w, float *m, float *v,
+__global__ __launch_bounds__(kWgThreads) void cw_adam_scalar_kernel(float *w, float *m, float *v,
                                                                 const float *__restrict__ x,
                                                                 const float *__restrict__ gm, int64_t begin,
                                                                 int64_t n, AdamScalars s) {
-    for (int64_t i = begin + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    for (int64_t i = begin + (int64_t)blockIdx.x * kWgThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kWgThreads) {
         float W = w[i], M = m[i], V = v[i];
         cw_adam_elem(W, M, V, x[i], gm[i], s);
         w[i] = W;
@@ -278,73 +210,14 @@ __global__ __launch_bounds__(kBlock) void cw_adam_scalar_kernel(float *w, float 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// row kernels: grid = (C tiles per row, B rows); tile c of row b covers samples [c*kTile, min(T, (c+1)*kTile))
-// VEC = rows are float4-addressable (T % 4 == 0 and 16-byte aligned bases).
+// row kernels: grid = (C tiles per row, B rows); tile addressing, whole-tile loads / stores and the re-reduction of a row's
+// partials are row_tiles.h's.  VEC = rows are float4-addressable (T % 4 == 0 and 16-byte aligned bases).
 // ---------------------------------------------------------------------------------------------------------
-
-// Loads the workgroup's tile of one row into registers (out-of-range lanes get `fill`).
-template <bool VEC>
-__device__ __forceinline__ void load_tile(const float *__restrict__ row, int64_t T, int tile, float fill,
-                                          float4 (&r)[kVecs]) {
-    if (VEC) {
-        const float4 *row4 = reinterpret_cast<const float4 *>(row);
-        const int64_t T4 = T >> 2;
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = (int64_t)tile * kTileVec + j * kBlock + threadIdx.x;
-            r[j] = (i < T4) ? row4[i] : make_float4(fill, fill, fill, fill);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = ((int64_t)tile * kTileVec + j * kBlock + threadIdx.x) * 4;
-            r[j].x = (i + 0 < T) ? row[i + 0] : fill;
-            r[j].y = (i + 1 < T) ? row[i + 1] : fill;
-            r[j].z = (i + 2 < T) ? row[i + 2] : fill;
-            r[j].w = (i + 3 < T) ? row[i + 3] : fill;
-        }
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store_tile(float *row, int64_t T, int tile, const float4 (&r)[kVecs]) {
-    if (VEC) {
-        float4 *row4 = reinterpret_cast<float4 *>(row);
-        const int64_t T4 = T >> 2;
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = (int64_t)tile * kTileVec + j * kBlock + threadIdx.x;
-            if (i < T4) row4[i] = r[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            const int64_t i = ((int64_t)tile * kTileVec + j * kBlock + threadIdx.x) * 4;
-            if (i + 0 < T) row[i + 0] = r[j].x;
-            if (i + 1 < T) row[i + 1] = r[j].y;
-            if (i + 2 < T) row[i + 2] = r[j].z;
-            if (i + 3 < T) row[i + 3] = r[j].w;
-        }
-    }
-}
-
-// Is sample k (0..3) of vector j of this thread inside the row?  (only needed where `fill` cannot be neutral)
-__device__ __forceinline__ bool in_row(int64_t T, int tile, int j, int k) {
-    return ((int64_t)tile * kTileVec + j * kBlock + threadIdx.x) * 4 + k < T;
-}
-
-#define ADV_FOR_EACH_LANE(r, expr)      \
-    _Pragma("unroll") for (int j = 0; j < kVecs; ++j) { \
-        { float &e = r[j].x; const int k = 0; (void)k; expr; } \
-        { float &e = r[j].y; const int k = 1; (void)k; expr; } \
-        { float &e = r[j].z; const int k = 2; (void)k; expr; } \
-        { float &e = r[j].w; const int k = 3; (void)k; expr; } \
-    }
 
 // ---- a1: to_minmax ----------------------------------------------------------------------------------------
 
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void minmax_partial_kernel(const float *__restrict__ x, int64_t T,
+__global__ __launch_bounds__(kWgThreads) void minmax_partial_kernel(const float *__restrict__ x, int64_t T,
                                                                 float *__restrict__ pmin, float *__restrict__ pmax) {
     __shared__ float lds[8];
     const int tile = blockIdx.x, C = gridDim.x;
@@ -355,9 +228,12 @@ __global__ __launch_bounds__(kBlock) void minmax_partial_kernel(const float *__r
     float4 r[kVecs];
     load_tile<VEC>(row, T, tile, fill, r);
     float lo = fill, hi = fill;
-    ADV_FOR_EACH_LANE(r, lo = min_nan(lo, e); hi = max_nan(hi, e));
-    lo = block_reduce(lo, MinOp(), lds);
-    hi = block_reduce(hi, MaxOp(), lds + 4);
+    for_each_lane(r, [&](float e) {
+        lo = min_nan(lo, e);
+        hi = max_nan(hi, e);
+    });
+    lo = wg_min_nan(lo, lds);
+    hi = wg_max_nan(hi, lds + 4);
     if (threadIdx.x == 0) {
         pmin[b * C + tile] = lo;
         pmax[b * C + tile] = hi;
@@ -365,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void minmax_partial_kernel(const float *__r
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void minmax_apply_kernel(const float *__restrict__ x, float *x01,
+__global__ __launch_bounds__(kWgThreads) void minmax_apply_kernel(const float *__restrict__ x, float *x01,
                                                               float *__restrict__ mn_out, float *__restrict__ mx_out,
                                                               int64_t T, const float *__restrict__ pmin,
                                                               const float *__restrict__ pmax) {
@@ -374,11 +250,10 @@ __global__ __launch_bounds__(kBlock) void minmax_apply_kernel(const float *__res
     const int64_t b = blockIdx.y;
     float4 r[kVecs];
     load_tile<VEC>(x + b * T, T, tile, 0.0f, r);
-    const float first = pmin[b * C];
-    const float mn = reduce_partials(pmin + b * C, C, first, MinOp(), lds);
-    const float mx = reduce_partials(pmax + b * C, C, pmax[b * C], MaxOp(), lds + 4);
+    const float mn = row_min(pmin + b * C, C, lds);
+    const float mx = row_max(pmax + b * C, C, lds + 4);
     const float range = mx - mn;
-    ADV_FOR_EACH_LANE(r, e = (e - mn) / range);
+    for_each_lane(r, [&](float &e) { e = (e - mn) / range; });
     store_tile<VEC>(x01 + b * T, T, tile, r);
     if (tile == 0 && threadIdx.x == 0) {
         mn_out[b] = mn;
@@ -389,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void minmax_apply_kernel(const float *__res
 // ---- a2: revert_minmax ------------------------------------------------------------------------------------
 
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void minmax_revert_kernel(const float *__restrict__ x01,
+__global__ __launch_bounds__(kWgThreads) void minmax_revert_kernel(const float *__restrict__ x01,
                                                                const float *__restrict__ mn,
                                                                const float *__restrict__ mx, float *out, int64_t T) {
     const int tile = blockIdx.x;
@@ -398,14 +273,14 @@ __global__ __launch_bounds__(kBlock) void minmax_revert_kernel(const float *__re
     load_tile<VEC>(x01 + b * T, T, tile, 0.0f, r);
     const float lo = mn[b];
     const float range = mx[b] - lo;
-    ADV_FOR_EACH_LANE(r, e = (e * range) + lo);
+    for_each_lane(r, [&](float &e) { e = (e * range) + lo; });
     store_tile<VEC>(out + b * T, T, tile, r);
 }
 
 // ---- row sum of squares (||grad||^2, ||normal||^2) ------------------------------------------------------------
 
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void sumsq_partial_kernel(const float *__restrict__ g, int64_t T,
+__global__ __launch_bounds__(kWgThreads) void sumsq_partial_kernel(const float *__restrict__ g, int64_t T,
                                                                float *__restrict__ part) {
     __shared__ float lds[4];
     const int tile = blockIdx.x, C = gridDim.x;
@@ -415,7 +290,7 @@ __global__ __launch_bounds__(kBlock) void sumsq_partial_kernel(const float *__re
     float s = 0.0f;
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) s += (r[j].x * r[j].x + r[j].y * r[j].y) + (r[j].z * r[j].z + r[j].w * r[j].w);
-    s = block_reduce(s, SumOp(), lds);
+    s = wg_sum(s, lds);
     if (threadIdx.x == 0) part[b * C + tile] = s;
 }
 
@@ -423,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void sumsq_partial_kernel(const float *__re
 
 // pass 2: gn from the grad partials; a = adv + alpha * (g / gn); d = a - orig; partial sum d^2
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pgd_l2_delta_kernel(const float *__restrict__ adv,
+__global__ __launch_bounds__(kWgThreads) void pgd_l2_delta_kernel(const float *__restrict__ adv,
                                                               const float *__restrict__ grad,
                                                               const float *__restrict__ orig, int64_t T, float alpha,
                                                               float eps_div, const float *__restrict__ gpart,
@@ -435,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_delta_kernel(const float *__res
     load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
     load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
     load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
-    const float gsq = reduce_partials(gpart + b * C, C, 0.0f, SumOp(), lds);
+    const float gsq = row_sum(gpart + b * C, C, lds);
     const float gn_raw = sqrtf(gsq);
     const float gn = gn_raw + eps_div;
     float s = 0.0f;
@@ -447,13 +322,13 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_delta_kernel(const float *__res
         d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
         d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
         // out-of-row lanes: a = g = x = 0 -> d = 0 when gn != 0; mask explicitly so gn == 0 / NaN cannot leak
-        if (!in_row(T, tile, j, 0)) d.x = 0.0f;
-        if (!in_row(T, tile, j, 1)) d.y = 0.0f;
-        if (!in_row(T, tile, j, 2)) d.z = 0.0f;
-        if (!in_row(T, tile, j, 3)) d.w = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 0)) d.x = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 1)) d.y = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 2)) d.z = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 3)) d.w = 0.0f;
         s += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
     }
-    s = block_reduce(s, SumOp(), lds + 4);
+    s = wg_sum(s, lds + 4);
     if (threadIdx.x == 0) {
         dpart[b * C + tile] = s;
         if (tile == 0 && gnorm) gnorm[b] = gn_raw;
@@ -462,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_delta_kernel(const float *__res
 
 // pass 3: recompute d, f = min((1/dn) * eps, 1), out = clamp(orig + d * f, lo, hi)
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pgd_l2_project_kernel(const float *__restrict__ adv,
+__global__ __launch_bounds__(kWgThreads) void pgd_l2_project_kernel(const float *__restrict__ adv,
                                                                 const float *__restrict__ grad,
                                                                 const float *__restrict__ orig, float *out, int64_t T,
                                                                 float alpha, float eps, float eps_div, float lo,
@@ -476,8 +351,8 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_project_kernel(const float *__r
     load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
     load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
     load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
-    const float gn = sqrtf(reduce_partials(gpart + b * C, C, 0.0f, SumOp(), lds)) + eps_div;
-    const float dn = sqrtf(reduce_partials(dpart + b * C, C, 0.0f, SumOp(), lds + 4));
+    const float gn = sqrtf(row_sum(gpart + b * C, C, lds)) + eps_div;
+    const float dn = sqrtf(row_sum(dpart + b * C, C, lds + 4));
     const float f = min_nan((1.0f / dn) * eps, 1.0f);
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
@@ -504,7 +379,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_project_kernel(const float *__r
 // word counts the single-pass calls that used it (the repair kernel behind every call advances it), so a granule of an earlier
 // call — or a word some other user of the scratch left there — never carries this call's tag and nothing has to be cleaned
 // between calls (round 5; rounds 2-3 zeroed the granules with a memset node, round 4 in the repair kernel).  The partial sums
-// and their re-reduction are the three-kernel path's own (same block_reduce, same order): results are bit-identical to it.
+// and their re-reduction are the three-kernel path's own (same wg_sum, same order): results are bit-identical to it.
 //
 // Co-residency.  A spinning workgroup must not wait for one that has no slot.  The host takes this path only when the
 // launch fits the device's resident capacity for THIS kernel (CU count x hipOccupancyMaxActiveBlocksPerMultiprocessor,
@@ -553,9 +428,9 @@ __device__ __forceinline__ float row_exchange_sum(unsigned long long *granules, 
         }
         if (!done && threadIdx.x == 0) *lds_failed = 1;
     }
-    // same reduction as reduce_partials(): thread i holds partial i (C <= 64 on this path), the others the identity
-    // (block_reduce's barrier also publishes *lds_failed)
-    return block_reduce(v, SumOp(), lds);
+    // same reduction as row_sum(): thread i holds partial i (C <= 64 on this path), the others the identity
+    // (wg_sum's barrier also publishes *lds_failed)
+    return wg_sum(v, lds);
 }
 
 // A workgroup that gives up: flag the row, poison this workgroup's granules of the phases it will not reach.
@@ -575,7 +450,7 @@ __device__ __forceinline__ void row_exchange_abandon(unsigned *fail, int64_t b, 
 // in LDS (16 KB per workgroup, 8 workgroups per CU = 128 of the 160 KB) and is read back where it is used; adv and grad stay
 // in registers.  (With all three in registers hipcc spilled 15 dwords per lane: 31 MB of scratch writes per launch.)
 template <bool VEC>
-__global__ __launch_bounds__(kBlock, 8) void pgd_l2_fused_kernel(const float *__restrict__ adv, const float *__restrict__ grad,
+__global__ __launch_bounds__(kWgThreads, 8) void pgd_l2_fused_kernel(const float *__restrict__ adv, const float *__restrict__ grad,
                                                                  const float *__restrict__ orig, float *out, int64_t T,
                                                                  float alpha, float eps, float eps_div, float lo, float hi,
                                                                  unsigned long long *__restrict__ gran_g,
@@ -593,14 +468,14 @@ __global__ __launch_bounds__(kBlock, 8) void pgd_l2_fused_kernel(const float *__
         float4 x[kVecs];
         load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
 #pragma unroll
-        for (int j = 0; j < kVecs; ++j) xs[j * kBlock + threadIdx.x] = x[j];      // each thread reads back only its own slots
+        for (int j = 0; j < kVecs; ++j) xs[j * kWgThreads + threadIdx.x] = x[j];      // each thread reads back only its own slots
     }
     load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
     load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
     float s = 0.0f;
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) s += (g[j].x * g[j].x + g[j].y * g[j].y) + (g[j].z * g[j].z + g[j].w * g[j].w);
-    s = block_reduce(s, SumOp(), lds);
+    s = wg_sum(s, lds);
     const unsigned base = exchange_tag_base(epoch);
     const float gsq = row_exchange_sum(gran_g + b * C, C, tile, s, base, 1u, spin_limit, lds + 4, &failed);
     if (failed) {
@@ -612,19 +487,19 @@ __global__ __launch_bounds__(kBlock, 8) void pgd_l2_fused_kernel(const float *__
     s = 0.0f;
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
-        const float4 x = xs[j * kBlock + threadIdx.x];
+        const float4 x = xs[j * kWgThreads + threadIdx.x];
         float4 m;
         m.x = (a[j].x + alpha * (g[j].x / gn)) - x.x;
         m.y = (a[j].y + alpha * (g[j].y / gn)) - x.y;
         m.z = (a[j].z + alpha * (g[j].z / gn)) - x.z;
         m.w = (a[j].w + alpha * (g[j].w / gn)) - x.w;
-        if (!in_row(T, tile, j, 0)) m.x = 0.0f;
-        if (!in_row(T, tile, j, 1)) m.y = 0.0f;
-        if (!in_row(T, tile, j, 2)) m.z = 0.0f;
-        if (!in_row(T, tile, j, 3)) m.w = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 0)) m.x = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 1)) m.y = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 2)) m.z = 0.0f;
+        if (!in_row(T, quad_of(tile, j), 3)) m.w = 0.0f;
         s += (m.x * m.x + m.y * m.y) + (m.z * m.z + m.w * m.w);
     }
-    s = block_reduce(s, SumOp(), lds + 8);
+    s = wg_sum(s, lds + 8);
     const float dn = sqrtf(row_exchange_sum(gran_d + b * C, C, tile, s, base, 2u, spin_limit, lds + 4, &failed));
     if (failed) {
         row_exchange_abandon(fail, b, nullptr, gran_d + b * C, tile, base);
@@ -633,7 +508,7 @@ __global__ __launch_bounds__(kBlock, 8) void pgd_l2_fused_kernel(const float *__
     const float f = min_nan((1.0f / dn) * eps, 1.0f);
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {      // d recomputed (same expressions, same bits) rather than kept across the exchange
-        const float4 x = xs[j * kBlock + threadIdx.x];
+        const float4 x = xs[j * kWgThreads + threadIdx.x];
         float4 d;
         d.x = (a[j].x + alpha * (g[j].x / gn)) - x.x;
         d.y = (a[j].y + alpha * (g[j].y / gn)) - x.y;
@@ -676,7 +551,7 @@ __device__ __forceinline__ unsigned take_flag(unsigned *fail, unsigned *last, un
 // pgd_l2_project), so a repaired row carries the same bits as any other.  adv / orig / grad are re-read from global memory:
 // the single-pass path is not taken when `out` aliases an input.
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pgd_l2_repair_kernel(const float *__restrict__ adv, const float *__restrict__ grad,
+__global__ __launch_bounds__(kWgThreads) void pgd_l2_repair_kernel(const float *__restrict__ adv, const float *__restrict__ grad,
                                                                const float *__restrict__ orig, float *out, int64_t T, int C,
                                                                float alpha, float eps, float eps_div, float lo, float hi,
                                                                unsigned *fail, unsigned *last, unsigned *epoch,
@@ -690,11 +565,11 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_repair_kernel(const float *__re
         float s = 0.0f;
 #pragma unroll
         for (int j = 0; j < kVecs; ++j) s += (g[j].x * g[j].x + g[j].y * g[j].y) + (g[j].z * g[j].z + g[j].w * g[j].w);
-        s = block_reduce(s, SumOp(), lds);
+        s = wg_sum(s, lds);
         if (threadIdx.x == 0) gpart[tile] = s;
         __syncthreads();
     }
-    const float gn_raw = sqrtf(reduce_partials(gpart, C, 0.0f, SumOp(), lds + 4));
+    const float gn_raw = sqrtf(row_sum(gpart, C, lds + 4));
     const float gn = gn_raw + eps_div;
     for (int tile = 0; tile < C; ++tile) {
         load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
@@ -708,17 +583,17 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_repair_kernel(const float *__re
             d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
             d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
             d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-            if (!in_row(T, tile, j, 0)) d.x = 0.0f;
-            if (!in_row(T, tile, j, 1)) d.y = 0.0f;
-            if (!in_row(T, tile, j, 2)) d.z = 0.0f;
-            if (!in_row(T, tile, j, 3)) d.w = 0.0f;
+            if (!in_row(T, quad_of(tile, j), 0)) d.x = 0.0f;
+            if (!in_row(T, quad_of(tile, j), 1)) d.y = 0.0f;
+            if (!in_row(T, quad_of(tile, j), 2)) d.z = 0.0f;
+            if (!in_row(T, quad_of(tile, j), 3)) d.w = 0.0f;
             s += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
         }
-        s = block_reduce(s, SumOp(), lds);
+        s = wg_sum(s, lds);
         if (threadIdx.x == 0) dpart[tile] = s;
         __syncthreads();
     }
-    const float dn = sqrtf(reduce_partials(dpart, C, 0.0f, SumOp(), lds + 8));
+    const float dn = sqrtf(row_sum(dpart, C, lds + 8));
     const float f = min_nan((1.0f / dn) * eps, 1.0f);
     for (int tile = 0; tile < C; ++tile) {
         load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
@@ -757,7 +632,7 @@ __global__ __launch_bounds__(64) void count_flags_kernel(const unsigned *__restr
 
 // explicit draws: out = clamp(x + normal * ((r / nrm) * eps), lo, hi)
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pgd_l2_init_noise_kernel(const float *__restrict__ x,
+__global__ __launch_bounds__(kWgThreads) void pgd_l2_init_noise_kernel(const float *__restrict__ x,
                                                                    const float *__restrict__ normal,
                                                                    const float *__restrict__ r, float *out, int64_t T,
                                                                    float eps, float lo, float hi,
@@ -768,7 +643,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_init_noise_kernel(const float *
     float4 xv[kVecs], nz[kVecs];
     load_tile<VEC>(x + b * T, T, tile, 0.0f, xv);
     load_tile<VEC>(normal + b * T, T, tile, 0.0f, nz);
-    const float nrm = sqrtf(reduce_partials(npart + b * C, C, 0.0f, SumOp(), lds));
+    const float nrm = sqrtf(row_sum(npart + b * C, C, lds));
     const float scale = (r[b] / nrm) * eps;
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
@@ -785,19 +660,19 @@ __device__ __forceinline__ void philox_normal_tile(int64_t T, int tile, uint32_t
                                                    float4 (&nz)[kVecs]) {
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
-        const int64_t q = (int64_t)tile * kTileVec + j * kBlock + threadIdx.x;
-        if (q * 4 < T) {
+        const int64_t q = quad_of(tile, j);
+        if (in_row(T, q, 0)) {
             nz[j] = philox_normal4((uint32_t)q, b, seed, offset);
-            if (q * 4 + 1 >= T) nz[j].y = 0.0f;
-            if (q * 4 + 2 >= T) nz[j].z = 0.0f;
-            if (q * 4 + 3 >= T) nz[j].w = 0.0f;
+            if (!in_row(T, q, 1)) nz[j].y = 0.0f;
+            if (!in_row(T, q, 2)) nz[j].z = 0.0f;
+            if (!in_row(T, q, 3)) nz[j].w = 0.0f;
         } else {
             nz[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
     }
 }
 
-__global__ __launch_bounds__(kBlock) void philox_normal_sumsq_kernel(int64_t T, uint64_t seed, uint64_t offset,
+__global__ __launch_bounds__(kWgThreads) void philox_normal_sumsq_kernel(int64_t T, uint64_t seed, uint64_t offset,
                                                                      float *__restrict__ part) {
     __shared__ float lds[4];
     const int tile = blockIdx.x, C = gridDim.x;
@@ -808,12 +683,12 @@ __global__ __launch_bounds__(kBlock) void philox_normal_sumsq_kernel(int64_t T, 
 #pragma unroll
     for (int j = 0; j < kVecs; ++j)
         s += (nz[j].x * nz[j].x + nz[j].y * nz[j].y) + (nz[j].z * nz[j].z + nz[j].w * nz[j].w);
-    s = block_reduce(s, SumOp(), lds);
+    s = wg_sum(s, lds);
     if (threadIdx.x == 0) part[b * C + tile] = s;
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pgd_l2_init_philox_kernel(const float *__restrict__ x, float *out,
+__global__ __launch_bounds__(kWgThreads) void pgd_l2_init_philox_kernel(const float *__restrict__ x, float *out,
                                                                     int64_t T, float eps, float lo, float hi,
                                                                     uint64_t seed, uint64_t offset,
                                                                     const float *__restrict__ npart) {
@@ -823,7 +698,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_init_philox_kernel(const float 
     float4 xv[kVecs], nz[kVecs];
     load_tile<VEC>(x + b * T, T, tile, 0.0f, xv);
     philox_normal_tile(T, tile, (uint32_t)b, seed, offset, nz);
-    const float nrm = sqrtf(reduce_partials(npart + b * C, C, 0.0f, SumOp(), lds));
+    const float nrm = sqrtf(row_sum(npart + b * C, C, lds));
     const uint64_t off1 = offset + 1;
     const Quad rq = philox4x32_10((uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)off1, (uint32_t)(off1 >> 32),
                                   (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -841,7 +716,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_init_philox_kernel(const float 
 // The same start in ONE launch: the normals are generated once and stay in registers across the row exchange of ||n||^2
 // (granule protocol of pgd_l2_fused_kernel; same partial sums and re-reduction as the two-kernel path: bit-identical).
 template <bool VEC>
-__global__ __launch_bounds__(kBlock, 8) void pgd_l2_init_philox_fused_kernel(const float *__restrict__ x, float *out, int64_t T,
+__global__ __launch_bounds__(kWgThreads, 8) void pgd_l2_init_philox_fused_kernel(const float *__restrict__ x, float *out, int64_t T,
                                                                              float eps, float lo, float hi, uint64_t seed,
                                                                              uint64_t offset,
                                                                              unsigned long long *__restrict__ gran,
@@ -858,7 +733,7 @@ __global__ __launch_bounds__(kBlock, 8) void pgd_l2_init_philox_fused_kernel(con
 #pragma unroll
     for (int j = 0; j < kVecs; ++j)
         s += (nz[j].x * nz[j].x + nz[j].y * nz[j].y) + (nz[j].z * nz[j].z + nz[j].w * nz[j].w);
-    s = block_reduce(s, SumOp(), lds);
+    s = wg_sum(s, lds);
     // the tile of x is requested BEFORE the exchange (16-byte path): its HBM latency then runs under the wait for the row's other
     // workgroups; the scalar path (rows not 16-byte addressable) keeps it behind - 16 more live registers make it spill
     float4 xv[kVecs];
@@ -887,7 +762,7 @@ __global__ __launch_bounds__(kBlock, 8) void pgd_l2_init_philox_fused_kernel(con
 // Repair pass of the single-pass start (see pgd_l2_repair_kernel): the two-kernel path's arithmetic, one workgroup per
 // flagged row.
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pgd_l2_init_philox_repair_kernel(const float *__restrict__ x, float *out, int64_t T, int C,
+__global__ __launch_bounds__(kWgThreads) void pgd_l2_init_philox_repair_kernel(const float *__restrict__ x, float *out, int64_t T, int C,
                                                                            float eps, float lo, float hi, uint64_t seed,
                                                                            uint64_t offset, unsigned *fail, unsigned *last,
                                                                            unsigned *epoch) {
@@ -901,11 +776,11 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_init_philox_repair_kernel(const
 #pragma unroll
         for (int j = 0; j < kVecs; ++j)
             s += (nz[j].x * nz[j].x + nz[j].y * nz[j].y) + (nz[j].z * nz[j].z + nz[j].w * nz[j].w);
-        s = block_reduce(s, SumOp(), lds);
+        s = wg_sum(s, lds);
         if (threadIdx.x == 0) npart[tile] = s;
         __syncthreads();
     }
-    const float nrm = sqrtf(reduce_partials(npart, C, 0.0f, SumOp(), lds + 4));
+    const float nrm = sqrtf(row_sum(npart, C, lds + 4));
     const uint64_t off1 = offset + 1;
     const Quad rq = philox4x32_10((uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)off1, (uint32_t)(off1 >> 32),
                                   (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -928,7 +803,7 @@ __global__ __launch_bounds__(kBlock) void pgd_l2_init_philox_repair_kernel(const
 
 // adv = 1/2 * (tanh(w) + 1); partial sum (adv - x)^2
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void cw_tanh_sqdist_kernel(const float *__restrict__ w,
+__global__ __launch_bounds__(kWgThreads) void cw_tanh_sqdist_kernel(const float *__restrict__ w,
                                                                 const float *__restrict__ x, float *adv, int64_t T,
                                                                 float *__restrict__ part) {
     __shared__ float lds[4];
@@ -949,7 +824,7 @@ __global__ __launch_bounds__(kBlock) void cw_tanh_sqdist_kernel(const float *__r
         s += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
     store_tile<VEC>(adv + b * T, T, tile, wv);
-    s = block_reduce(s, SumOp(), lds);
+    s = wg_sum(s, lds);
     if (threadIdx.x == 0) part[b * C + tile] = s;
 }
 
@@ -965,7 +840,7 @@ __global__ __launch_bounds__(64) void row_partials_sum_kernel(const float *__res
 
 // best = mask * adv + (1 - mask) * best
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void cw_best_update_kernel(const float *__restrict__ adv,
+__global__ __launch_bounds__(kWgThreads) void cw_best_update_kernel(const float *__restrict__ adv,
                                                                 const float *__restrict__ mask, float *best,
                                                                 int64_t T) {
     const int tile = blockIdx.x;
@@ -987,18 +862,14 @@ __global__ __launch_bounds__(kBlock) void cw_best_update_kernel(const float *__r
 
 // ---- a8: 2-logit cross-entropy, closed form ------------------------------------------------------------------------
 
-__device__ __forceinline__ float softplusf(float t) {  // log(1 + exp(t)), stable
-    return (t > 0.0f ? t : 0.0f) + log1pf(expf(-fabsf(t)));
-}
-
-__global__ __launch_bounds__(kBlock) void ce2_loss_grad_kernel(const float *__restrict__ z,
+__global__ __launch_bounds__(kWgThreads) void ce2_loss_grad_kernel(const float *__restrict__ z,
                                                                const int64_t *__restrict__ labels,
                                                                float *__restrict__ dz, float *__restrict__ loss,
                                                                int64_t B, float scale) {
     __shared__ float lds[4];
     const float invB = 1.0f / (float)B;
     float acc = 0.0f;
-    for (int64_t b = threadIdx.x; b < B; b += kBlock) {
+    for (int64_t b = threadIdx.x; b < B; b += kWgThreads) {
         // CE([-z, z], y) = softplus(u), u = (1 - 2y) * 2z;  d/dz = (1 - 2y) * 2 * sigmoid(u).
         // (sigmoid(2z) - y written without the cancellation at saturated logits.)
         const float flip = 1.0f - 2.0f * (float)labels[b];
@@ -1007,18 +878,13 @@ __global__ __launch_bounds__(kBlock) void ce2_loss_grad_kernel(const float *__re
         const float sig = 1.0f / (1.0f + expf(-u));
         dz[b] = scale * ((2.0f * invB) * (flip * sig));
     }
-    acc = block_reduce(acc, SumOp(), lds);
+    acc = wg_sum(acc, lds);
     if (threadIdx.x == 0) loss[0] = scale * (acc * invB);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // host-side helpers
 // ---------------------------------------------------------------------------------------------------------
-
-// the row workspace's layout (RowWs, carve_ws) lives in advstep_common.h: csrc/apgd.hip carves the same buffer
-static_assert(kTile == kWsRowTile, "the workspace planes hold one partial per 4096-sample tile");
-inline int tiles_per_row(int64_t T) { return ws_tiles_per_row(T); }
-
 
 // ADVSTEP_L2_SINGLE_PASS=0 keeps the three-kernel PGD-L2 step (A/B measurements, read at every call); default on.
 inline bool l2_single_pass() {
@@ -1034,7 +900,7 @@ inline unsigned l2_spin_limit() {
     return 1u << 17;
 }
 
-// How many workgroups of `kernel` (kBlock threads, its static LDS) the CURRENT device holds at once: CU count x the
+// How many workgroups of `kernel` (kWgThreads threads, its static LDS) the CURRENT device holds at once: CU count x the
 // occupancy the runtime computes for this kernel's registers / LDS.  Queried once per (device, kernel); 0 if the query
 // fails (the caller then takes the multi-kernel path).  ADVSTEP_L2_CAPACITY overrides it (tests: a "smaller device").
 enum { kCapStepVec, kCapStepScalar, kCapInitVec, kCapInitScalar, kCapKinds };
@@ -1048,7 +914,7 @@ inline int64_t l2_resident_capacity(int kind, const void *kernel) {
     if (c == 0) {
         int cus = 0, per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) == hipSuccess && cus > 0 && per_cu > 0)
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWgThreads, 0) == hipSuccess && cus > 0 && per_cu > 0)
             c = (int64_t)cus * per_cu;
         else
             c = -1;
@@ -1057,14 +923,6 @@ inline int64_t l2_resident_capacity(int kind, const void *kernel) {
     }
     return c > 0 ? c : 0;
 }
-
-inline bool overlaps(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bytes && y < x + bytes;
-}
-
-// grid.y is limited to 65535 rows per launch; batches beyond that are launched in slabs.
-constexpr int64_t kMaxRowsPerLaunch = 65535;
 
 // float4 per thread per stream of the flat kernels.  Measured on MI355X at B = 128, T = 64 600 (tools/tune_pgd_step.hip,
 // profiles/): one float4 per stream per thread (8 076 workgroups) beats 4 (2 019 workgroups) by 3 % hot / 7 % cold.
@@ -1081,10 +939,10 @@ inline int flat_vecs() {
 template <int NIN, int VECS, class Op>
 void launch_flat_vec(const float *in0, const float *in1, const float *in2, float *out, int64_t n4, Op op,
                      hipStream_t st) {
-    const int64_t ntiles = ceil_div(n4, kBlock * VECS);
+    const int64_t ntiles = ceil_div(n4, kWgThreads * VECS);
     const int64_t cap = (int64_t)kMaxGrid * (4 / VECS);
     const int grid = (int)(ntiles < cap ? ntiles : cap);
-    hipLaunchKernelGGL((flat_vec_kernel<NIN, VECS, Op>), dim3(grid), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL((flat_vec_kernel<NIN, VECS, Op>), dim3(grid), dim3(kWgThreads), 0, st,
                        reinterpret_cast<const float4 *>(in0), reinterpret_cast<const float4 *>(in1),
                        reinterpret_cast<const float4 *>(in2), reinterpret_cast<float4 *>(out), n4, ntiles, op);
 }
@@ -1104,19 +962,12 @@ int launch_flat(const float *in0, const float *in1, const float *in2, float *out
     }
     const int64_t begin = n4 * 4;
     if (begin < n) {
-        const int64_t blocks = ceil_div(n - begin, kBlock);
+        const int64_t blocks = ceil_div(n - begin, kWgThreads);
         const int grid = (int)(blocks < kMaxGrid ? blocks : kMaxGrid);
-        hipLaunchKernelGGL((flat_scalar_kernel<NIN, Op>), dim3(grid), dim3(kBlock), 0, st, in0, in1, in2, out, begin,
+        hipLaunchKernelGGL((flat_scalar_kernel<NIN, Op>), dim3(grid), dim3(kWgThreads), 0, st, in0, in1, in2, out, begin,
                            n, op);
     }
     return status_after_launch();
-}
-
-inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
-    if (T % 4 != 0) return false;
-    for (const void *p : ptrs)
-        if (!aligned16(p)) return false;
-    return true;
 }
 
 }  // namespace
@@ -1125,17 +976,18 @@ inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
 
-// Launch a row kernel over all B rows in slabs of <= 65535 rows; `ARGS` may use `b0` (first row of the slab).
-#define ADV_LAUNCH_ROWS(KERNEL, VECFLAG, B, T, st, ...)                                          \
-    do {                                                                                         \
-        const int C_ = tiles_per_row(T);                                                         \
-        for (int64_t b0 = 0; b0 < (B); b0 += kMaxRowsPerLaunch) {                                \
-            const int64_t nb_ = ((B)-b0 < kMaxRowsPerLaunch) ? ((B)-b0) : kMaxRowsPerLaunch;     \
-            if (VECFLAG)                                                                         \
-                hipLaunchKernelGGL((KERNEL<true>), dim3(C_, (unsigned)nb_), dim3(kBlock), 0, st, __VA_ARGS__); \
-            else                                                                                 \
-                hipLaunchKernelGGL((KERNEL<false>), dim3(C_, (unsigned)nb_), dim3(kBlock), 0, st, __VA_ARGS__); \
-        }                                                                                        \
+// Launch a row kernel over all B rows in slabs of <= kMaxGridY rows (grid.y is 16 bits); `ARGS` may use `b0` (first row of
+// the slab).  Only this file slabs: apgd.hip and momentum.hip reject B > kMaxGridY.
+#define ADV_LAUNCH_ROWS(KERNEL, VECFLAG, B, T, st, ...)                                                    \
+    do {                                                                                                   \
+        const int C_ = ws_tiles_per_row(T);                                                                \
+        for (int64_t b0 = 0; b0 < (B); b0 += kMaxGridY) {                                                  \
+            const int64_t nb_ = ((B)-b0 < kMaxGridY) ? ((B)-b0) : kMaxGridY;                               \
+            if (VECFLAG)                                                                                   \
+                hipLaunchKernelGGL((KERNEL<true>), dim3(C_, (unsigned)nb_), dim3(kWgThreads), 0, st, __VA_ARGS__);  \
+            else                                                                                           \
+                hipLaunchKernelGGL((KERNEL<false>), dim3(C_, (unsigned)nb_), dim3(kWgThreads), 0, st, __VA_ARGS__); \
+        }                                                                                                  \
     } while (0)
 
 extern "C" {
@@ -1176,7 +1028,7 @@ int advstep_minmax_normalize_f32(const float *x, float *x01, float *mn, float *m
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x, x01});
-    const int C = tiles_per_row(T);
+    const int C = ws_tiles_per_row(T);
     ADV_LAUNCH_ROWS(minmax_partial_kernel, vec, B, T, st, x + b0 * T, T, w.p0 + b0 * C, w.p1 + b0 * C);
     ADV_LAUNCH_ROWS(minmax_apply_kernel, vec, B, T, st, x + b0 * T, x01 + b0 * T, mn + b0, mx + b0, T, w.p0 + b0 * C,
                     w.p1 + b0 * C);
@@ -1221,15 +1073,15 @@ int advstep_pgd_linf_init_philox_f32(const float *x, float *out, int64_t n, floa
     if (n4 > 0) {
         const int64_t ntiles = ceil_div(n4, kTileVec);
         const int grid = (int)(ntiles < kMaxGrid ? ntiles : kMaxGrid);
-        hipLaunchKernelGGL(pgd_linf_init_philox_vec_kernel, dim3(grid), dim3(kBlock), 0, st,
+        hipLaunchKernelGGL(pgd_linf_init_philox_vec_kernel, dim3(grid), dim3(kWgThreads), 0, st,
                            reinterpret_cast<const float4 *>(x), reinterpret_cast<float4 *>(out), n4, ntiles, eps, lo,
                            hi, seed, offset);
     }
     const int64_t begin = n4 * 4;
     if (begin < n) {
-        const int64_t blocks = ceil_div(n - begin, kBlock);
+        const int64_t blocks = ceil_div(n - begin, kWgThreads);
         const int grid = (int)(blocks < kMaxGrid ? blocks : kMaxGrid);
-        hipLaunchKernelGGL(pgd_linf_init_philox_scalar_kernel, dim3(grid), dim3(kBlock), 0, st, x, out, begin, n, eps,
+        hipLaunchKernelGGL(pgd_linf_init_philox_scalar_kernel, dim3(grid), dim3(kWgThreads), 0, st, x, out, begin, n, eps,
                            lo, hi, seed, offset);
     }
     return status_after_launch();
@@ -1253,7 +1105,7 @@ int advstep_pgd_l2_init_noise_f32(const float *x, const float *normal, const flo
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x, normal, out});
-    const int C = tiles_per_row(T);
+    const int C = ws_tiles_per_row(T);
     ADV_LAUNCH_ROWS(sumsq_partial_kernel, vec, B, T, st, normal + b0 * T, T, w.p0 + b0 * C);
     ADV_LAUNCH_ROWS(pgd_l2_init_noise_kernel, vec, B, T, st, x + b0 * T, normal + b0 * T, r + b0, out + b0 * T, T, eps,
                     lo, hi, w.p0 + b0 * C);
@@ -1266,31 +1118,31 @@ int advstep_pgd_l2_init_philox_f32(const float *x, float *out, int64_t B, int64_
     ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x && out);
-    ADVSTEP_REQUIRE(B <= kMaxRowsPerLaunch);  // the Philox counter carries the absolute row index
+    ADVSTEP_REQUIRE(B <= kMaxGridY);  // the Philox counter carries the absolute row index
     RowWs w;
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x, out});
-    const int C = tiles_per_row(T);
+    const int C = ws_tiles_per_row(T);
     const void *fused = vec ? (const void *)pgd_l2_init_philox_fused_kernel<true> : (const void *)pgd_l2_init_philox_fused_kernel<false>;
     if (l2_single_pass() && C <= 64 && !overlaps(x, out, (size_t)B * T * sizeof(float)) &&
         B * C <= l2_resident_capacity(vec ? kCapInitVec : kCapInitScalar, fused)) {
         // the repair kernel behind the launch serves flagged rows, lowers their flags and advances the epoch (closes the call)
         const unsigned spins = l2_spin_limit();
         if (vec) {
-            hipLaunchKernelGGL(pgd_l2_init_philox_fused_kernel<true>, dim3(C, (unsigned)B), dim3(kBlock), 0, st, x, out, T, eps, lo,
+            hipLaunchKernelGGL(pgd_l2_init_philox_fused_kernel<true>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, x, out, T, eps, lo,
                                hi, seed, offset, w.gran0, w.fail, w.epoch, spins);
-            hipLaunchKernelGGL(pgd_l2_init_philox_repair_kernel<true>, dim3((unsigned)B), dim3(kBlock), 0, st, x, out, T, C, eps,
+            hipLaunchKernelGGL(pgd_l2_init_philox_repair_kernel<true>, dim3((unsigned)B), dim3(kWgThreads), 0, st, x, out, T, C, eps,
                                lo, hi, seed, offset, w.fail, w.last, w.epoch);
         } else {
-            hipLaunchKernelGGL(pgd_l2_init_philox_fused_kernel<false>, dim3(C, (unsigned)B), dim3(kBlock), 0, st, x, out, T, eps, lo,
+            hipLaunchKernelGGL(pgd_l2_init_philox_fused_kernel<false>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, x, out, T, eps, lo,
                                hi, seed, offset, w.gran0, w.fail, w.epoch, spins);
-            hipLaunchKernelGGL(pgd_l2_init_philox_repair_kernel<false>, dim3((unsigned)B), dim3(kBlock), 0, st, x, out, T, C, eps,
+            hipLaunchKernelGGL(pgd_l2_init_philox_repair_kernel<false>, dim3((unsigned)B), dim3(kWgThreads), 0, st, x, out, T, C, eps,
                                lo, hi, seed, offset, w.fail, w.last, w.epoch);
         }
         return status_after_launch();
     }
-    hipLaunchKernelGGL(philox_normal_sumsq_kernel, dim3(C, (unsigned)B), dim3(kBlock), 0, st, T, seed, offset, w.p0);
+    hipLaunchKernelGGL(philox_normal_sumsq_kernel, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, T, seed, offset, w.p0);
     ADV_LAUNCH_ROWS(pgd_l2_init_philox_kernel, vec, B, T, st, x, out, T, eps, lo, hi, seed, offset, w.p0);
     return status_after_launch();
 }
@@ -1305,7 +1157,7 @@ int advstep_pgd_l2_step_f32(const float *adv, const float *grad, const float *or
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, grad, orig, out});
-    const int C = tiles_per_row(T);
+    const int C = ws_tiles_per_row(T);
     const void *fused = vec ? (const void *)pgd_l2_fused_kernel<true> : (const void *)pgd_l2_fused_kernel<false>;
     const size_t row_bytes = (size_t)B * T * sizeof(float);
     if (l2_single_pass() && C <= 64 && !overlaps(adv, out, row_bytes) && !overlaps(grad, out, row_bytes) &&
@@ -1314,14 +1166,14 @@ int advstep_pgd_l2_step_f32(const float *adv, const float *grad, const float *or
         // it serves rows whose exchange was abandoned, lowers their flags and advances the epoch (no memset node, nothing cleaned)
         const unsigned spins = l2_spin_limit();
         if (vec) {
-            hipLaunchKernelGGL(pgd_l2_fused_kernel<true>, dim3(C, (unsigned)B), dim3(kBlock), 0, st, adv, grad, orig, out, T, alpha,
+            hipLaunchKernelGGL(pgd_l2_fused_kernel<true>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, alpha,
                                eps, eps_div, lo, hi, w.gran0, w.gran1, w.fail, w.epoch, spins, gnorm, dnorm);
-            hipLaunchKernelGGL(pgd_l2_repair_kernel<true>, dim3((unsigned)B), dim3(kBlock), 0, st, adv, grad, orig, out, T, C, alpha,
+            hipLaunchKernelGGL(pgd_l2_repair_kernel<true>, dim3((unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, C, alpha,
                                eps, eps_div, lo, hi, w.fail, w.last, w.epoch, gnorm, dnorm);
         } else {
-            hipLaunchKernelGGL(pgd_l2_fused_kernel<false>, dim3(C, (unsigned)B), dim3(kBlock), 0, st, adv, grad, orig, out, T, alpha,
+            hipLaunchKernelGGL(pgd_l2_fused_kernel<false>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, alpha,
                                eps, eps_div, lo, hi, w.gran0, w.gran1, w.fail, w.epoch, spins, gnorm, dnorm);
-            hipLaunchKernelGGL(pgd_l2_repair_kernel<false>, dim3((unsigned)B), dim3(kBlock), 0, st, adv, grad, orig, out, T, C, alpha,
+            hipLaunchKernelGGL(pgd_l2_repair_kernel<false>, dim3((unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, C, alpha,
                                eps, eps_div, lo, hi, w.fail, w.last, w.epoch, gnorm, dnorm);
         }
         return status_after_launch();
@@ -1361,7 +1213,7 @@ int advstep_cw_tanh_sqdist_f32(const float *w, const float *x, float *adv, float
     if (!carve_ws(ws, ws_bytes, B, T, &wsp)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {w, x, adv});
-    const int C = tiles_per_row(T);
+    const int C = ws_tiles_per_row(T);
     ADV_LAUNCH_ROWS(cw_tanh_sqdist_kernel, vec, B, T, st, w + b0 * T, x + b0 * T, adv + b0 * T, T, wsp.p0 + b0 * C);
     hipLaunchKernelGGL(row_partials_sum_kernel, dim3((unsigned)B), dim3(64), 0, st, wsp.p0, C, l2);
     return status_after_launch();
@@ -1388,16 +1240,16 @@ int advstep_cw_adam_step_f32(float *w, float *m, float *v, const float *x, const
     if (n4 > 0) {
         const int64_t ntiles = ceil_div(n4, kTileVec);
         const int grid = (int)(ntiles < kMaxGrid ? ntiles : kMaxGrid);
-        hipLaunchKernelGGL(cw_adam_vec_kernel, dim3(grid), dim3(kBlock), 0, st, reinterpret_cast<float4 *>(w),
+        hipLaunchKernelGGL(cw_adam_vec_kernel, dim3(grid), dim3(kWgThreads), 0, st, reinterpret_cast<float4 *>(w),
                            reinterpret_cast<float4 *>(m), reinterpret_cast<float4 *>(v),
                            reinterpret_cast<const float4 *>(x), reinterpret_cast<const float4 *>(grad_adv), n4, ntiles,
                            s);
     }
     const int64_t begin = n4 * 4;
     if (begin < n) {
-        const int64_t blocks = ceil_div(n - begin, kBlock);
+        const int64_t blocks = ceil_div(n - begin, kWgThreads);
         const int grid = (int)(blocks < kMaxGrid ? blocks : kMaxGrid);
-        hipLaunchKernelGGL(cw_adam_scalar_kernel, dim3(grid), dim3(kBlock), 0, st, w, m, v, x, grad_adv, begin, n, s);
+        hipLaunchKernelGGL(cw_adam_scalar_kernel, dim3(grid), dim3(kWgThreads), 0, st, w, m, v, x, grad_adv, begin, n, s);
     }
     return status_after_launch();
 }
@@ -1417,7 +1269,7 @@ int advstep_ce2_loss_grad_f32(const float *z, const int64_t *labels, float *dz, 
                               advstep_stream_t stream) {
     ADVSTEP_REQUIRE(B >= 1);
     ADVSTEP_REQUIRE(z && labels && dz && loss);
-    hipLaunchKernelGGL(ce2_loss_grad_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), z, labels, dz, loss, B,
+    hipLaunchKernelGGL(ce2_loss_grad_kernel, dim3(1), dim3(kWgThreads), 0, as_stream(stream), z, labels, dz, loss, B,
                        scale);
     return status_after_launch();
 }

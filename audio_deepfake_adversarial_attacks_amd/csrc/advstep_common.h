@@ -33,7 +33,7 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
 
-// ---- the row workspace of include/advstep.h (ABI 3): advstep.hip and apgd.hip carve the same buffer --------------------------
+// ---- the row workspace of include/advstep.h (ABI 3): advstep.hip, apgd.hip and momentum.hip carve the same buffer ----------
 
 // One float partial per (row, 4096-sample tile): C = ceil(T / 4096) tiles per row.
 constexpr int64_t kWsRowTile = 4096;
@@ -80,37 +80,62 @@ inline bool carve_ws(void *ws, size_t ws_bytes, int64_t B, int64_t T, RowWs *out
 
 // ---- device side ------------------------------------------------------------------------------------------------------
 
-// torch.max(a, b) for tensors: NaN propagates.
+// ---- scalar semantics shared by all kernels (include/advstep.h): torch's, NaN included ------------------------------------
+
+// torch.max(a, b) / torch.min(a, b) for tensors: NaN propagates.
 __device__ __forceinline__ float max_nan(float a, float b) {
     if (a != a) return a;
     if (b != b) return b;
     return a > b ? a : b;
 }
-
-// Reductions over a 256-thread workgroup (4 wave64): xor shuffles, then one LDS slot per wave.  All threads receive the
-// result; `lds` holds >= 4 floats, and two calls in a row must use different slots (each ends on a barrier over its own).
-constexpr int kWgThreads = 256;
-__device__ __forceinline__ float wg_sum(float v, float *lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-__device__ __forceinline__ float wg_max_nan(float v, float *lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max_nan(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return max_nan(max_nan(max_nan(lds[0], lds[1]), lds[2]), lds[3]);
-}
-
-// torch.min(a, b) for tensors: NaN propagates.
 __device__ __forceinline__ float min_nan(float a, float b) {
     if (a != a) return a;
     if (b != b) return b;
     return a < b ? a : b;
 }
+
+// torch.sign: (0 < g) - (g < 0); NaN and +-0 give 0.
+__device__ __forceinline__ float sgn(float g) { return (float)(0.0f < g) - (float)(g < 0.0f); }
+
+// torch.clamp(v, lo, hi) = min(max(v, lo), hi), NaN in v propagates.
+__device__ __forceinline__ float clampf(float v, float lo, float hi) {
+    v = (v < lo) ? lo : v;
+    return (v > hi) ? hi : v;
+}
+
+// log(1 + exp(t)), stable: the 2-logit cross-entropy in closed form.
+__device__ __forceinline__ float softplusf(float t) { return (t > 0.0f ? t : 0.0f) + log1pf(expf(-fabsf(t))); }
+
+// ---- reductions: wave64 xor shuffles (offsets 32 -> 1), then over a 256-thread workgroup one LDS slot per wave, combined as
+// ((l0 . l1) . l2) . l3.  All threads receive the result; `lds` holds >= 4 floats, and two calls in a row must use different
+// slots (each ends on a barrier over its own).  Partials that separate kernels re-reduce must agree bit for bit: this is the
+// one body.
+constexpr int kWgThreads = 256;
+template <class Op>
+__device__ __forceinline__ float wave_reduce(float v, Op op) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    return v;
+}
+template <class Op>
+__device__ __forceinline__ float wg_reduce(float v, Op op, float *lds) {
+    v = wave_reduce(v, op);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return op(op(op(lds[0], lds[1]), lds[2]), lds[3]);
+}
+struct SumOp {
+    __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
+};
+struct MinNanOp {
+    __device__ __forceinline__ float operator()(float a, float b) const { return min_nan(a, b); }
+};
+struct MaxNanOp {
+    __device__ __forceinline__ float operator()(float a, float b) const { return max_nan(a, b); }
+};
+__device__ __forceinline__ float wg_sum(float v, float *lds) { return wg_reduce(v, SumOp(), lds); }
+__device__ __forceinline__ float wg_max_nan(float v, float *lds) { return wg_reduce(v, MaxNanOp(), lds); }
+__device__ __forceinline__ float wg_min_nan(float v, float *lds) { return wg_reduce(v, MinNanOp(), lds); }
 
 // ---- Philox4x32-10 (Salmon et al., SC'11), counter-based: the random starts of advstep.hip and apgd.hip draw from it ----
 

@@ -8,7 +8,6 @@
 // Built with -ffp-contract=off; divisions and sqrt are IEEE; min / max / clamp propagate NaN (see include/advstep.h).
 
 #include <hip/hip_runtime.h>
-#include <initializer_list>
 #include <math.h>
 #include <stdint.h>
 
@@ -21,23 +20,9 @@ namespace {
 constexpr int kNormLinf = 0, kNormL2 = 1;
 constexpr uint8_t kFooled = 1, kImproved = 2, kReset = 4;
 
-// ---- scalar semantics (include/advstep.h) -------------------------------------------------------------------------------
-
-__device__ __forceinline__ float sgn(float g) { return (float)(0.0f < g) - (float)(g < 0.0f); }
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {
-    v = (v < lo) ? lo : v;
-    return (v > hi) ? hi : v;
-}
 // torch.clamp(torch.min(torch.max(v, x - eps), x + eps), 0, 1)
 __device__ __forceinline__ float ball_box(float v, float x, float eps) {
     return clampf(min_nan(max_nan(v, x - eps), x + eps), 0.0f, 1.0f);
-}
-__device__ __forceinline__ float softplusf(float t) { return (t > 0.0f ? t : 0.0f) + log1pf(expf(-fabsf(t))); }
-
-__device__ __forceinline__ float row_max(const float *__restrict__ part, int C, float *lds) {
-    float v = part[0];
-    for (int i = threadIdx.x; i < C; i += kWgThreads) v = max_nan(v, part[i]);
-    return wg_max_nan(v, lds);
 }
 
 // ---- random start ------------------------------------------------------------------------------------------------------
@@ -71,7 +56,7 @@ __device__ __forceinline__ float4 start_t(const float *__restrict__ draw, int64_
     for (int k = 0; k < 4; ++k) {
         float &e = lane(d, k);
         if (norm == kNormLinf) e = 2.0f * e - 1.0f;
-        if (q * 4 + k >= T) e = 0.0f;
+        if (!in_row(T, q, k)) e = 0.0f;
     }
     return d;
 }
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(kWgThreads) void apgd_init_apply_kernel(const float
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
         const int64_t q = quad_of(tile, j);
-        if (q * 4 >= T) continue;
+        if (!in_row(T, q, 0)) continue;
         const float4 t = start_t<VEC, PHILOX>(draw, b, T, q, norm, seed, offset);
         float4 v = load4<VEC>(x + b * T, T, q, 0.0f);
         v.x = clampf(v.x + (scale * t.x) / m, lo, hi);
@@ -196,7 +181,7 @@ __global__ __launch_bounds__(kWgThreads) void apgd_track_kernel(float *x_adv, fl
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
         const int64_t q = quad_of(tile, j);
-        if (q * 4 >= T) continue;
+        if (!in_row(T, q, 0)) continue;
         if (f & (kFooled | kImproved)) {
             const float4 xa = load4<VEC>(x_adv + o, T, q, 0.0f);
             if (f & kFooled) store4<VEC>(x_best_adv + o, T, q, xa);
@@ -329,7 +314,7 @@ __global__ __launch_bounds__(kWgThreads) void apgd_l2_pass_kernel(const float *_
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (q * 4 + k >= T) lane(v, k) = 0.0f;  // out-of-row lanes must not leak a 0/0 into the sum
+                if (!in_row(T, q, k)) lane(v, k) = 0.0f;  // out-of-row lanes must not leak a 0/0 into the sum
             s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
         }
     }

@@ -22,12 +22,6 @@
 
 namespace {
 
-__device__ __forceinline__ float sgn(float g) { return (float)(0.0f < g) - (float)(g < 0.0f); }
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {
-    v = (v < lo) ? lo : v;
-    return (v > hi) ? hi : v;
-}
-
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // ---- the update ---------------------------------------------------------------------------------------------------------

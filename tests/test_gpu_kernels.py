@@ -225,6 +225,47 @@ def test_cw_vs_oracle(ops, cuda, B, T):
     assert same(host(db), K.cw_best_update(host(adv), mask, best))
 
 
+@pytest.mark.parametrize("T", [4, 5])
+def test_rows_beyond_one_grid_slab(ops, cuda, monkeypatch, T):
+    """B = 65 537: a launch holds 65 535 rows (grid.y), so every row kernel runs a second slab of two rows whose waveform,
+    per-row scalar and workspace pointers are offset by the slab's first row; T = 4 is float4-addressable, T = 5 is not.
+    Same comparisons with the oracle as the tests above."""
+    B = 65_537
+    x = randn((B, T), 300 + T, 0.05)
+    x01, mn, mx = ops.to_minmax(dev(x, cuda))
+    w01, wmn, wmx = K.minmax_normalize(x)
+    assert same(host(x01), w01) and same(host(mn).ravel(), wmn) and same(host(mx).ravel(), wmx)
+    p = rand01((B, T), 301 + T)
+    assert same(host(ops.revert_minmax(dev(p, cuda), mn, mx)), K.minmax_revert(p, wmn, wmx))
+
+    a = np.clip(p + randn((B, T), 302 + T, 1e-3), 0, 1).astype(np.float32)
+    g = randn((B, T), 303 + T, 1e-4)
+    want, wgn, wdn = K.pgd_l2_step(a, g, p, 0.2, 0.1)
+    for mode in ("0", None):
+        if mode is None:
+            monkeypatch.delenv("ADVSTEP_L2_SINGLE_PASS", raising=False)
+        else:
+            monkeypatch.setenv("ADVSTEP_L2_SINGLE_PASS", mode)
+        got, gn, dn = ops.pgd_l2_step(dev(a, cuda), dev(g, cuda), dev(p, cuda), 0.2, 0.1, return_norms=True)
+        np.testing.assert_allclose(host(gn), wgn, rtol=2e-6)
+        np.testing.assert_allclose(host(dn), wdn, rtol=2e-6)
+        np.testing.assert_allclose(host(got), want, atol=3e-7, rtol=0)
+    normal, r = randn((B, T), 304 + T), rand01((B,), 305 + T)
+    got = ops.pgd_l2_init(dev(p, cuda), 0.1, draws=(dev(normal, cuda), dev(r, cuda)))
+    np.testing.assert_allclose(host(got), K.pgd_l2_init_noise(p, normal, r, 0.1), atol=3e-7, rtol=0)
+
+    wv = randn((B, T), 306 + T, 2.0)
+    adv, l2 = ops.cw_tanh_sqdist(dev(wv, cuda), dev(p, cuda))
+    wadv, wl2 = K.cw_tanh_sqdist(wv, p)
+    np.testing.assert_allclose(host(adv), wadv, atol=2e-7, rtol=0)
+    np.testing.assert_allclose(host(l2), wl2, rtol=1e-5)
+    mask = (np.arange(B) % 2).astype(np.float32)
+    best = rand01((B, T), 307 + T)
+    db = dev(best, cuda)
+    ops.cw_best_update(adv, dev(mask, cuda), db)
+    assert same(host(db), K.cw_best_update(host(adv), mask, best))
+
+
 @pytest.mark.parametrize("B", [1, 2, 64, 128, 1000])
 def test_ce2_loss_grad_vs_oracle_and_torch(ops, cuda, B):
     z = randn((B, 1), 31 + B, 3.0)
