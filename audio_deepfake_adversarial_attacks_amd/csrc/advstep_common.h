@@ -3,7 +3,9 @@
 // Each .hip file is its own translation unit and includes this once, so every helper keeps internal linkage.  Some of
 // these are rules that separate kernels must agree on bit for bit: the max-feature-map / 2x2 pool selection written by
 // the forward kernels (lcnn_conv0.hip, lcnn_wino.hip, lcnn_mfm.hip) and read back by the backward ones (lcnn_mfm.hip),
-// and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).
+// and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The four attack files (advstep.hip,
+// apgd.hip, momentum.hip, fab.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the
+// host's rows_vec / overlaps; what depends on the 256-thread (tile, row) geometry is in row_tiles.h, which fab.hip does not use.
 
 #ifndef ADVSTEP_COMMON_H
 #define ADVSTEP_COMMON_H
@@ -11,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <initializer_list>
 
 #include "advstep.h"
 
@@ -32,6 +36,19 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline hipStream_t as_stream(advstep_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline int status_after_launch() { return hipGetLastError() == hipSuccess ? ADVSTEP_OK : ADVSTEP_ELAUNCH; }
+
+// Are rows of T samples float4-addressable from every (non-null) base?  The VEC choice of every row kernel, 256- or 1024-thread.
+inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
+    if (T % 4 != 0) return false;
+    for (const void *p : ptrs)
+        if (p && !aligned16(p)) return false;
+    return true;
+}
+
+inline bool overlaps(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bytes && y < x + bytes;
+}
 
 // ---- the row workspace of include/advstep.h (ABI 3): advstep.hip, apgd.hip and momentum.hip carve the same buffer ----------
 
@@ -109,7 +126,8 @@ __device__ __forceinline__ float softplusf(float t) { return (t > 0.0f ? t : 0.0
 // ---- reductions: wave64 xor shuffles (offsets 32 -> 1), then over a 256-thread workgroup one LDS slot per wave, combined as
 // ((l0 . l1) . l2) . l3.  All threads receive the result; `lds` holds >= 4 floats, and two calls in a row must use different
 // slots (each ends on a barrier over its own).  Partials that separate kernels re-reduce must agree bit for bit: this is the
-// one body.
+// one body.  (fab.hip's 1024-thread row_reduce is built on wave_reduce and states its own contract: 16 slots per value, several
+// values per barrier pair, a trailing barrier.)
 constexpr int kWgThreads = 256;
 template <class Op>
 __device__ __forceinline__ float wave_reduce(float v, Op op) {

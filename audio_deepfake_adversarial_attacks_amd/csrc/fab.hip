@@ -9,12 +9,18 @@
 // joined through LDS in a fixed order — deterministic, and every thread of the workgroup sees the same scalar, which
 // keeps the data-dependent iteration counts workgroup-uniform.
 //
+// From advstep_common.h: the NaN-propagating maximum, the reduction operators, the wave butterfly, rows_vec, kMaxGridY.
+// Private to this file, because no other file has 1024-thread rows: row_reduce, the row traversal and launch_rows.
+//
 // No sort: see include/advstep_fab.h.  Algorithmic bytes per row sample: hyperplane 8 B, projection 12 B (t, w in, d
 // out; the re-reads of the fixed-point iteration hit L2), combine 20 B, backward step 8-20 B.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
+#include <utility>
 
 #include "advstep_fab.h"
 #include "advstep_common.h"
@@ -26,24 +32,16 @@ constexpr int kRowWaves = kRow / 64;
 constexpr int kMaxNewton = 64;   // the iteration is finite (<= number of breakpoints); in practice 3-8 passes
 constexpr float kBig = 1e12f;
 
-struct Sum {
-    __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
-};
-struct MaxNan {  // torch.max semantics: NaN wins
-    __device__ __forceinline__ float operator()(float a, float b) const {
-        return (a != a) ? a : ((b != b) ? b : fmaxf(a, b));
-    }
-};
-
-// Reduce NV per-thread values over the workgroup; every thread receives the results.  lds: NV * kRowWaves floats.
+// Reduce NV per-thread values over the 1024-thread workgroup with advstep_common.h's wave_reduce, then one LDS slot per wave and
+// value, combined as ((w0 . w1) . w2) ... w15; every thread receives the results.  Against wg_reduce: 16 waves instead of 4, NV
+// values per barrier pair (lds: NV * kRowWaves floats), and a trailing barrier that frees the slots, so two calls in a row may
+// use the same ones.
 template <int NV, class Op>
 __device__ __forceinline__ void row_reduce(float (&v)[NV], Op op, float *lds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-        float x = v[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x = op(x, __shfl_xor(x, off, 64));
+        const float x = wave_reduce(v[k], op);
         if (lane == 0) lds[k * kRowWaves + wave] = x;
     }
     __syncthreads();
@@ -57,45 +55,53 @@ __device__ __forceinline__ void row_reduce(float (&v)[NV], Op op, float *lds) {
     __syncthreads();
 }
 
-// f(a_i, b_i) over a row pair; VEC: float4 loads.
-template <bool VEC, class F>
-__device__ __forceinline__ void visit2(const float *__restrict__ a, const float *__restrict__ b, int64_t T, F f) {
+// The one row traversal: f(a_i, b_i, ...) over the samples of the N rows `in`, or f(i, a_i, b_i, ...) where f takes the sample
+// index.  The index form is chosen iff f is callable with N + 1 arguments, so f must have a fixed arity (no generic lambda).
+// VEC: quads q = threadIdx.x, += kRow, lanes x, y, z, w in order, one float4 load per row; otherwise samples
+// i = threadIdx.x, += kRow.  That order is each thread's accumulation order, so part of every reduced result's bits.
+// STORE: out_i = f(...), one float4 store per quad after all of the quad's loads.  out may alias an input (no __restrict__).
+template <size_t>
+using Sample = float;
+
+template <bool VEC, bool STORE, class F, size_t... K>
+__device__ __forceinline__ void traverse(const float *const (&in)[sizeof...(K)], float *out, int64_t T, F f,
+                                         std::index_sequence<K...>) {
+    auto at = [&](int64_t i, Sample<K>... s) {
+        if constexpr (std::is_invocable_v<F, int64_t, Sample<K>...>) return f(i, s...);
+        else return f(s...);
+    };
     if constexpr (VEC) {
-        const float4 *a4 = reinterpret_cast<const float4 *>(a);
-        const float4 *b4 = reinterpret_cast<const float4 *>(b);
         const int64_t n4 = T >> 2;
         for (int64_t q = threadIdx.x; q < n4; q += kRow) {
-            const float4 x = a4[q], y = b4[q];
-            f(x.x, y.x);
-            f(x.y, y.y);
-            f(x.z, y.z);
-            f(x.w, y.w);
+            const float4 v[] = {reinterpret_cast<const float4 *>(in[K])[q]...};
+            if constexpr (STORE) {
+                float4 o;
+                o.x = at(4 * q, v[K].x...);
+                o.y = at(4 * q + 1, v[K].y...);
+                o.z = at(4 * q + 2, v[K].z...);
+                o.w = at(4 * q + 3, v[K].w...);
+                reinterpret_cast<float4 *>(out)[q] = o;
+            } else {
+                at(4 * q, v[K].x...);
+                at(4 * q + 1, v[K].y...);
+                at(4 * q + 2, v[K].z...);
+                at(4 * q + 3, v[K].w...);
+            }
         }
     } else {
-        for (int64_t i = threadIdx.x; i < T; i += kRow) f(a[i], b[i]);
+        for (int64_t i = threadIdx.x; i < T; i += kRow) {
+            if constexpr (STORE) out[i] = at(i, in[K][i]...);
+            else at(i, in[K][i]...);
+        }
     }
 }
-
-// out_i = f(a_i, b_i), same traversal.
-template <bool VEC, class F>
-__device__ __forceinline__ void map2(const float *a, const float *b, float *out, int64_t T, F f) {  // out may alias a / b
-    if constexpr (VEC) {
-        const float4 *a4 = reinterpret_cast<const float4 *>(a);
-        const float4 *b4 = reinterpret_cast<const float4 *>(b);
-        float4 *o4 = reinterpret_cast<float4 *>(out);
-        const int64_t n4 = T >> 2;
-        for (int64_t q = threadIdx.x; q < n4; q += kRow) {
-            const float4 x = a4[q], y = b4[q];
-            float4 o;
-            o.x = f(x.x, y.x);
-            o.y = f(x.y, y.y);
-            o.z = f(x.z, y.z);
-            o.w = f(x.w, y.w);
-            o4[q] = o;
-        }
-    } else {
-        for (int64_t i = threadIdx.x; i < T; i += kRow) out[i] = f(a[i], b[i]);
-    }
+template <bool VEC, size_t N, class F>
+__device__ __forceinline__ void visit_rows(const float *const (&in)[N], int64_t T, F f) {
+    traverse<VEC, false>(in, nullptr, T, f, std::make_index_sequence<N>());
+}
+template <bool VEC, size_t N, class F>
+__device__ __forceinline__ void map_rows(const float *const (&in)[N], float *out, int64_t T, F f) {
+    traverse<VEC, true>(in, out, T, f, std::make_index_sequence<N>());
 }
 
 __device__ __forceinline__ float dual_norm_finish(float v, int kind) { return kind == ADVSTEP_FAB_L2 ? sqrtf(v) : v; }
@@ -111,15 +117,17 @@ __global__ __launch_bounds__(kRow) void fab_hyperplane_kernel(const float *__res
         const float *g = gz + row * T, *xr = x + row * T;
         float dot[1] = {0.0f}, nrm[1] = {0.0f};
         if (kind == ADVSTEP_FAB_LINF) {
-            visit2<VEC>(g, xr, T, [&](float gi, float xi) { dot[0] += gi * xi; nrm[0] += fabsf(gi); });
+            visit_rows<VEC>({g, xr}, T, [&](float gi, float xi) { dot[0] += gi * xi; nrm[0] += fabsf(gi); });
         } else if (kind == ADVSTEP_FAB_L2) {
-            visit2<VEC>(g, xr, T, [&](float gi, float xi) { dot[0] += gi * xi; nrm[0] += gi * gi; });
+            visit_rows<VEC>({g, xr}, T, [&](float gi, float xi) { dot[0] += gi * xi; nrm[0] += gi * gi; });
         } else {
-            visit2<VEC>(g, xr, T, [&](float gi, float xi) { dot[0] += gi * xi; nrm[0] = MaxNan()(nrm[0], fabsf(gi)); });
+            // max_nan selects by a > b; torch.max's fmaxf differs from it only in which zero wins a (+0, -0) tie, and every
+            // use in this file folds fabsf values into a 0.0f start, so no -0 occurs
+            visit_rows<VEC>({g, xr}, T, [&](float gi, float xi) { dot[0] += gi * xi; nrm[0] = max_nan(nrm[0], fabsf(gi)); });
         }
-        row_reduce<1>(dot, Sum(), lds);
-        if (kind == ADVSTEP_FAB_L1) row_reduce<1>(nrm, MaxNan(), lds + kRowWaves);
-        else row_reduce<1>(nrm, Sum(), lds + kRowWaves);
+        row_reduce<1>(dot, SumOp(), lds);
+        if (kind == ADVSTEP_FAB_L1) row_reduce<1>(nrm, MaxNanOp(), lds + kRowWaves);
+        else row_reduce<1>(nrm, SumOp(), lds + kRowWaves);
         if (threadIdx.x == 0) {
             const float n = dual_norm_finish(nrm[0], kind);
             if (gnorm) gnorm[row] = n;
@@ -181,7 +189,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_linf_kernel(const float *
         const float sc = wscale ? wscale[row % w_rows] : 1.0f;
         // pass 1: w.t, sum|w|, and sum|w| * room for both orientations of the hyperplane, count of w != 0
         float acc[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        visit2<VEC>(tr, wr, T, [&](float ti, float wraw) {
+        visit_rows<VEC>({tr, wr}, T, [&](float ti, float wraw) {
             const float wi = sc * wraw, aw = fabsf(wi);
             acc[0] += wi * ti;
             acc[1] += aw;
@@ -189,7 +197,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_linf_kernel(const float *
             acc[3] += aw * (wi > 0.0f ? 1.0f - ti : ti);
             acc[4] += (wi != 0.0f) ? 1.0f : 0.0f;
         });
-        row_reduce<5>(acc, Sum(), lds);
+        row_reduce<5>(acc, SumOp(), lds);
         const float c = acc[0] - b[row];
         const bool keep = c >= 0.0f;                  // fab.py:566: sign = 2 * ((w*t).sum(1) - b >= 0) - 1
         const float beta = fabsf(c);                  // -(b*sign - (w*sign * t).sum(1))
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_linf_kernel(const float *
         if (reach - beta > 0.0f) {                    // fab.py:588  b - b0 > 0
             lam = waterfill(beta, acc[1], acc[4], [&](float cur, float &A, float &S, float &cnt) {
                 float v[3] = {0.0f, 0.0f, 0.0f};
-                visit2<VEC>(tr, wr, T, [&](float ti, float wraw) {
+                visit_rows<VEC>({tr, wr}, T, [&](float ti, float wraw) {
                     const float wi = sc * wraw, aw = fabsf(wi);
                     const bool up = keep ? wi < 0.0f : wi > 0.0f;
                     const float p = up ? 1.0f - ti : ti;
@@ -207,7 +215,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_linf_kernel(const float *
                     v[1] += active ? aw : 0.0f;
                     v[2] += (active && wi != 0.0f) ? 1.0f : 0.0f;
                 });
-                row_reduce<3>(v, Sum(), lds);
+                row_reduce<3>(v, SumOp(), lds);
                 A = v[0];
                 S = v[1];
                 cnt = v[2];
@@ -215,17 +223,17 @@ __global__ __launch_bounds__(kRow) void fab_projection_linf_kernel(const float *
             lam = fmaxf(lam, 0.0f);                   // clamp_min(lmbd_opt, 0)
         }
         float mx[1] = {0.0f};
-        map2<VEC>(tr, wr, d + row * T, T, [&](float ti, float wraw) {
+        map_rows<VEC>({tr, wr}, d + row * T, T, [&](float ti, float wraw) {
             const float wi = sc * wraw;
             const bool up = keep ? wi < 0.0f : wi > 0.0f;
             const float p = up ? 1.0f - ti : ti;
             const float m = fminf(lam, p);            // lam is never NaN here; p NaN propagates below
             float di = (p != p) ? p : (up ? m : -m);
             if (wi == 0.0f) di = 0.0f;
-            mx[0] = MaxNan()(mx[0], fabsf(di));
+            mx[0] = max_nan(mx[0], fabsf(di));
             return di;
         });
-        row_reduce<1>(mx, MaxNan(), lds);
+        row_reduce<1>(mx, MaxNanOp(), lds);
         if (threadIdx.x == 0 && dnorm) dnorm[row] = mx[0];
     }
 }
@@ -252,7 +260,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l2_kernel(const float *__
         const float sc = wscale ? wscale[row % w_rows] : 1.0f;
         // pass 1: w.t, sum w^2, and sum (r w) w over the movable coordinates for both orientations
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        visit2<VEC>(tr, wr, T, [&](float ti, float wraw) {
+        visit_rows<VEC>({tr, wr}, T, [&](float ti, float wraw) {
             const float wi = sc * wraw;
             acc[0] += wi * ti;
             acc[1] += wi * wi;
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l2_kernel(const float *__
                 acc[3] += (l2_ratio(ti, -wi) * wi) * wi;
             }
         });
-        row_reduce<4>(acc, Sum(), lds);
+        row_reduce<4>(acc, SumOp(), lds);
         const float c0 = acc[0] - b[row];
         const float sg = c0 >= 0.0f ? 1.0f : -1.0f;
         const float c = fabsf(c0);
@@ -270,7 +278,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l2_kernel(const float *__
         if (!(c - reach > 0.0f)) {                   // fab.py:642  c3 = (d*w).sum + c > 0  -> every coordinate to its face
             alpha = waterfill(c, acc[1], (float)T, [&](float cur, float &A, float &S, float &cnt) {
                 float v[3] = {0.0f, 0.0f, 0.0f};
-                visit2<VEC>(tr, wr, T, [&](float ti, float wraw) {
+                visit_rows<VEC>({tr, wr}, T, [&](float ti, float wraw) {
                     const float wi = sg * (sc * wraw);
                     const float r = l2_ratio(ti, wi), w2 = wi * wi;
                     const bool active = r > cur;
@@ -278,14 +286,14 @@ __global__ __launch_bounds__(kRow) void fab_projection_l2_kernel(const float *__
                     v[1] += active ? w2 : 0.0f;
                     v[2] += active ? 1.0f : 0.0f;
                 });
-                row_reduce<3>(v, Sum(), lds);
+                row_reduce<3>(v, SumOp(), lds);
                 A = v[0];
                 S = v[1];
                 cnt = v[2];
             });
         }
         float ss[1] = {0.0f};
-        map2<VEC>(tr, wr, d + row * T, T, [&](float ti, float wraw) {
+        map_rows<VEC>({tr, wr}, d + row * T, T, [&](float ti, float wraw) {
             const float wi = sg * (sc * wraw);
             const float r = l2_ratio(ti, wi);
             float di = (alpha > r) ? -(r * wi) : -(alpha * wi);   // fab.py:666-667
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l2_kernel(const float *__
             ss[0] += di * di;
             return di;
         });
-        row_reduce<1>(ss, Sum(), lds);
+        row_reduce<1>(ss, SumOp(), lds);
         if (threadIdx.x == 0 && dnorm) dnorm[row] = sqrtf(ss[0]);
     }
 }
@@ -328,14 +336,14 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
         const float sc = wscale ? wscale[row % w_rows] : 1.0f;
         // pass 1: w.t, total gain for either orientation; keys into the output row
         float acc[3] = {0.0f, 0.0f, 0.0f};
-        map2<VEC>(tr, wr, dr, T, [&](float ti, float wraw) {
+        map_rows<VEC>({tr, wr}, dr, T, [&](float ti, float wraw) {
             const float wi = sc * wraw;
             acc[0] += wi * ti;
             acc[1] += l1_gain(ti, wi);
             acc[2] += l1_gain(ti, -wi);
             return l1_ratio(wi);
         });
-        row_reduce<3>(acc, Sum(), lds);
+        row_reduce<3>(acc, SumOp(), lds);
         const float c0 = acc[0] - b[row];
         const float sg = c0 >= 0.0f ? 1.0f : -1.0f;
         const float c = fabsf(c0);
@@ -343,7 +351,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
         float sum_abs[1] = {0.0f};
         if (!(total < 0.0f)) {
             // the farthest corner does not reach the hyperplane: every coordinate to its face (fab.py:686)
-            map2<VEC>(tr, wr, dr, T, [&](float ti, float wraw) {
+            map_rows<VEC>({tr, wr}, dr, T, [&](float ti, float wraw) {
                 const float wi = sg * (sc * wraw);
                 float di = l1_face(ti, wi);
                 if (!(fabsf(wi) > 1e-8f)) di = 0.0f;
@@ -361,7 +369,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
                     float h[kBuckets];
 #pragma unroll
                     for (int q = 0; q < kBuckets; ++q) h[q] = 0.0f;
-                    auto tally = [&](float ti, float wraw, float ri) {
+                    visit_rows<VEC>({tr, wr, dr}, T, [&](float ti, float wraw, float ri) {
                         const uint32_t key = __float_as_uint(ri);
                         if (key >= rho) {
                             const uint32_t q = (key - rho) >> shift;   // contributes to every candidate j > q
@@ -369,22 +377,8 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
 #pragma unroll
                             for (int k = 0; k < kBuckets; ++k) h[k] += (q == (uint32_t)k) ? gn : 0.0f;
                         }
-                    };
-                    if constexpr (VEC) {
-                        const int64_t n4 = T >> 2;
-                        for (int64_t q4 = threadIdx.x; q4 < n4; q4 += kRow) {
-                            const float4 a = reinterpret_cast<const float4 *>(tr)[q4];
-                            const float4 e = reinterpret_cast<const float4 *>(wr)[q4];
-                            const float4 r = reinterpret_cast<const float4 *>(dr)[q4];
-                            tally(a.x, e.x, r.x);
-                            tally(a.y, e.y, r.y);
-                            tally(a.z, e.z, r.z);
-                            tally(a.w, e.w, r.w);
-                        }
-                    } else {
-                        for (int64_t i = threadIdx.x; i < T; i += kRow) tally(tr[i], wr[i], dr[i]);
-                    }
-                    row_reduce<kBuckets>(h, Sum(), lds);
+                    });
+                    row_reduce<kBuckets>(h, SumOp(), lds);
                     float run = before;
                     uint32_t pick = 0;
                     for (uint32_t j = 1; j <= limit; ++j) {            // residual before candidate j = before + h[0..j)
@@ -405,7 +399,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
             float ties[1] = {0.0f};
             float tie_t = 0.0f, tie_w = 0.0f;
             int64_t tie_i = -1;
-            auto settle = [&](int64_t i, float ti, float wraw, float ri) {
+            map_rows<VEC>({tr, wr, dr}, dr, T, [&](int64_t i, float ti, float wraw, float ri) {
                 const float wi = sg * (sc * wraw);
                 const uint32_t key = __float_as_uint(ri);
                 float di = 0.0f;
@@ -419,24 +413,8 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
                 if (!(fabsf(wi) > 1e-8f)) di = 0.0f;
                 sum_abs[0] += fabsf(di);
                 return di;
-            };
-            if constexpr (VEC) {
-                const int64_t n4 = T >> 2;
-                for (int64_t q4 = threadIdx.x; q4 < n4; q4 += kRow) {
-                    const float4 a = reinterpret_cast<const float4 *>(tr)[q4];
-                    const float4 e = reinterpret_cast<const float4 *>(wr)[q4];
-                    const float4 r = reinterpret_cast<const float4 *>(dr)[q4];
-                    float4 o;
-                    o.x = settle(4 * q4, a.x, e.x, r.x);
-                    o.y = settle(4 * q4 + 1, a.y, e.y, r.y);
-                    o.z = settle(4 * q4 + 2, a.z, e.z, r.z);
-                    o.w = settle(4 * q4 + 3, a.w, e.w, r.w);
-                    reinterpret_cast<float4 *>(dr)[q4] = o;
-                }
-            } else {
-                for (int64_t i = threadIdx.x; i < T; i += kRow) dr[i] = settle(i, tr[i], wr[i], dr[i]);
-            }
-            row_reduce<1>(ties, Sum(), lds);
+            });
+            row_reduce<1>(ties, SumOp(), lds);
             if (ties[0] == 1.0f) {
                 // the usual case: the tie group is one coordinate, the one that would overshoot (fab.py:711,715)
                 if (tie_i >= 0) {
@@ -481,7 +459,7 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
                 }
             }
         }
-        row_reduce<1>(sum_abs, Sum(), lds);
+        row_reduce<1>(sum_abs, SumOp(), lds);
         if (threadIdx.x == 0 && dnorm) dnorm[row] = sum_abs[0];
         __syncthreads();
     }
@@ -498,27 +476,11 @@ __global__ __launch_bounds__(kRow) void fab_combine_kernel(const float *__restri
         float alpha = a1 / (a1 + a2);
         alpha = (alpha != alpha) ? alpha : fminf(fmaxf(alpha, 0.0f), alpha_max);
         const float keep = 1.0f - alpha;
-        auto f = [&](float p1, float p0, float m1, float m2) {
-            const float v = (p1 + eta * m1) * keep + (p0 + m2 * eta) * alpha;
-            return (v != v) ? v : fminf(fmaxf(v, 0.0f), 1.0f);
-        };
-        const float *p1 = x1 + row * T, *p0 = x0 + row * T, *m1 = d1 + row * T, *m2 = d2 + row * T;
-        float *o = out + row * T;
-        if constexpr (VEC) {
-            const int64_t n4 = T >> 2;
-            for (int64_t q = threadIdx.x; q < n4; q += kRow) {
-                const float4 a = reinterpret_cast<const float4 *>(p1)[q], c = reinterpret_cast<const float4 *>(p0)[q];
-                const float4 e = reinterpret_cast<const float4 *>(m1)[q], g = reinterpret_cast<const float4 *>(m2)[q];
-                float4 r;
-                r.x = f(a.x, c.x, e.x, g.x);
-                r.y = f(a.y, c.y, e.y, g.y);
-                r.z = f(a.z, c.z, e.z, g.z);
-                r.w = f(a.w, c.w, e.w, g.w);
-                reinterpret_cast<float4 *>(o)[q] = r;
-            }
-        } else {
-            for (int64_t i = threadIdx.x; i < T; i += kRow) o[i] = f(p1[i], p0[i], m1[i], m2[i]);
-        }
+        map_rows<VEC>({x1 + row * T, x0 + row * T, d1 + row * T, d2 + row * T}, out + row * T, T,
+                      [&](float p1, float p0, float m1, float m2) {
+                          const float v = (p1 + eta * m1) * keep + (p0 + m2 * eta) * alpha;
+                          return (v != v) ? v : fminf(fmaxf(v, 0.0f), 1.0f);
+                      });
     }
 }
 
@@ -535,29 +497,38 @@ __global__ __launch_bounds__(kRow) void fab_backward_step_kernel(float *x1, cons
         float *pa = adv + row * T;
         float v[1] = {0.0f};
         if (kind == ADVSTEP_FAB_LINF) {
-            visit2<VEC>(p1, p0, T, [&](float a, float c) { v[0] = MaxNan()(v[0], fabsf(a - c)); });
-            row_reduce<1>(v, MaxNan(), lds);
+            visit_rows<VEC>({p1, p0}, T, [&](float a, float c) { v[0] = max_nan(v[0], fabsf(a - c)); });
+            row_reduce<1>(v, MaxNanOp(), lds);
         } else if (kind == ADVSTEP_FAB_L2) {
-            visit2<VEC>(p1, p0, T, [&](float a, float c) { v[0] += (a - c) * (a - c); });
-            row_reduce<1>(v, Sum(), lds);
+            visit_rows<VEC>({p1, p0}, T, [&](float a, float c) { v[0] += (a - c) * (a - c); });
+            row_reduce<1>(v, SumOp(), lds);
             v[0] = sqrtf(v[0]);
         } else {
-            visit2<VEC>(p1, p0, T, [&](float a, float c) { v[0] += fabsf(a - c); });
-            row_reduce<1>(v, Sum(), lds);
+            visit_rows<VEC>({p1, p0}, T, [&](float a, float c) { v[0] += fabsf(a - c); });
+            row_reduce<1>(v, SumOp(), lds);
         }
         const float tn = v[0], best = res2[row];
         const bool better = tn < best, worse = tn >= best;   // both false for a NaN norm: the reference's masks zero adv
         if (!worse) {
-            if (better) map2<VEC>(p1, p0, pa, T, [&](float a, float) { return a; });
-            else map2<VEC>(p1, pa, pa, T, [&](float a, float o) { return a * 0.0f + o * 0.0f; });
+            if (better) map_rows<VEC>({p1, p0}, pa, T, [&](float a, float) { return a; });
+            else map_rows<VEC>({p1, pa}, pa, T, [&](float a, float o) { return a * 0.0f + o * 0.0f; });
         }
-        map2<VEC>(p1, p0, p1, T, [&](float a, float c) { return c + (a - c) * beta; });
+        map_rows<VEC>({p1, p0}, p1, T, [&](float a, float c) { return c + (a - c) * beta; });
         __syncthreads();
         if (threadIdx.x == 0) res2[row] = better ? tn : (worse ? best : tn * 0.0f + best * 0.0f);
     }
 }
 
-inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < 65535 ? rows : 65535); }
+inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }
+
+// One kRow-thread workgroup per row (the kernels stride on past kMaxGridY rows): k[1] where the rows are float4-addressable.
+// FAB_KERNEL_PAIR is the only place that writes the pair, so its order is fixed once.
+#define FAB_KERNEL_PAIR(KERNEL) {KERNEL<false>, KERNEL<true>}
+template <class... P, class... A>
+int launch_rows(void (*const (&k)[2])(P...), bool vec, int64_t rows, advstep_stream_t stream, A... args) {
+    hipLaunchKernelGGL(k[vec], dim3(grid_rows(rows)), dim3(kRow), 0, as_stream(stream), args...);
+    return status_after_launch();
+}
 
 }  // namespace
 
@@ -569,14 +540,8 @@ int advstep_fab_hyperplane_f32(const float *gz, const float *x, const float *z, 
     ADVSTEP_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (B == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(gz && x && ((z == nullptr) == (labels == nullptr)) && (!z || (wscale && b)));
-    const bool vec = (T % 4 == 0) && aligned16(gz) && aligned16(x);
-    if (vec)
-        hipLaunchKernelGGL(fab_hyperplane_kernel<true>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), gz, x, z, labels,
-                           wscale, b, gnorm, gdot, B, T, norm_kind);
-    else
-        hipLaunchKernelGGL(fab_hyperplane_kernel<false>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), gz, x, z,
-                           labels, wscale, b, gnorm, gdot, B, T, norm_kind);
-    return status_after_launch();
+    return launch_rows(FAB_KERNEL_PAIR(fab_hyperplane_kernel), rows_vec(T, {gz, x}), B, stream, gz, x, z,
+                       labels, wscale, b, gnorm, gdot, B, T, norm_kind);
 }
 
 int advstep_fab_projection_f32(const float *t, const float *w, const float *wscale, const float *b, float *d,
@@ -585,20 +550,11 @@ int advstep_fab_projection_f32(const float *t, const float *w, const float *wsca
     ADVSTEP_REQUIRE(R >= 0 && T >= 0 && w_rows >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (R == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(t && w && b && d && d != t && d != w && w_rows >= 1 && T >= 1 && T < (int64_t(1) << 24));
-    const bool vec = (T % 4 == 0) && aligned16(t) && aligned16(w) && aligned16(d);
-    const dim3 grid(grid_rows(R)), block(kRow);
-    hipStream_t st = as_stream(stream);
-    if (norm_kind == ADVSTEP_FAB_LINF) {
-        if (vec) hipLaunchKernelGGL(fab_projection_linf_kernel<true>, grid, block, 0, st, t, w, wscale, b, d, dnorm, R, w_rows, T);
-        else hipLaunchKernelGGL(fab_projection_linf_kernel<false>, grid, block, 0, st, t, w, wscale, b, d, dnorm, R, w_rows, T);
-    } else if (norm_kind == ADVSTEP_FAB_L2) {
-        if (vec) hipLaunchKernelGGL(fab_projection_l2_kernel<true>, grid, block, 0, st, t, w, wscale, b, d, dnorm, R, w_rows, T);
-        else hipLaunchKernelGGL(fab_projection_l2_kernel<false>, grid, block, 0, st, t, w, wscale, b, d, dnorm, R, w_rows, T);
-    } else {
-        if (vec) hipLaunchKernelGGL(fab_projection_l1_kernel<true>, grid, block, 0, st, t, w, wscale, b, d, dnorm, R, w_rows, T);
-        else hipLaunchKernelGGL(fab_projection_l1_kernel<false>, grid, block, 0, st, t, w, wscale, b, d, dnorm, R, w_rows, T);
-    }
-    return status_after_launch();
+    static_assert(ADVSTEP_FAB_LINF == 0 && ADVSTEP_FAB_L2 == 1 && ADVSTEP_FAB_L1 == 2, "the table's row order");
+    static constexpr decltype(&fab_projection_linf_kernel<true>) kernels[3][2] = {   // [norm_kind][vec]
+        FAB_KERNEL_PAIR(fab_projection_linf_kernel), FAB_KERNEL_PAIR(fab_projection_l2_kernel),
+        FAB_KERNEL_PAIR(fab_projection_l1_kernel)};
+    return launch_rows(kernels[norm_kind], rows_vec(T, {t, w, d}), R, stream, t, w, wscale, b, d, dnorm, R, w_rows, T);
 }
 
 int advstep_fab_combine_f32(const float *x1, const float *x0, const float *d1, const float *d2, const float *n1,
@@ -607,14 +563,8 @@ int advstep_fab_combine_f32(const float *x1, const float *x0, const float *d1, c
     ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x1 && x0 && d1 && d2 && n1 && n2 && out);
-    const bool vec = (T % 4 == 0) && aligned16(x1) && aligned16(x0) && aligned16(d1) && aligned16(d2) && aligned16(out);
-    if (vec)
-        hipLaunchKernelGGL(fab_combine_kernel<true>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), x1, x0, d1, d2, n1,
-                           n2, out, B, T, eta, alpha_max);
-    else
-        hipLaunchKernelGGL(fab_combine_kernel<false>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), x1, x0, d1, d2, n1,
-                           n2, out, B, T, eta, alpha_max);
-    return status_after_launch();
+    return launch_rows(FAB_KERNEL_PAIR(fab_combine_kernel), rows_vec(T, {x1, x0, d1, d2, out}), B, stream, x1,
+                       x0, d1, d2, n1, n2, out, B, T, eta, alpha_max);
 }
 
 int advstep_fab_backward_step_f32(float *x1, const float *x0, float *adv, float *res2, const uint8_t *is_adv, int64_t B,
@@ -622,14 +572,8 @@ int advstep_fab_backward_step_f32(float *x1, const float *x0, float *adv, float 
     ADVSTEP_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (B == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x1 && x0 && adv && res2 && is_adv);
-    const bool vec = (T % 4 == 0) && aligned16(x1) && aligned16(x0) && aligned16(adv);
-    if (vec)
-        hipLaunchKernelGGL(fab_backward_step_kernel<true>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), x1, x0, adv,
-                           res2, is_adv, B, T, beta, norm_kind);
-    else
-        hipLaunchKernelGGL(fab_backward_step_kernel<false>, dim3(grid_rows(B)), dim3(kRow), 0, as_stream(stream), x1, x0, adv,
-                           res2, is_adv, B, T, beta, norm_kind);
-    return status_after_launch();
+    return launch_rows(FAB_KERNEL_PAIR(fab_backward_step_kernel), rows_vec(T, {x1, x0, adv}), B, stream,
+                       x1, x0, adv, res2, is_adv, B, T, beta, norm_kind);
 }
 
 }  // extern "C"

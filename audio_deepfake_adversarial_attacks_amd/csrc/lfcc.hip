@@ -15,8 +15,7 @@ constexpr int kBlock = 256;
 constexpr int kFrames = 64;   // frames per projection tile (one wave per coefficient chunk)
 
 __device__ __forceinline__ float block_max(float v, float *lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max_nan(v, __shfl_xor(v, off, 64));
+    v = wave_reduce(v, MaxNanOp());
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
     __syncthreads();
     float r = lds[0];

@@ -316,8 +316,7 @@ __global__ __launch_bounds__(kThreads) void stft_bands_kernel(const float *__res
         }
         wave_lds_sync();                          // xs / a are rewritten by the next frame
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) vmax = max_nan(vmax, __shfl_xor(vmax, off, 64));
+    vmax = wave_reduce(vmax, MaxNanOp());
     if (lane == 0) L.red[wave] = vmax;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -685,8 +684,7 @@ __global__ __launch_bounds__(kThreads) void stft_bands_reg_kernel(const float *_
         }
         lds_wave_fence();                                      // pw is rewritten by the next group's exchange
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) vmax = max_nan(vmax, __shfl_xor(vmax, off, 64));
+    vmax = wave_reduce(vmax, MaxNanOp());
     if (lane == 0) S.red[wave] = vmax;
     __syncthreads();
     if (threadIdx.x == 0) {

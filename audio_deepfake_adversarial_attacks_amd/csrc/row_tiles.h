@@ -1,5 +1,6 @@
 // row_tiles.h — the (tile, row) addressing of every row kernel (advstep.hip, apgd.hip, momentum.hip) and the re-reduction of a
-// row's per-tile partials (internal, like advstep_common.h).
+// row's per-tile partials (internal, like advstep_common.h, which has the rules that do not depend on this 256-thread tile:
+// scalar semantics, reductions, rows_vec, overlaps).
 //
 // grid = (C tiles of 4096 samples, B rows), 256 threads, 4 float4 per thread and stream; float4 q of a row is loaded whole when
 // the rows are float4-addressable (VEC) and sample by sample otherwise (T % 4 != 0 leaves rows 2 .. B unaligned).  Tile c of
@@ -7,8 +8,6 @@
 
 #ifndef ADVSTEP_ROW_TILES_H
 #define ADVSTEP_ROW_TILES_H
-
-#include <initializer_list>
 
 #include "advstep_common.h"
 
@@ -93,18 +92,6 @@ __device__ __forceinline__ float row_min(const float *__restrict__ part, int C, 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-
-inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
-    if (T % 4 != 0) return false;
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    return true;
-}
-
-inline bool overlaps(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bytes && y < x + bytes;
-}
 
 inline dim3 row_grid(int64_t B, int64_t T) { return dim3((unsigned)ws_tiles_per_row(T), (unsigned)B); }
 

@@ -236,3 +236,53 @@ def test_fab_on_lcnn_invariants(cuda, norm, eps):
         moved = bool((adv[r] != x01[r]).any())
         # a row is changed only if the change fools the detector within eps (fab.py:515-526)
         assert (not moved) or (now[r] != y[r] and size[r] <= eps * (1 + 1e-5)), (r, size[r].item())
+
+
+@pytest.mark.parametrize("T", [4, 5])
+def test_rows_beyond_one_grid(cuda, ops, T):
+    """65 537 rows: the grid holds 65 535 workgroups, so the last two rows are the second trip of each kernel's
+    `row += gridDim.x` loop.  T = 4 is the float4 path, T = 5 the scalar one."""
+    R = 65537
+    ends = [0, 1, R - 3, R - 2, R - 1]
+    gen = torch.Generator().manual_seed(11 + T)
+    t = torch.rand(R, T, generator=gen)                 # fab_projection_inputs' rows, one offset per row in turn
+    t[:, ::7] = 0.0
+    t[:, 3::11] = 1.0
+    w = torch.randn(R, T, generator=gen) * 0.01
+    w[:, ::13] = 0.0
+    b = (w * t).sum(1) + torch.tensor([1e-4, -1e-3, 0.05, -0.2, 0.45, 5.0])[torch.arange(R) % 6] * w.abs().sum(1)
+    for norm in NORMS:
+        out = torch.full((R, T), float("nan"), device=cuda)
+        d, dn = ops.fab_projection(t.to(cuda), w.to(cuda), b.to(cuda), norm, out=out)
+        d, dn = d.cpu().numpy(), dn.cpu().numpy()
+        assert not np.isnan(d).any(), (norm, np.flatnonzero(np.isnan(d).any(1)))
+        want = OF.PROJECTIONS[norm](t[ends].numpy(), w[ends].numpy(), b[ends].numpy())
+        assert np.abs(d[ends] - want).max() <= TOL[norm], (norm, np.abs(d[ends] - want).max(1))
+        assert np.allclose(dn[ends], _norm_of(want, norm), rtol=1e-4, atol=TOL[norm])
+        # every row's norm is that of the row beside it: at most T float32 additions, or an exact maximum
+        assert np.allclose(dn, _norm_of(d, norm), rtol=1e-5, atol=0), norm
+
+    x1, x0 = torch.rand(R, T, generator=gen), torch.rand(R, T, generator=gen)
+    d1, d2 = torch.randn(R, T, generator=gen) * 0.1, torch.randn(R, T, generator=gen) * 0.1
+    n1, n2 = torch.rand(R, generator=gen), torch.rand(R, generator=gen)
+    n1[::5] = 0.0
+    out = torch.full((R, T), float("nan"), device=cuda)
+    got = ops.fab_combine(*(v.to(cuda) for v in (x1, x0, d1, d2, n1, n2)), 1.05, 0.1, out=out).cpu()
+    assert not torch.isnan(got).any()
+    assert torch.equal(got, O.fab_combine(x1, x0, d1, d2, n1, n2, 1.05, 0.1))
+
+    x1 = (x0 + torch.randn(R, T, generator=gen) * 0.01).clamp(0, 1)
+    adv = torch.rand(R, T, generator=gen)
+    flags = torch.tensor([1, 1, 1, 0, 0, 1], dtype=torch.uint8)[torch.arange(R) % 6]
+    flags[R - 2:] = 1                                   # the rows of the second trip do work
+    for norm in NORMS:
+        big = float(OF.row_norm(x1 - x0, norm).max()) * 2
+        res2 = torch.tensor([1e10, 1e-6, big, 1e10, 1e-6, big])[torch.arange(R) % 6]
+        c1, ca, cr = x1.clone(), adv.clone(), res2.clone()
+        O.fab_backward_step(c1, x0, ca, cr, flags, 0.9, norm)
+        g1, ga, gr = x1.to(cuda), adv.to(cuda), res2.to(cuda)
+        ops.fab_backward_step(g1, x0.to(cuda), ga, gr, flags.to(cuda).bool(), 0.9, norm)
+        assert torch.equal(g1.cpu(), c1) and torch.equal(ga.cpu(), ca), norm
+        assert torch.allclose(gr.cpu(), cr, rtol=1e-5), norm
+        # row R - 2 (best so far 1e10) is kept as the new best and steps back, row R - 1 (1e-6) only steps back
+        assert (g1.cpu()[R - 2:] != x1[R - 2:]).any(1).all() and torch.equal(ga.cpu()[R - 2], x1[R - 2])
