@@ -8,6 +8,14 @@ from enum import Enum
 from .. import torchattacks
 
 
+def _worst_case_linf(eps, steps=10, apgd_steps=None):
+    """The members of a WORSTCASE* entry within one L-inf radius, cheapest first, with the hyper-parameters of the single-attack
+    members of the same radius below (alpha = eps / steps for MI-FGSM)."""
+    return {"members": [("PGD", {"eps": eps, "steps": steps}),
+                        ("MIFGSM", {"eps": eps, "alpha": eps / steps, "steps": steps, "decay": 1.0}),
+                        ("APGD", {"norm": "Linf", "eps": eps, "steps": apgd_steps or steps})]}
+
+
 class AttackEnum(Enum):
 
     # --- reference members (aa_types.py:8-22) ---
@@ -57,5 +65,16 @@ class AttackEnum(Enum):
     VNIFGSM = (torchattacks.VNIFGSM, {"eps": 0.0005, "alpha": 0.0005 / 10, "steps": 10, "decay": 1.0, "N": 20, "beta": 1.5})
 
     MIFGSM40_eps003 = (torchattacks.MIFGSM, {"eps": 0.003, "alpha": 0.003 / 40, "steps": 40, "decay": 1.0})  # PGD40_eps003's radius
+
+    # --- additive members: the worst case over the attacks of one threat model (torchattacks.MultiAttack: each member only on
+    # the utterances the previous ones failed to flip).  The value's callable builds the members on the attacked model ---
+    WORSTCASE = (torchattacks.MultiAttack.on_model, _worst_case_linf(0.0005))
+    WORSTCASE_eps00075 = (torchattacks.MultiAttack.on_model, _worst_case_linf(0.00075))
+    WORSTCASE_eps001 = (torchattacks.MultiAttack.on_model, _worst_case_linf(0.001))
+
+    WORSTCASE_L2 = (torchattacks.MultiAttack.on_model, {"members": [("PGDL2", {"eps": 0.1, "steps": 10}),
+                                                                    ("APGD", {"norm": "L2", "eps": 0.1, "steps": 10})]})
+
+    WORSTCASE40_eps003 = (torchattacks.MultiAttack.on_model, _worst_case_linf(0.003, steps=40, apgd_steps=100))  # PGD40_eps003's radius
 
     NO_ATTACK = (None, {})

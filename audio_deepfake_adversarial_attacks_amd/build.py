@@ -12,13 +12,15 @@ SOURCES = [PKG / "csrc" / "advstep.hip", PKG / "csrc" / "lcnn_mfm.hip", PKG / "c
            PKG / "csrc" / "lcnn_conv1x1.hip", PKG / "csrc" / "lcnn_lstm.hip", PKG / "csrc" / "lcnn_wino.hip",
            PKG / "csrc" / "lfcc.hip", PKG / "csrc" / "lfcc_stft.hip", PKG / "csrc" / "fab.hip",
            PKG / "csrc" / "wave_prep.hip", PKG / "csrc" / "specrnet_gru.hip", PKG / "csrc" / "detector_elem.hip",
-           PKG / "csrc" / "detector_conv.hip", PKG / "csrc" / "apgd.hip", PKG / "csrc" / "momentum.hip"]
+           PKG / "csrc" / "detector_conv.hip", PKG / "csrc" / "apgd.hip", PKG / "csrc" / "momentum.hip",
+           PKG / "csrc" / "multiattack.hip"]
 HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants (tools/gen_stft_tables.py), #included by lfcc_stft.hip
            PKG / "csrc" / "advstep_common.h",      # internal helpers #included by every source
            PKG / "csrc" / "row_tiles.h",           # (tile, row) addressing and partial re-reductions of every row kernel
            ROOT / "include" / "advstep.h", ROOT / "include" / "advstep_lcnn.h", ROOT / "include" / "advstep_frontend.h",
            ROOT / "include" / "advstep_fab.h", ROOT / "include" / "advstep_dataset.h", ROOT / "include" / "advstep_detector.h",
-           ROOT / "include" / "advstep_apgd.h", ROOT / "include" / "advstep_momentum.h"]
+           ROOT / "include" / "advstep_apgd.h", ROOT / "include" / "advstep_momentum.h",
+           ROOT / "include" / "advstep_multi.h"]
 LIB = PKG / "libadvstep.so"
 STAMP = PKG / "libadvstep.so.buildkey"   # git-ignored like the library; travels with it to the GPU box
 

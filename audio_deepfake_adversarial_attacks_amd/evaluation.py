@@ -12,7 +12,8 @@ log line.  What is different is how the work is placed on the machine:
   * scores stay on the device until the end (the reference synchronises with `.item()` / `.cpu()` every batch,
     :261-265); one D2H copy per run;
   * the final aggregate is the only communication: an all-reduce(SUM) of the two counters and one all-gather of
-    the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests.
+    the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
+    (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts).
 """
 from __future__ import annotations
 
@@ -348,6 +349,13 @@ def generate_attacks(
         # decorrelate the random starts of different ranks (all ranks were seeded alike to build equal replicas)
         torch.manual_seed(seed + rank)
 
+    # a MultiAttack reports the utterances left after every member as well (multiattack.py's `save` mechanism: accumulate the
+    # records of every call)
+    from .torchattacks import MultiAttack
+    multi = atk if isinstance(atk, MultiAttack) else None
+    if multi is not None:
+        multi._start_multi_atk_records()
+
     lanes = _Lanes(device, in_flight if in_flight is not None
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
@@ -397,11 +405,23 @@ def generate_attacks(
     all_pred, all_label, all_y, n_correct, n_total = aggregate_across_ranks(
         torch.cat(y_pred), torch.cat(y_pred_label), torch.cat(y), num_correct, num_total)
 
+    if multi is not None:
+        remaining = torch.tensor([int(r) for r in multi._multi_atk_records], dtype=torch.int64, device=device)
+        multi._clear_multi_atk_records()
+        multi._accumulate_multi_atk_records = False
+        if world > 1:
+            dist.all_reduce(remaining, op=dist.ReduceOp.SUM)     # next to the counters' all-reduce: (n_members + 1) int64
+        remaining = remaining.tolist()
+
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
     if return_scores:
         report["scores"] = {"y_pred": all_pred, "y_pred_label": all_label, "y": all_y}
+    if multi is not None:
+        report["multi_attack/remaining"] = remaining
     if rank == 0:
+        if multi is not None:
+            LOGGER.info(multi._return_sr_record(remaining))
         LOGGER.info(format_report(report))
     return report

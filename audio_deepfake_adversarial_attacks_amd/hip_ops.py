@@ -14,6 +14,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   cw_*                               .../attacks/cw.py:57, 72-77, 87-103
   ce2_loss_grad                      .../attacks/pgd.py:62,50,68 (and the same lines of fgsm.py / pgdl2.py)
   mi_step / vt_*                     .../attacks/mifgsm.py:70-76, nifgsm.py:56,67-71, vmifgsm.py:77-101
+  multi_route                        .../attacks/multiattack.py:55-66
 """
 from __future__ import annotations
 
@@ -708,3 +709,45 @@ def vt_variance(gv, adv_grad, N: int, out=None):
                                                  _stream(gv.device))
     _lib.check(st, "advstep_vt_variance_f32")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# MultiAttack's row router (include/advstep_multi.h; reference .../attacks/multiattack.py:55-66)
+# ---------------------------------------------------------------------------------------------------------
+
+def multi_route(adv, x, z, labels, rows, final, next_x=None, next_y=None, next_rows=None):
+    """One stage of MultiAttack's bookkeeping over the n rows of a sub-batch: row i is wrong when (z[i] > 0) != labels[i];
+    a wrong row goes to final[rows[i]] = adv[i], a kept row to the next free row k of next_x / next_y / next_rows (= x[i],
+    labels[i], rows[i]), in ascending i.  Returns (next_x, next_y, next_rows, counts): the buffers are n rows long and only
+    their first counts[1] rows are written; counts = int32 (number wrong, number kept) on the device — the caller narrows
+    after reading it.  next_x must not be x, adv or final (no compaction in place); final is none of the others."""
+    _require(adv, "adv"), _require(x, "x"), _require(z, "z"), _require(final, "final")
+    _require(labels, "labels", torch.int64), _require(rows, "rows", torch.int32)
+    _same_shape(("adv", adv), ("x", x))
+    n, T = _rows(adv, "adv")
+    B, Tf = _rows(final, "final")
+    if (n and Tf != T) or final.device != adv.device:
+        raise ValueError(f"final {tuple(final.shape)}@{final.device} does not hold rows of adv {tuple(adv.shape)}@{adv.device}")
+    for name, t in (("z", z), ("labels", labels), ("rows", rows)):
+        if t.numel() != n or t.device != adv.device:
+            raise ValueError(f"{name} must hold one value per row of adv ({n}) on {adv.device}, got {tuple(t.shape)}@{t.device}")
+    next_x = _out_like(x, next_x, "next_x")
+    if next_y is None:
+        next_y = torch.empty(n, dtype=torch.int64, device=adv.device)
+    if next_rows is None:
+        next_rows = torch.empty(n, dtype=torch.int32, device=adv.device)
+    _require(next_y, "next_y", torch.int64), _require(next_rows, "next_rows", torch.int32)
+    if next_y.numel() != n or next_rows.numel() != n:
+        raise ValueError(f"next_y and next_rows must hold {n} values, got {next_y.numel()} and {next_rows.numel()}")
+    if n and T == 0:
+        raise ValueError("multi_route: rows of zero samples cannot be routed")
+    # n == 0: the library launches nothing and writes nothing, not even counts
+    counts = (torch.zeros if n == 0 else torch.empty)(2, dtype=torch.int32, device=adv.device)
+    scratch = torch.empty(max(n, 1), dtype=torch.int32, device=adv.device)
+    # compulsory traffic: every row is read once (from adv or from x) and written once (to final or to next_x)
+    with _Launch("multi_route", adv.device, tensors=(adv, adv)):
+        st = _lib.load().advstep_multi_route_f32(adv.data_ptr(), x.data_ptr(), z.data_ptr(), labels.data_ptr(), rows.data_ptr(),
+                                                 final.data_ptr(), next_x.data_ptr(), next_y.data_ptr(), next_rows.data_ptr(),
+                                                 counts.data_ptr(), scratch.data_ptr(), n, B, T, _stream(adv.device))
+    _lib.check(st, "advstep_multi_route_f32")
+    return next_x, next_y, next_rows, counts

@@ -32,6 +32,9 @@ class Attack(object):
     # the attack's inner loop can replay from a hipGraph (torchattacks/graphed.py): PGD, PGDL2.  evaluation.generate_attacks
     # keeps two batches in flight for those (additive attribute; the reference has no counterpart)
     replays_from_graph = False
+    # per-attack off switch of the hipGraph replay (graphed.run_iterations): MultiAttack sets it around member calls on a
+    # sub-batch, whose ever-changing row counts must not become captures
+    _graph_off = False
 
     def __init__(self, name, model):
         # attack.py:14-35

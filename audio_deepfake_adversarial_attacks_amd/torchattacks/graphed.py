@@ -26,7 +26,8 @@ weights before every attack call: those calls stay eager), and capturing a workl
 the same workload under older states (each holds a private memory pool).  Random starts are drawn OUTSIDE the graph (a fresh Philox key per call).
 
 Eager fallback, always bit-identical: CPU op tables / checked ops (tests), launch profiling of kernels INSIDE the model
-part (hip_ops.start_profile without graph_ok: bench.py's per-family brackets), ADVSTEP_ATTACK_GRAPH=0, or a failed capture."""
+part (hip_ops.start_profile without graph_ok: bench.py's per-family brackets), ADVSTEP_ATTACK_GRAPH=0, the attack's own off
+switch (Attack._graph_off: MultiAttack's member calls on a sub-batch), or a failed capture."""
 from __future__ import annotations
 
 import os
@@ -152,7 +153,7 @@ def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torc
     # launch profiling: brackets around kernels of the model part need eager launches; brackets around the step kernels only
     # (start_profile(..., graph_ok=True): bench.py's timed region) go with the split form, whose steps are plain launches
     profiling_allows = hip_ops._profile is None or (hip_ops._profile_graph_ok and not fused)
-    use_graph = (enabled() and ops is hip_ops and profiling_allows and adv.is_cuda and steps >= 4
+    use_graph = (enabled() and not attack._graph_off and ops is hip_ops and profiling_allows and adv.is_cuda and steps >= 4
                  and not torch.cuda.is_current_stream_capturing() and not (fused and step_has_state))
     done = 0
     if use_graph:
