@@ -34,31 +34,52 @@
 #include "advstep_detector.h"
 #include "advstep_lcnn.h"
 #include "advstep_common.h"
-
-// Build-time switches (tools/build_variant.sh SOURCE -DNAME=...):
-// WINO_GLDS: the STREAM kernels copy weight chunks global -> LDS by LDS-DMA rather than through registers (wino3x3_kernel's
-// copy_chunk); by default only the compact-source (SRC == 1) instantiations do.  Expands inside the kernel template, whose
-// parameter SRC it names.
-#ifndef WINO_GLDS
-#define WINO_GLDS (SRC == 1)
-#endif
-#ifndef WINO_TIMING_NT1          // timing-only builds (tools/build_variant.sh ... -DWINO_TIMING_NT1=1): the last slice ALWAYS as one
-#define WINO_TIMING_NT1 0       // accumulator tile, i.e. rows 16..31 of a 17..32-row slice dropped (wrong results) - what SpecRNet's
-#endif                          // 20-row layers would cost if their 12 dead rows were free
+#include "lcnn_wino_plan.h"       // Src, Epi and their predicates, the tile constants, the launch plan, the wrappers' checks
 
 namespace {
 
-constexpr int kWaves = 8, kThreads = kWaves * 64;
-constexpr int kChunkCin = 16;                         // input channels per LDS chunk
-constexpr int kChunkFloats = 16 * kChunkCin * 32;     // [xi][cin][16 j][2 m] = 32 KB
-constexpr int kMaxResident = 4;                       // chunks kept in LDS when K <= 64
+// The convolution kernel's LDS, at namespace scope so that every helper below names it directly (handed on as a pointer it is
+// a generic one until the compiler proves otherwise, and the kernels come out differently).  A kernel is charged for what its
+// instantiation uses: the weight chunks (dynamic: the resident chunks, or 2 / 4 stream buffers), and per slice the epilogue
+// constants and the few-channel 1x1 weights — see stage_constants.
+extern __shared__ __attribute__((aligned(16))) float wino_u_s[];
+__shared__ __attribute__((aligned(16))) float wino_cst[48];
+__shared__ float wino_few_w[64];
 
 // ---- weight transform: U = G g G^T into the chunked layout ------------------------------------------------------------
+// u = G g G^T of one (output row, reduction channel) for both preparation kernels
+__device__ __forceinline__ void weight_transform(const float (&g)[3][3], float (&u)[4][4]) {
+    // G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
+    float t[4][3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        t[0][b] = g[0][b];
+        t[1][b] = 0.5f * (g[0][b] + g[1][b] + g[2][b]);
+        t[2][b] = 0.5f * (g[0][b] - g[1][b] + g[2][b]);
+        t[3][b] = g[2][b];
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        u[a][0] = t[a][0];
+        u[a][1] = 0.5f * (t[a][0] + t[a][1] + t[a][2]);
+        u[a][2] = 0.5f * (t[a][0] - t[a][1] + t[a][2]);
+        u[a][3] = t[a][2];
+    }
+}
+// U: [slice][chunk][xi][16 cin][16 j][2 m], zero where a row / channel does not exist: u of reduction channel k for output
+// row (slice, j, m).  wino_prepare_plain_kernel keeps these four lines in its own body: with the call it schedules one
+// global load differently (one more s_waitcnt).
+__device__ __forceinline__ void store_chunked(const float (&u)[4][4], float *U, int slice, int chunks, int k, int j, int m) {
+    const int chunk = k / kChunkCin, kc = k % kChunkCin;
+    float *dst = U + ((int64_t)(slice * chunks + chunk)) * kChunkFloats + (kc * 16 + j) * 2 + m;
+#pragma unroll
+    for (int xi = 0; xi < 16; ++xi) dst[xi * (kChunkCin * 32)] = u[xi >> 2][xi & 3];
+}
+
 // mode 0 (forward, max-feature-map pairs): output row (slice, j, m) = conv channel m * C + slice * 16 + j, g = weight.
 // mode 1 (input gradient): the convolution that maps d(conv out) (2C channels) to d(conv in) (Cin channels) has kernel
 //         g'[ci][co][a][b] = weight[co][ci][2 - a][2 - b]; output row (slice, j, m) = input channel slice*32 + m*16 + j.
 // mode 2: mode 1 with the reduction channels in the compact source's order (halves interleaved per k-step, see below).
-// U: [slice][chunk][xi][16 cin][16 j][2 m], zero where a row / channel does not exist.
 __global__ void wino_prepare_kernel(const float *__restrict__ weight, const float *__restrict__ kscale,
                                     float *__restrict__ U, int Cin, int Cout, int mode, int slices, int chunks) {
     const int K = mode == 0 ? Cin : Cout;        // reduction channels
@@ -97,26 +118,9 @@ __global__ void wino_prepare_kernel(const float *__restrict__ weight, const floa
                 for (int b = 0; b < 3; ++b) g[a][b] *= f;
         }
     }
-    // G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
-    float t[4][3], u[4][4];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        t[0][b] = g[0][b];
-        t[1][b] = 0.5f * (g[0][b] + g[1][b] + g[2][b]);
-        t[2][b] = 0.5f * (g[0][b] - g[1][b] + g[2][b]);
-        t[3][b] = g[2][b];
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        u[a][0] = t[a][0];
-        u[a][1] = 0.5f * (t[a][0] + t[a][1] + t[a][2]);
-        u[a][2] = 0.5f * (t[a][0] - t[a][1] + t[a][2]);
-        u[a][3] = t[a][2];
-    }
-    const int chunk = k / kChunkCin, kc = k % kChunkCin;
-    float *dst = U + ((int64_t)(slice * chunks + chunk)) * kChunkFloats + (kc * 16 + j) * 2 + m;
-#pragma unroll
-    for (int xi = 0; xi < 16; ++xi) dst[xi * (kChunkCin * 32)] = u[xi >> 2][xi & 3];
+    float u[4][4];
+    weight_transform(g, u);
+    store_chunked(u, U, slice, chunks, k, j, m);
 }
 
 // Plain convolutions (advstep_resconv_*): R output rows, reduction over K1 channels with 3x3 taps followed by K2 channels
@@ -155,21 +159,9 @@ __global__ void wino_prepare_plain_kernel(const float *__restrict__ w3, const fl
 #pragma unroll
             for (int b = 0; b < 3; ++b) g[a][b] *= f;
     }
-    float t[4][3], u[4][4];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        t[0][b] = g[0][b];
-        t[1][b] = 0.5f * (g[0][b] + g[1][b] + g[2][b]);
-        t[2][b] = 0.5f * (g[0][b] - g[1][b] + g[2][b]);
-        t[3][b] = g[2][b];
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        u[a][0] = t[a][0];
-        u[a][1] = 0.5f * (t[a][0] + t[a][1] + t[a][2]);
-        u[a][2] = 0.5f * (t[a][0] - t[a][1] + t[a][2]);
-        u[a][3] = t[a][2];
-    }
+    float u[4][4];
+    weight_transform(g, u);
+    // store_chunked's lines, in place: see there
     const int chunk = k / kChunkCin, kc = k % kChunkCin;
     float *dst = U + ((int64_t)(slice * chunks + chunk)) * kChunkFloats + (kc * 16 + j) * 2 + m;
 #pragma unroll
@@ -177,61 +169,36 @@ __global__ void wino_prepare_plain_kernel(const float *__restrict__ w3, const fl
 }
 
 // ---- the convolution ---------------------------------------------------------------------------------------------------
-// EPI 0: plain store of min(32, Cout - slice * 32) channels per slice (the input-gradient convolution).
-// EPI 1: bias + max-feature-map + 2x2 pool [+ BatchNorm]; Cout = number of max-feature-map channels C.
-// EPI 2: bias + max-feature-map [+ BatchNorm] without the pool; one selection byte per 2x2 tile.
-// STREAM: K > 64, U chunks streamed through LDS (two buffers and a barrier per chunk; SRC 1: four buffers, a barrier per two
-//         chunks, one stream across tile groups); otherwise all chunks stay resident.
-// grid = slices * ranges workgroups; workgroup b: slice b % slices, tile range b / slices.
-// SRC 0: the input is a dense tensor x (N, K, H, W).
-// SRC 1: the input is d(conv out) of a max-feature-map + 2x2 pool block, given in its compact form — the pooled gradient
-//        gy (N, C, H/2, W/2) and the selection bytes (advstep_mfm_pool2_forward_f32's encoding), K = 2C: channel k of
-//        half k / C at conv position (h, w) carries gy[k % C][h/2][w/2] if that position of that half won, else 0.  The
-//        4x4 patch of a lane is expanded from the 3x3 pooled cells around its tile; the dense gradient never exists.
-// SRC 2: the same for a plain MaxPool2d(2) (no halves): gy (N, K, H/2, W/2) and ATen-order selection bytes (2 * dh + dw):
-//        channel k at (h, w) carries gy[k][h/2][w/2] if that position won its window, else 0 (odd trailing row / column: 0).
-// EPI 3: + shift[ch], LeakyReLU(slope), plain store            (the residual blocks of SpecRNet, advstep_detector.h)
-// EPI 4: + bias[ch], MaxPool2d(2) with ATen's selection byte (detector_elem.hip::pool4): the conv output never exists.
-// EPI 5: * (h > 0 ? 1 : slope) with h (N, Cout, H, W) passed in `bn_mean` — LeakyReLU's backward from its OUTPUT (same sign as
-//        its input for slope > 0) — plain store.
-// EPI 6: the same from the activation's SIGN BYTES passed in `idx` (read only): one byte per (n, channel, 2x2 tile), bit 2 i + j =
-//        h > 0 at tile position (i, j), (N, Cout, TH, TW) — what EPI 3 writes next to h when it is given an `idx` to fill.  At
-//        SpecRNet's first block that is 21 MB in the epilogue instead of 331 MB of h: 476 -> 3xx us (round 3).
-// EPI 7: EPI 4 plus a 1x1 convolution over the ga.few (1 or 2) channels of ga.x2 added to the convolution output on the vector
-//        ALUs before the pool, weights (Cout, few) in `bn_mean`: SpecRNet's block0, whose downsample convolution has two input
-//        channels — as part of the reduction (GEN's x2) those two channels cost a whole k-step of six, 32 matrix instructions per
-//        wave and tile group for 8 useful rows of K; here they are 64 fused multiply-adds per lane.
+// wino3x3_kernel<EPI, STREAM, SRC, NT, GEN, WODD>, grid = slices * ranges workgroups; workgroup b: slice b % slices, tile range
+// b / slices (GenArgs::xcd: see there).
+// STREAM: K > 64, U chunks streamed through LDS (two buffers and a barrier per chunk; Src::MfmPooled: four buffers, a barrier per
+//         two chunks, one stream across tile groups); otherwise all chunks stay resident.
 // NT: accumulator tiles a wave computes — 2, or 1 for a convolution's LAST slice when only its first 16 rows exist
 //     (Cout % 32 in 1..16, LCNN's 128 -> 48 input gradient): that slice is launched on its own with half the matrix
 //     instructions instead of multiplying 16 zero rows.  slice0: first slice of this launch.
-// GEN (SRC 0 only): the reduction runs over the channels of TWO dense tensors, x (K1 channels, K1 % 4 == 0 when x2 is
+// GEN (not Src::MfmPooled): the reduction runs over the channels of TWO dense tensors, x (K1 channels, K1 % 4 == 0 when x2 is
 //     given) then x2 (Kreal - K1 channels) — a 1x1 convolution of x2 added to the 3x3 convolution of x is the same
 //     reduction with centre-tap-only weights — and Kreal need not fill the last k-step: K is Kreal rounded up to 4 (>= 8),
 //     channels >= Kreal get an out-of-range offset (read 0; their U rows are 0 as well).
+// WODD (Src::Dense): the plane width is odd, so the last tile of a row has no second column and its pair load's second element
+//     must be masked; even widths (all of LCNN's) skip those 4 selects per k-step.
 struct GenArgs {
     const float *x2;
     int K1, Kreal;
     float slope;
     int xcd;          // 1: workgroups b, b + 8, b + 16, ... (one XCD, one L2) take the slices of the same tile ranges
-    int few;          // EPI 7: channels of x2 (1 or 2) whose 1x1 convolution is added in the epilogue
+    int few;          // Epi::BiasPoolFew: channels of x2 (1 or 2) whose 1x1 convolution is added in the epilogue
     int halves;       // NT == 1, round 5: the launch's "slices" are the two 16-row HALVES of slice `slice0` (rows 16 h .. 16 h + 15:
                       // component h of the A pairs) - a one-slice layer on a small plane (LCNN's 64 -> 32 input gradient at 50 x 10:
                       // 1 000 tile groups, 125 workgroups) then fills the chip with 250 workgroups of half the matrix instructions
 };
 
-// WODD (SRC 0): the plane width is odd, so the last tile of a row has no second column and its pair load's second element must
-//     be masked; even widths (all of LCNN's) skip those 4 selects per k-step.
-template <int EPI, bool STREAM, int SRC, int NT = 2, bool GEN = false, bool WODD = false>
-__global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restrict__ x, const uint8_t *__restrict__ xsel,
-                                                           const float *__restrict__ U,
-                                                           const float *__restrict__ bias,
-                                                           const float *__restrict__ bn_mean,
-                                                           const float *__restrict__ bn_invstd, float *__restrict__ y,
-                                                           uint8_t *__restrict__ idx, int N, int K, int H, int W, int Cout,
-                                                           int slices, int ranges, int slice0, GenArgs ga) {
-    static_assert(NT == 2 || EPI == 0 || EPI == 3 || EPI == 5 || EPI == 6, "one accumulator tile only for the plain-store epilogues");
-    static_assert(!GEN || SRC != 1, "the general reduction reads dense tensors or a plain pooled gradient");
-    extern __shared__ __attribute__((aligned(16))) float u_s[];
+// a workgroup's slice (and 16-row half of it, GenArgs::halves) and tile range
+struct WgPlace {
+    int slice, half, range;
+};
+template <int NT>
+__device__ __forceinline__ WgPlace place_of_workgroup(int slices, int ranges, int slice0, const GenArgs &ga) {
     int slice_i = blockIdx.x % slices, range = blockIdx.x / slices;
     if (ga.xcd) {
         const int x = blockIdx.x & 7, w = blockIdx.x >> 3;
@@ -240,19 +207,25 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
     }
     const int half = (NT == 1 && ga.halves) ? slice_i : 0;
     const int slice = (NT == 1 && ga.halves) ? slice0 : slice0 + slice_i;
-    const int chunks = (K + kChunkCin - 1) / kChunkCin, steps = K / 4;
-    const float *Usl = U + (int64_t)slice * chunks * kChunkFloats;
-    // STREAM with a compact source: a chunk goes global -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers, nothing
-    // to wait for at the point of issue; round 3).  Through registers the four loads of a chunk are followed at once by their four
-    // ds_write, i.e. by s_waitcnt vmcnt(0), right after every chunk barrier.  Measured: compact-source input gradients 286 -> 281
-    // and 170 -> 167 us; the dense-source ones get SLOWER (276 -> 287 us: with a DMA in flight hipcc waits vmcnt(0) at the next
-    // use of an ordinary load, which drains their patch prefetch), so they keep the register path.  The DMA's completion is waited
-    // for (vmcnt(0)) before the barrier that publishes the chunk.  The LDS destination of a wave-instruction is a wave-uniform
-    // base + lane x 16 B, which is exactly this copy's layout.  WINO_GLDS (top of the file) selects it.
-    auto copy_chunk = [&](int chunk, int buf) {
+    return {slice, half, range};
+}
+
+// This slice's weight chunks: where they are in global memory, the LDS buffers they go to, and how they get there.
+template <bool DMA>
+struct WeightChunks {
+    const float *Usl;
+    // DMA (STREAM with a compact max-feature-map source): a chunk goes global -> LDS by LDS-DMA (global_load_lds_dwordx4: no
+    // staging registers, nothing to wait for at the point of issue; round 3).  Through registers the four loads of a chunk are
+    // followed at once by their four ds_write, i.e. by s_waitcnt vmcnt(0), right after every chunk barrier.  Measured:
+    // compact-source input gradients 286 -> 281 and 170 -> 167 us; the dense-source ones get SLOWER (276 -> 287 us: with a DMA in
+    // flight hipcc waits vmcnt(0) at the next use of an ordinary load, which drains their patch prefetch), so they keep the
+    // register path.  The DMA's completion is waited for (vmcnt(0)) before the barrier that publishes the chunk.  The LDS
+    // destination of a wave-instruction is a wave-uniform base + lane x 16 B, which is exactly this copy's layout.
+    // chunks_by_dma() selects it.
+    __device__ __forceinline__ void copy(int chunk, int buf) const {
         const float4 *src = reinterpret_cast<const float4 *>(Usl + (int64_t)chunk * kChunkFloats);
-        float4 *dst = reinterpret_cast<float4 *>(u_s + buf * kChunkFloats);
-        if (STREAM && WINO_GLDS) {
+        float4 *dst = reinterpret_cast<float4 *>(wino_u_s + buf * kChunkFloats);
+        if (DMA) {
             const int w64 = (threadIdx.x >> 6) << 6;
 #pragma unroll
             for (int i = 0; i < kChunkFloats / 4 / kThreads; ++i)
@@ -262,28 +235,36 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
 #pragma unroll
             for (int i = 0; i < kChunkFloats / 4 / kThreads; ++i) dst[threadIdx.x + i * kThreads] = src[threadIdx.x + i * kThreads];
         }
-    };
-    // every LDS-DMA transfer of this wave has landed (vmcnt(0); expcnt / lgkmcnt untouched) — before the barrier that publishes it
-    auto dma_landed = [&]() {
-        if (STREAM && WINO_GLDS) __builtin_amdgcn_s_waitcnt(0x0F70);
-    };
-    // Per-slice epilogue constants, staged once per workgroup (round 3; they were 16 global loads + their address arithmetic per
-    // tile group): cst[0..15] / cst[16..31] = what is added to the two accumulator tiles' rows — the convolution's bias (EPI 1 / 2:
-    // of the two max-feature-map halves, minus the folded BatchNorm's mean: max-feature-map and max-pool commute with a
-    // per-channel shift), EPI 3's shift, EPI 4's bias; cst[32..47] = the BatchNorm's 1 / std (EPI 1 / 2).  The additive part
-    // enters through the matrix instruction's C operand: position (1, 1) of M reaches all four outputs of A^T M A with weight
-    // +1, so its accumulator starts at the constant instead of 0 and the epilogue has no bias adds.
-    constexpr bool kHasConst = EPI == 1 || EPI == 2 || EPI == 3 || EPI == 4 || EPI == 7;
-    __shared__ __attribute__((aligned(16))) float cst[48];
-    __shared__ float few_w[EPI == 7 ? 64 : 1];               // EPI 7: the 1x1 weights of this slice's 32 rows, [row][channel]
-    if (EPI == 7 && threadIdx.x >= 64 && threadIdx.x < 128) {
-        const int i = threadIdx.x - 64, row = i >> 1, c = i & 1, ch = slice * 32 + row;
-        few_w[i] = (ch < Cout && c < ga.few) ? bn_mean[ch * ga.few + c] : 0.0f;
     }
-    if (kHasConst && threadIdx.x < 48) {
+    // every LDS-DMA transfer of this wave has landed (vmcnt(0); expcnt / lgkmcnt untouched) — before the barrier that publishes it
+    __device__ __forceinline__ void landed() const {
+        if (DMA) __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
+    // lane's A address inside a chunk buffer for k-step s: cin_in_chunk = (s & 3) * 4 + g
+    __device__ __forceinline__ const float *a_ptr(int s, int buf, int g, int nl) const {
+        return wino_u_s + buf * kChunkFloats + (((s & 3) * 4 + g) * 16 + nl) * 2;
+    }
+};
+
+// Per-slice epilogue constants, staged once per workgroup (round 3; they were 16 global loads + their address arithmetic per
+// tile group): wino_cst[0..15] / [16..31] = what is added to the two accumulator tiles' rows — the convolution's bias (is_mfm:
+// of the two max-feature-map halves, minus the folded BatchNorm's mean: max-feature-map and max-pool commute with a
+// per-channel shift), ShiftLrelu's shift, BiasPool's bias; [32..47] = the BatchNorm's 1 / std (is_mfm).  The additive part
+// enters through the matrix instruction's C operand: position (1, 1) of M reaches all four outputs of A^T M A with weight
+// +1, so its accumulator starts at the constant instead of 0 and the epilogue has no bias adds.
+// wino_few_w (adds_few): the 1x1 weights of this slice's 32 rows, [row][channel]; they arrive in the kernel's `bn_mean`.
+template <Epi EPI>
+__device__ __forceinline__ void stage_constants(int slice, int Cout, const float *bias, const float *bn_mean,
+                                                const float *bn_invstd, const GenArgs &ga) {
+    if (adds_few(EPI) && threadIdx.x >= 64 && threadIdx.x < 128) {
+        const float *w1x1 = bn_mean;
+        const int i = threadIdx.x - 64, row = i >> 1, c = i & 1, ch = slice * 32 + row;
+        wino_few_w[i] = (ch < Cout && c < ga.few) ? w1x1[ch * ga.few + c] : 0.0f;
+    }
+    if (has_constants(EPI) && threadIdx.x < 48) {
         const int q = threadIdx.x >> 4, j = threadIdx.x & 15;
         float v = q == 2 ? 1.0f : 0.0f;
-        if (EPI == 1 || EPI == 2) {
+        if (is_mfm(EPI)) {
             const int ch = slice * 16 + j;
             if (ch < Cout) {
                 if (q == 2) v = bn_mean ? bn_invstd[ch] : 1.0f;
@@ -293,10 +274,54 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
             const int ch = slice * 32 + q * 16 + j;
             if (ch < Cout && bias) v = bias[ch];
         }
-        cst[threadIdx.x] = v;
+        wino_cst[threadIdx.x] = v;
     }
+}
+
+// the input transform V = B^T d B (32 adds)
+__device__ __forceinline__ void input_transform(const float (&d)[4][4], float (&v)[4][4]) {
+    float tr[4][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        tr[0][q] = d[0][q] - d[2][q];
+        tr[1][q] = d[1][q] + d[2][q];
+        tr[2][q] = d[2][q] - d[1][q];
+        tr[3][q] = d[1][q] - d[3][q];
+    }
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+        v[a4][0] = tr[a4][0] - tr[a4][2];
+        v[a4][1] = tr[a4][1] + tr[a4][2];
+        v[a4][2] = tr[a4][2] - tr[a4][1];
+        v[a4][3] = tr[a4][1] - tr[a4][3];
+    }
+}
+
+// Stage the slice's constants and resident weights, then per tile group of this wave: address the patch, reduce over K, run the
+// epilogue.  Two parameters carry their epilogue's operand under another name, and each is renamed where it is read:
+// `bn_mean` is also LreluGradH's h and BiasPoolFew's 1x1 weights (stage_constants), `idx` is whatever EpiBytes says.
+// The patch addressing, the k-step lambdas, the two k loops and the epilogues stay in this one scope: moved into functions
+// (operands in structs or as arguments) each of them changed the generated code of some instantiations — DESIGN.md 4p has
+// the list.  What did hold still is above: the workgroup's place, the weight chunks, the constants, the input transform.
+template <Epi EPI, bool STREAM, Src SRC, int NT = 2, bool GEN = false, bool WODD = false>
+__global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restrict__ x, const uint8_t *__restrict__ xsel,
+                                                           const float *__restrict__ U,
+                                                           const float *__restrict__ bias,
+                                                           const float *__restrict__ bn_mean,
+                                                           const float *__restrict__ bn_invstd, float *__restrict__ y,
+                                                           EpiBytes<EPI> *__restrict__ idx, int N, int K, int H, int W, int Cout,
+                                                           int slices, int ranges, int slice0, GenArgs ga) {
+    static_assert(NT == 2 || plain_store(EPI), "one accumulator tile only for the plain-store epilogues");
+    static_assert(!GEN || SRC != Src::MfmPooled, "the general reduction reads dense tensors or a plain pooled gradient");
+    const WgPlace wg = place_of_workgroup<NT>(slices, ranges, slice0, ga);
+    const int half = wg.half, slice = wg.slice, range = wg.range;
+    const int chunks = (K + kChunkCin - 1) / kChunkCin, steps = K / 4;
+    const float *Usl = U + (int64_t)slice * chunks * kChunkFloats;
+    const WeightChunks<STREAM && chunks_by_dma(SRC)> wc{Usl};
+    constexpr bool kHasConst = has_constants(EPI);
+    stage_constants<EPI>(slice, Cout, bias, bn_mean, bn_invstd, ga);
     if (!STREAM) {
-        for (int c = 0; c < chunks; ++c) copy_chunk(c, c);
+        for (int c = 0; c < chunks; ++c) wc.copy(c, c);
     }
     if (!STREAM || kHasConst) __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, nl = lane & 15;
@@ -305,22 +330,22 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
     const int iters = (groups + ranges * kWaves - 1) / (ranges * kWaves);   // the same for every workgroup
     const uint32_t plane = (uint32_t)(H * W);
     // raw buffer over x: an out-of-range offset reads as 0 — the convolution's zero padding, for free
-    // SRC 1: pooled grid, max-feature-map channels (two conv channels per pooled channel); SRC 2: pooled grid, Kreal channels
-    const int Hs = H >> 1, Ws = W >> 1, Cs = SRC == 1 ? K >> 1 : (GEN ? ga.Kreal : K);
+    // MfmPooled: pooled grid, max-feature-map channels (two conv channels per pooled channel); Pooled: pooled grid, Kreal channels
+    const int Hs = H >> 1, Ws = W >> 1, Cs = SRC == Src::MfmPooled ? K >> 1 : (GEN ? ga.Kreal : K);
     const uint32_t cplane = (uint32_t)(Hs * Ws);
     const int KA = GEN ? ga.K1 : K, KB = GEN ? ga.Kreal - ga.K1 : 0;      // channels of x and of x2
-    const size_t src_elems = SRC == 0 ? (size_t)N * KA * plane : (size_t)N * Cs * cplane;
+    const size_t src_elems = SRC == Src::Dense ? (size_t)N * KA * plane : (size_t)N * Cs * cplane;
     const __amdgpu_buffer_rsrc_t xr =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x), 0, (int)(src_elems * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t xr2 = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(GEN && KB > 0 ? ga.x2 : x), 0, GEN && KB > 0 ? (int)((size_t)N * KB * plane * 4) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t sr =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(SRC != 0 ? xsel : reinterpret_cast<const uint8_t *>(x)), 0,
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(SRC != Src::Dense ? xsel : reinterpret_cast<const uint8_t *>(x)), 0,
                                           (int)src_elems, 0x00020000);
 
-    if (STREAM && SRC == 1) {       // the U stream's first two chunks (see the k loop of SRC 1)
-        copy_chunk(0, 0);
-        copy_chunk(1, 1);
+    if (STREAM && SRC == Src::MfmPooled) {       // the U stream's first two chunks (see the k loop of Src::MfmPooled)
+        wc.copy(0, 0);
+        wc.copy(1, 1);
     }
     for (int it = 0; it < iters; ++it) {
         const int grp = (it * ranges + range) * kWaves + wave;
@@ -332,7 +357,7 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
         // as lane masks, and an invalid tap gets an out-of-range offset (reads 0) when the load is issued
         const uint32_t lane_base = (((uint32_t)(n * KA + g)) * plane + (uint32_t)((2 * th - 1) * W + (2 * tw - 1))) * 4u;
         const uint32_t lane_base2 = (((uint32_t)(n * KB + g)) * plane + (uint32_t)((2 * th - 1) * W + (2 * tw - 1))) * 4u;
-        // SRC 0: a patch row is [column 2 tw - 1 | columns 2 tw, 2 tw + 1 | column 2 tw + 2].  The middle pair is ONE 8-byte load
+        // Src::Dense: a patch row is [column 2 tw - 1 | columns 2 tw, 2 tw + 1 | column 2 tw + 2].  The middle pair is ONE 8-byte load
         // (the 16 lanes of a lane row hold consecutive tiles: 128 contiguous bytes); the outer columns are the neighbouring
         // tiles' pairs and come from the neighbouring LANES (DPP row shift) — only the first / last lane of a lane row loads its
         // outer column itself (one dword load per patch row with 2 of 16 lanes active).  8 load instructions per k-step instead of
@@ -340,8 +365,8 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
         // (halving them — wrong results, timing only — made the L6 / L13 kernels 9-25 % faster).
         bool row_ok[4], ok_l[4], ok_r[4], ok_2[4], ok_e[4];      // lane masks (scalar registers)
         uint32_t pair_off[4], edge_off[4];                       // byte offsets from the lane base (GEN) / the tensor base
-        uint32_t cell[3][3];     // SRC 1: element offsets of the 3x3 pooled cells around the tile (0x20000000 = outside)
-        if (SRC == 0) {
+        uint32_t cell[3][3];     // compact sources: element offsets of the 3x3 pooled cells around the tile (0x20000000 = outside)
+        if (SRC == Src::Dense) {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int hh = 2 * th - 1 + p;
@@ -366,10 +391,10 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
         }
         f32x4 acc[16][NT];
 
-        // a patch in flight: SRC 0 the 16 taps; SRC 1 the 9 pooled gradients + their 9 selection bytes
+        // a patch in flight: Src::Dense the 16 taps; compact sources the 9 pooled gradients + their 9 selection bytes
         struct Patch {
-            float v[SRC == 0 ? 12 : 9];          // SRC 0: per patch row the pair (2 p, 2 p + 1), then the 4 edge values (8 + p)
-            uint32_t code[SRC == 0 ? 1 : 9];
+            float v[SRC == Src::Dense ? 12 : 9];          // Dense: per patch row the pair (2 p, 2 p + 1), then the 4 edge values (8 + p)
+            uint32_t code[SRC == Src::Dense ? 1 : 9];
         };
         auto load_row = [&](Patch &dst, int p, __amdgpu_buffer_rsrc_t r, uint32_t po, uint32_t eo, uint32_t soff) {
             const f32x2 pr = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, po, soff, 0));
@@ -378,7 +403,7 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
             dst.v[8 + p] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, eo, soff, 0));
         };
         auto load_patch = [&](Patch &dst, int s) {
-            if (SRC == 0 && GEN) {
+            if (SRC == Src::Dense && GEN) {
                 const bool first = 4 * s < ga.K1;                          // wave-uniform: this k-step reads x (else x2)
                 const uint32_t soff = (uint32_t)(first ? 4 * s : 4 * s - ga.K1) * plane * 4u;
                 const bool lane_ok = 4 * s + g < ga.Kreal;                // padded reduction channels read 0
@@ -388,14 +413,14 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                 for (int p = 0; p < 4; ++p)
                     load_row(dst, p, r, (row_ok[p] && lane_ok) ? base + pair_off[p] : 0x80000000u,
                              (ok_e[p] && lane_ok) ? base + edge_off[p] : 0x80000000u, soff);
-            } else if (SRC == 0) {
+            } else if (SRC == Src::Dense) {
                 const uint32_t soff = (uint32_t)(4 * s) * plane * 4u;
 #pragma unroll
                 for (int p = 0; p < 4; ++p) load_row(dst, p, xr, pair_off[p], edge_off[p], soff);
             } else {
-                const int k0 = 4 * s, c0 = k0;      // wave-uniform: channel of lane group 0 (SRC 1: `s` counts k-step PAIRS)
+                const int k0 = 4 * s, c0 = k0;      // wave-uniform: channel of lane group 0 (MfmPooled: `s` counts k-step PAIRS)
                 const uint32_t soff = (uint32_t)c0 * cplane;
-                const bool lane_ok = SRC == 1 || !GEN || k0 + g < ga.Kreal;        // padded reduction channels read 0
+                const bool lane_ok = SRC == Src::MfmPooled || !GEN || k0 + g < ga.Kreal;        // padded reduction channels read 0
 #pragma unroll
                 for (int i = 0; i < 9; ++i) {
                     const uint32_t e = lane_ok ? cell[i / 3][i % 3] : 0x20000000u;
@@ -404,9 +429,9 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                 }
             }
         };
-        // the 4x4 taps of a patch: SRC 1 routes each pooled gradient to the one conv position (of the one half) that won
+        // the 4x4 taps of a patch: a compact source routes each pooled gradient to the one conv position (of the one half) that won
         auto taps = [&](const Patch &src, int s, float (&d)[4][4]) {
-            if (SRC == 0) {
+            if (SRC == Src::Dense) {
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const float a = src.v[2 * p], b = src.v[2 * p + 1], e = src.v[8 + p];
@@ -421,7 +446,7 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                     d[p][3] = ok_r[p] ? right : 0.0f;
                 }
             } else {
-                const uint32_t half_bit = SRC == 1 && (s & 1) ? 4u : 0u;              // wave-uniform: odd k-steps are the second half
+                const uint32_t half_bit = SRC == Src::MfmPooled && (s & 1) ? 4u : 0u;              // wave-uniform: odd k-steps are the second half
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -450,28 +475,15 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
             request(0);
             request(1);
             __builtin_amdgcn_sched_barrier(0);
-            float d[4][4], tr[4][4], v[4][4];
+            float d[4][4], v[4][4];
             taps(patch, s_idx, d);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                tr[0][q] = d[0][q] - d[2][q];
-                tr[1][q] = d[1][q] + d[2][q];
-                tr[2][q] = d[2][q] - d[1][q];
-                tr[3][q] = d[1][q] - d[3][q];
-            }
-#pragma unroll
-            for (int a4 = 0; a4 < 4; ++a4) {
-                v[a4][0] = tr[a4][0] - tr[a4][2];
-                v[a4][1] = tr[a4][1] + tr[a4][2];
-                v[a4][2] = tr[a4][2] - tr[a4][1];
-                v[a4][3] = tr[a4][1] - tr[a4][3];
-            }
+            input_transform(d, v);
             __builtin_amdgcn_sched_barrier(0);
             const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
             f32x4 c0 = zero, c1 = zero;                         // the first k-step's C operand of position (1, 1): see cst[]
             if (decltype(first)::value && kHasConst) {
-                c0 = *reinterpret_cast<const f32x4 *>(cst + 4 * g);
-                c1 = *reinterpret_cast<const f32x4 *>(cst + 16 + 4 * g);
+                c0 = *reinterpret_cast<const f32x4 *>(wino_cst + 4 * g);
+                c1 = *reinterpret_cast<const f32x4 *>(wino_cst + 16 + 4 * g);
             }
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -490,11 +502,8 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
             }
             __builtin_amdgcn_s_setprio(0);
         };
-        // lane's A address inside a chunk buffer for k-step s: cin_in_chunk = (s & 3) * 4 + g
-        auto a_ptr = [&](int s, int buf) { return u_s + buf * kChunkFloats + (((s & 3) * 4 + g) * 16 + nl) * 2; };
-
         Patch da, db;
-        if constexpr (SRC == 1) {
+        if constexpr (SRC == Src::MfmPooled) {
             // Compact max-feature-map source (round 3): the two halves (c, c + C) of a pooled channel read the SAME pooled gradient
             // and selection byte, so the reduction is ordered half 0 / half 1 of channels 4 j .. 4 j + 3 in k-steps 2 j / 2 j + 1
             // (U prepared with mode 2) and ONE patch serves two k-steps: half the vector-memory loads of the k loop.  `da` is
@@ -514,113 +523,115 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
             load_patch(db, 1);
             const int q0 = it * chunks;                     // even: K % 32 == 0 for these sources
             auto stream_point = [&](int c) {                // before chunk c (even) of this tile group
-                dma_landed();           // vmcnt(0): BEFORE the next pair's patch is requested, or it would wait for that too
+                wc.landed();           // vmcnt(0): BEFORE the next pair's patch is requested, or it would wait for that too
                 __syncthreads();
 #pragma unroll
                 for (int d = 2; d < 4; ++d) {
                     const int cn = c + d;
-                    if (cn < chunks) copy_chunk(cn, (q0 + cn) & 3);
-                    else if (it + 1 < iters) copy_chunk(cn - chunks, (q0 + cn) & 3);
+                    if (cn < chunks) wc.copy(cn, (q0 + cn) & 3);
+                    else if (it + 1 < iters) wc.copy(cn - chunks, (q0 + cn) & 3);
                 }
             };
             if (STREAM) stream_point(0);
-            step(da, 0, a_ptr(0, STREAM ? (q0 & 3) : 0), std::true_type{});
-            step(da, 1, a_ptr(1, STREAM ? (q0 & 3) : 0), std::false_type{});
+            step(da, 0, wc.a_ptr(0, STREAM ? (q0 & 3) : 0, g, nl), std::true_type{});
+            step(da, 1, wc.a_ptr(1, STREAM ? (q0 & 3) : 0, g, nl), std::false_type{});
 #pragma unroll 1
             for (int s = 2; s < steps; s += 2) {
                 da = db;
                 if (STREAM && (s & 7) == 0) stream_point(s >> 2);
                 if (s + 2 < steps) load_patch(db, (s + 2) >> 1);
                 const int buf = STREAM ? ((q0 + (s >> 2)) & 3) : (s >> 2);
-                step(da, s, a_ptr(s, buf), std::false_type{});
-                step(da, s + 1, a_ptr(s + 1, buf), std::false_type{});
+                step(da, s, wc.a_ptr(s, buf, g, nl), std::false_type{});
+                step(da, s + 1, wc.a_ptr(s + 1, buf, g, nl), std::false_type{});
             }
         } else {
         if (STREAM) {
             __syncthreads();            // previous iteration's readers are done with both buffers
-            copy_chunk(0, 0);
-            dma_landed();
+            wc.copy(0, 0);
+            wc.landed();
             __syncthreads();
         }
         load_patch(da, 0);
         load_patch(db, 1);
-        step(da, 0, a_ptr(0, 0), std::true_type{});
+        step(da, 0, wc.a_ptr(0, 0, g, nl), std::true_type{});
         load_patch(da, 2);
-        step(db, 1, a_ptr(1, 0), std::false_type{});
-        if (STREAM) copy_chunk(1, 1);   // chunks >= 2 always here; lands while chunk 0's last steps run
+        step(db, 1, wc.a_ptr(1, 0, g, nl), std::false_type{});
+        if (STREAM) wc.copy(1, 1);   // chunks >= 2 always here; lands while chunk 0's last steps run
 #pragma unroll 1
         for (int s = 2; s + 1 < steps; s += 2) {
             if (STREAM && (s & 3) == 0) {
-                dma_landed();
+                wc.landed();
                 __syncthreads();        // chunk s/4 is complete in its buffer; chunk s/4 - 1 is free
-                if (s / 4 + 1 < chunks) copy_chunk(s / 4 + 1, (s / 4 + 1) & 1);
+                if (s / 4 + 1 < chunks) wc.copy(s / 4 + 1, (s / 4 + 1) & 1);
             }
             const int buf = STREAM ? ((s >> 2) & 1) : (s >> 2);
             load_patch(db, s + 1);      // in flight while this step's matrix instructions run
-            step(da, s, a_ptr(s, buf), std::false_type{});
+            step(da, s, wc.a_ptr(s, buf, g, nl), std::false_type{});
             if (s + 2 < steps) load_patch(da, s + 2);
-            step(db, s + 1, a_ptr(s + 1, buf), std::false_type{});
+            step(db, s + 1, wc.a_ptr(s + 1, buf, g, nl), std::false_type{});
         }
         if (GEN && (steps & 1)) {
             // an odd number of k-steps (K a multiple of 4, not of 8 — SpecRNet's 20-channel layers: 5 steps instead of 6): the last
             // one on its own; its patch was requested by the last pair (or by the prologue when steps == 3)
             const int s = steps - 1;
             if (STREAM && (s & 3) == 0) {                       // its chunk was copied one pair earlier
-                dma_landed();
+                wc.landed();
                 __syncthreads();
             }
-            step(da, s, a_ptr(s, STREAM ? ((s >> 2) & 1) : (s >> 2)), std::false_type{});
+            step(da, s, wc.a_ptr(s, STREAM ? ((s >> 2) & 1) : (s >> 2), g, nl), std::false_type{});
         }
-        }   // SRC != 1
+        }   // SRC != Src::MfmPooled
 
         // epilogue: Y = A^T M A per (channel, tile)
         const int Ho = H >> 1, Wo = W >> 1;
-        // EPI 5 reads the activation's output h at the tile's 2x2 positions of every row it stores — a 331 MB tensor at SpecRNet's
+        // Epi::LreluGradH reads the activation's output h at the tile's 2x2 positions of every row it stores — a 331 MB tensor at SpecRNet's
         // first block, i.e. HBM latency.  All of a lane's reads (4 rows x NT tiles x 2 tile rows) are requested HERE, before the
         // output transform's ~200 adds, instead of one row at a time right where they are used (round 3).
-        float hv5[EPI == 5 ? 4 : 1][EPI == 5 ? NT : 1][2][2];
-        if constexpr (EPI == 5) {
+        float hv[EPI == Epi::LreluGradH ? 4 : 1][EPI == Epi::LreluGradH ? NT : 1][2][2];
+        if constexpr (EPI == Epi::LreluGradH) {
+            const float *h = bn_mean;       // this epilogue's operand in that parameter
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int m = 0; m < NT; ++m) {
                     const int ch = slice * 32 + (m + half) * 16 + 4 * g + r;
                     const bool live = valid && ch < Cout;
-                    const float *hp = bn_mean + (((size_t)n * Cout + (live ? ch : 0)) * H + 2 * th) * W + 2 * tw;
+                    const float *hp = h + (((size_t)n * Cout + (live ? ch : 0)) * H + 2 * th) * W + 2 * tw;
                     const bool h1 = 2 * th + 1 < H, w1 = 2 * tw + 1 < W;
-                    hv5[r][m][0][0] = hv5[r][m][0][1] = hv5[r][m][1][0] = hv5[r][m][1][1] = 1.0f;
+                    hv[r][m][0][0] = hv[r][m][0][1] = hv[r][m][1][0] = hv[r][m][1][1] = 1.0f;
                     if (live) {
                         if ((W & 1) == 0) {
                             const f32x2 a = *reinterpret_cast<const f32x2 *>(hp);
-                            hv5[r][m][0][0] = a.x, hv5[r][m][0][1] = a.y;
+                            hv[r][m][0][0] = a.x, hv[r][m][0][1] = a.y;
                             if (h1) {
                                 const f32x2 b = *reinterpret_cast<const f32x2 *>(hp + W);
-                                hv5[r][m][1][0] = b.x, hv5[r][m][1][1] = b.y;
+                                hv[r][m][1][0] = b.x, hv[r][m][1][1] = b.y;
                             }
                         } else {
-                            hv5[r][m][0][0] = hp[0];
-                            if (w1) hv5[r][m][0][1] = hp[1];
+                            hv[r][m][0][0] = hp[0];
+                            if (w1) hv[r][m][0][1] = hp[1];
                             if (h1) {
-                                hv5[r][m][1][0] = hp[W];
-                                if (w1) hv5[r][m][1][1] = hp[W + 1];
+                                hv[r][m][1][0] = hp[W];
+                                if (w1) hv[r][m][1][1] = hp[W + 1];
                             }
                         }
                     }
                 }
         }
-        uint32_t hb6[EPI == 6 ? 4 : 1][EPI == 6 ? NT : 1];      // EPI 6: the same moment, one byte per (row, tile)
-        if constexpr (EPI == 6) {
+        uint32_t hb[reads_sign_bytes(EPI) ? 4 : 1][reads_sign_bytes(EPI) ? NT : 1];      // LreluGradBytes: the same moment, one byte per (row, tile)
+        if constexpr (reads_sign_bytes(EPI)) {
+            const uint8_t *act = idx;       // read only here: EpiBytes
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int m = 0; m < NT; ++m) {
                     const int ch = slice * 32 + (m + half) * 16 + 4 * g + r;
                     const bool live = valid && ch < Cout;
-                    hb6[r][m] = live ? idx[(((size_t)n * Cout + ch) * TH + th) * TW + tw] : 0u;
+                    hb[r][m] = live ? act[(((size_t)n * Cout + ch) * TH + th) * TW + tw] : 0u;
                 }
         }
-        float xf[EPI == 7 ? 2 : 1][2][2];       // EPI 7: x2 at the tile's 2x2 positions, requested before the output transform
-        if constexpr (EPI == 7) {
+        float xf[adds_few(EPI) ? 2 : 1][2][2];       // BiasPoolFew: x2 at the tile's 2x2 positions, requested before the output transform
+        if constexpr (adds_few(EPI)) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 xf[c][0][0] = xf[c][0][1] = xf[c][1][0] = xf[c][1][1] = 0.0f;
@@ -651,24 +662,24 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                 yy[m][1][0] = s1[0] + s1[1] + s1[2];
                 yy[m][1][1] = s1[1] - s1[2] - s1[3];
             }
-            if (EPI == 1) {
+            if constexpr (EPI == Epi::MfmPoolBn) {
                 const int ch = slice * 16 + 4 * g + r;
                 const bool live = ch < Cout;
                 int code;       // (bias - BatchNorm mean came in through the accumulator of position (1, 1): cst[])
                 float vbest = pool_select_fast(yy[0][0][0], yy[1][0][0], yy[0][0][1], yy[1][0][1], yy[0][1][0], yy[1][1][0],
                                                yy[0][1][1], yy[1][1][1], code);
-                if (bn_mean) vbest *= cst[32 + 4 * g + r];
+                if (bn_mean) vbest *= wino_cst[32 + 4 * g + r];
                 if (valid && live && th < Ho && tw < Wo) {
                     const size_t o = ((size_t)n * Cout + ch) * Ho * Wo + (size_t)th * Wo + tw;
                     y[o] = vbest;
                     idx[o] = (uint8_t)code;
                 }
-            } else if (EPI == 2) {
+            } else if constexpr (EPI == Epi::MfmBn) {
                 // bias + max-feature-map [+ BatchNorm], no pool: the tile's 2x2 outputs and one byte with their 4
                 // "second half won" bits (bit = 2 * row + col), (N, C, TH, TW)
                 const int ch = slice * 16 + 4 * g + r;
                 const bool live = ch < Cout;
-                const float sc = cst[32 + 4 * g + r];
+                const float sc = wino_cst[32 + 4 * g + r];
                 float out[2][2];
                 uint32_t bits = 0;
 #pragma unroll
@@ -691,13 +702,13 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                     }
                     idx[((size_t)n * Cout + ch) * TH * TW + (size_t)th * TW + tw] = (uint8_t)bits;
                 }
-            } else if (EPI == 4 || EPI == 7) {
+            } else if constexpr (pools(EPI)) {
 #pragma unroll
                 for (int m = 0; m < NT; ++m) {
                     const int ch = slice * 32 + (m + half) * 16 + 4 * g + r;
                     const bool live = ch < Cout;
-                    if (EPI == 7) {
-                        const float w0 = few_w[(m * 16 + 4 * g + r) * 2], w1 = few_w[(m * 16 + 4 * g + r) * 2 + 1];
+                    if (adds_few(EPI)) {
+                        const float w0 = wino_few_w[(m * 16 + 4 * g + r) * 2], w1 = wino_few_w[(m * 16 + 4 * g + r) * 2 + 1];
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                             yy[m][e >> 1][e & 1] = fmaf(w1, xf[1][e >> 1][e & 1], fmaf(w0, xf[0][e >> 1][e & 1], yy[m][e >> 1][e & 1]));
@@ -720,7 +731,7 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                 for (int m = 0; m < NT; ++m) {
                     const int ch = slice * 32 + (m + half) * 16 + 4 * g + r;
                     if (!(valid && ch < Cout)) continue;
-                    if (EPI == 3) {
+                    if constexpr (EPI == Epi::ShiftLrelu) {
                         uint32_t bits = 0;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -728,7 +739,7 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                             bits |= (uint32_t)(v > 0.0f) << e;
                             yy[m][e >> 1][e & 1] = v > 0.0f ? v : v * ga.slope;
                         }
-                        // the activation's sign bytes for EPI 6 (v > 0 and output > 0 are the same statement for slope > 0);
+                        // the activation's sign bytes for Epi::LreluGradBytes (v > 0 and output > 0 are the same statement for slope > 0);
                         // positions outside an odd-sized plane read 0
                         if (idx) {
                             if (2 * tw + 1 >= W) bits &= 0x5u;
@@ -738,13 +749,13 @@ __global__ __launch_bounds__(kThreads) void wino3x3_kernel(const float *__restri
                     }
                     float *o = y + (((size_t)n * Cout + ch) * H + 2 * th) * W + 2 * tw;
                     const bool h1 = 2 * th + 1 < H;
-                    if (EPI == 5) {
+                    if (EPI == Epi::LreluGradH) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) yy[m][e >> 1][e & 1] *= hv5[r][m][e >> 1][e & 1] > 0.0f ? 1.0f : ga.slope;
+                        for (int e = 0; e < 4; ++e) yy[m][e >> 1][e & 1] *= hv[r][m][e >> 1][e & 1] > 0.0f ? 1.0f : ga.slope;
                     }
-                    if (EPI == 6) {
+                    if (reads_sign_bytes(EPI)) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) yy[m][e >> 1][e & 1] *= (hb6[r][m] >> e) & 1u ? 1.0f : ga.slope;
+                        for (int e = 0; e < 4; ++e) yy[m][e >> 1][e & 1] *= (hb[r][m] >> e) & 1u ? 1.0f : ga.slope;
                     }
                     if ((W & 1) == 0) {   // rows are 8-byte aligned: one 64-bit store per tile row
                         *reinterpret_cast<f32x2 *>(o) = (f32x2){yy[m][0][0], yy[m][0][1]};
@@ -783,71 +794,34 @@ __global__ __launch_bounds__(256) void wino_mfm_backward_kernel(const float *__r
     }
 }
 
-// ADVSTEP_WINO_HALF_SLICE=0 (read at every call) keeps the single launch that multiplies the zero rows (A/B measurements).
-inline bool half_slice_enabled() {
-    const char *e = getenv("ADVSTEP_WINO_HALF_SLICE");
-    return !(e && e[0] == '0');
+// the instantiation a plan entry names.  One-tile kernels exist for the plain-store epilogues only and odd-width ones for
+// the dense source only; a plan asks for no others.
+template <Epi EPI, Src SRC, bool GEN>
+auto wino_kernel_for(const WinoLaunch &l) {
+    constexpr int kOne = plain_store(EPI) ? 1 : 2;
+    constexpr bool kOdd = SRC == Src::Dense;
+    using Kernel = decltype(&wino3x3_kernel<EPI, false, SRC, 2, GEN, false>);
+    static constexpr Kernel table[2][2][2] = {      // [stream][one tile][odd width]
+        {{wino3x3_kernel<EPI, false, SRC, 2, GEN, false>, wino3x3_kernel<EPI, false, SRC, 2, GEN, kOdd>},
+         {wino3x3_kernel<EPI, false, SRC, kOne, GEN, false>, wino3x3_kernel<EPI, false, SRC, kOne, GEN, kOdd>}},
+        {{wino3x3_kernel<EPI, true, SRC, 2, GEN, false>, wino3x3_kernel<EPI, true, SRC, 2, GEN, kOdd>},
+         {wino3x3_kernel<EPI, true, SRC, kOne, GEN, false>, wino3x3_kernel<EPI, true, SRC, kOne, GEN, kOdd>}}};
+    return table[l.stream][l.NT == 1][l.wodd];
 }
 
-template <int EPI, int SRC, bool GEN = false>
+template <Epi EPI, Src SRC, bool GEN = false>
 int launch_wino(const float *x, const uint8_t *xsel, const float *U, const float *bias, const float *bn_mean,
-                const float *bn_invstd, float *y, uint8_t *idx, int64_t N, int64_t K, int64_t H, int64_t W, int64_t Cout,
+                const float *bn_invstd, float *y, EpiBytes<EPI> *idx, int64_t N, int64_t K, int64_t H, int64_t W, int64_t Cout,
                 int slices, hipStream_t st, GenArgs ga = GenArgs{nullptr, 0, 0, 1.0f, 0, 0, 0}) {
-    const int cus = 256;
-    const int chunks = (int)ceil_div(K, kChunkCin);
-    const bool stream = chunks > kMaxResident;
-    const int64_t groups = ceil_div(N * ((H + 1) / 2) * ((W + 1) / 2), 16);
-    const size_t lds = (size_t)(stream ? (SRC == 1 ? 4 : 2) : chunks) * kChunkFloats * sizeof(float);
-    const bool wodd = SRC == 0 && (W & 1);
-    // ADVSTEP_WINO_RANGE_MULT=k (read per call, default 1): k times the workgroups, each walking 1 / k of the tile groups - a
-    // grid that is NOT persistent, so that workgroups of another stream's launch find compute units while this one runs (round 6
-    // experiment; the weights are staged once per workgroup, i.e. k times as often)
-    const char *em = getenv("ADVSTEP_WINO_RANGE_MULT");
-    const int mult = em && em[0] >= '1' && em[0] <= '8' ? em[0] - '0' : 1;
-    auto go = [&](auto kernel, int n_slices, int slice0) {
-        int ranges = mult * cus / n_slices;
-        if ((int64_t)ranges * kWaves > groups) ranges = (int)ceil_div(groups, kWaves);
-        if (ranges < 1) ranges = 1;
-        // the slices of one tile range read the same input tiles at the same time: put them on ONE XCD (workgroups b, b + 8, ...
-        // share an L2) so all but one of the reads hit it: 2-3 % on L13 forward and SpecRNet's block2.
-        // ADVSTEP_WINO_XCD=0 (read per call): round-robin slices (A/B)
-        const char *e = getenv("ADVSTEP_WINO_XCD");
-        ga.xcd = 0;
-        // — only where rounding the ranges down to a multiple of 8 does not add a pass over the tile groups
-        const int ranges8 = ranges & ~7;
-        if (!(e && e[0] == '0') && n_slices > 1 && ranges8 >= 8 &&
-            ceil_div(groups, (int64_t)ranges8 * kWaves) == ceil_div(groups, (int64_t)ranges * kWaves)) {
-            ranges = ranges8;
-            ga.xcd = 1;
-        }
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(n_slices * ranges)), dim3(kThreads), lds, st, x, xsel, U, bias, bn_mean, bn_invstd,
-                           y, idx, (int)N, (int)K, (int)H, (int)W, (int)Cout, n_slices, ranges, slice0, ga);
-    };
-    // plain-store epilogues with a half-empty last slice (Cout % 32 in 1..16): that slice on its own, one accumulator tile
-    int full = slices;
-    if constexpr (EPI == 0 || EPI == 3 || EPI == 5 || EPI == 6) {
-        const int live_last = (int)(Cout - (int64_t)(slices - 1) * 32);
-        if ((live_last <= 16 || WINO_TIMING_NT1) && half_slice_enabled()) {
-            full = slices - 1;
-            if (stream) wodd ? go(wino3x3_kernel<EPI, true, SRC, 1, GEN, SRC == 0>, 1, slices - 1) : go(wino3x3_kernel<EPI, true, SRC, 1, GEN>, 1, slices - 1);
-            else wodd ? go(wino3x3_kernel<EPI, false, SRC, 1, GEN, SRC == 0>, 1, slices - 1) : go(wino3x3_kernel<EPI, false, SRC, 1, GEN>, 1, slices - 1);
-        }
-    }
-    if constexpr (EPI == 0 && SRC == 1 && !GEN) {
-        // a ONE-slice layer whose tile groups do not fill the chip's 2 048 wave slots even once: the slice as its two 16-row
-        // halves, one accumulator tile each - twice the workgroups, half the matrix instructions per wave (the patch loads and
-        // input transforms are done twice, on compute units that would have idled).  ADVSTEP_WINO_HALVES=0: one launch (A/B)
-        const char *eh = getenv("ADVSTEP_WINO_HALVES");
-        if (full == 1 && slices == 1 && Cout == 32 && groups <= (int64_t)cus * kWaves / 2 && !(eh && eh[0] == '0')) {
-            ga.halves = 1;
-            stream ? go(wino3x3_kernel<EPI, true, SRC, 1, GEN>, 2, 0) : go(wino3x3_kernel<EPI, false, SRC, 1, GEN>, 2, 0);
-            return status_after_launch();
-        }
-    }
-    if (full > 0) {
-        if (stream) wodd ? go(wino3x3_kernel<EPI, true, SRC, 2, GEN, SRC == 0>, full, 0) : go(wino3x3_kernel<EPI, true, SRC, 2, GEN>, full, 0);
-        else wodd ? go(wino3x3_kernel<EPI, false, SRC, 2, GEN, SRC == 0>, full, 0) : go(wino3x3_kernel<EPI, false, SRC, 2, GEN>, full, 0);
+    const WinoPlan plan = plan_wino(EPI, SRC, GEN, N, K, H, W, Cout, slices, read_wino_knobs());
+    for (int i = 0; i < plan.count; ++i) {
+        const WinoLaunch &l = plan.launch[i];
+        const auto kernel = wino_kernel_for<EPI, SRC, GEN>(l);
+        ga.xcd = l.xcd;
+        ga.halves = l.halves;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(l.n_slices * l.ranges)), dim3(kThreads), l.lds, st, x, xsel, U, bias, bn_mean,
+                           bn_invstd, y, idx, (int)N, (int)K, (int)H, (int)W, (int)Cout, l.n_slices, l.ranges, l.slice0, ga);
     }
     return status_after_launch();
 }
@@ -885,9 +859,9 @@ int advstep_conv3x3_mfm_pool2_forward_f32(const float *x, const float *U, const 
     ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
     if (N == 0 || H / 2 == 0 || W / 2 == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x && U && y && idx && (bn_mean == nullptr) == (bn_invstd == nullptr));
-    ADVSTEP_REQUIRE((uint64_t)N * Cin * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
-    return launch_wino<1, 0>(x, nullptr, U, bias, bn_mean, bn_invstd, y, idx, N, Cin, H, W, C, (int)ceil_div(C, 16),
-                             as_stream(stream));
+    ADVSTEP_REQUIRE(wino_sizes_ok(N, H, W, Cin, 0, 0));
+    return launch_wino<Epi::MfmPoolBn, Src::Dense>(x, nullptr, U, bias, bn_mean, bn_invstd, y, idx, N, Cin, H, W, C,
+                                                   (int)ceil_div(C, 16), as_stream(stream));
 }
 
 size_t advstep_conv3x3_mfm_sel_bytes(int64_t N, int64_t C, int64_t H, int64_t W) {
@@ -901,9 +875,9 @@ int advstep_conv3x3_mfm_forward_f32(const float *x, const float *U, const float 
     ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, 2 * C));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x && U && y && sel && (bn_mean == nullptr) == (bn_invstd == nullptr));
-    ADVSTEP_REQUIRE((uint64_t)N * Cin * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
-    return launch_wino<2, 0>(x, nullptr, U, bias, bn_mean, bn_invstd, y, sel, N, Cin, H, W, C, (int)ceil_div(C, 16),
-                             as_stream(stream));
+    ADVSTEP_REQUIRE(wino_sizes_ok(N, H, W, Cin, 0, 0));
+    return launch_wino<Epi::MfmBn, Src::Dense>(x, nullptr, U, bias, bn_mean, bn_invstd, y, sel, N, Cin, H, W, C,
+                                               (int)ceil_div(C, 16), as_stream(stream));
 }
 
 int advstep_conv3x3_mfm_backward_f32(const float *gy, const uint8_t *sel, const float *gscale, float *gout, int64_t N,
@@ -923,9 +897,9 @@ int advstep_conv3x3_backward_data_f32(const float *gout, const float *U, float *
     ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_conv3x3_supported(Cin, Cout));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(gout && U && gx);
-    ADVSTEP_REQUIRE((uint64_t)N * Cout * H * W * 4 < (1ull << 31) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
-    return launch_wino<0, 0>(gout, nullptr, U, nullptr, nullptr, nullptr, gx, nullptr, N, Cout, H, W, Cin,
-                             (int)ceil_div(Cin, 32), as_stream(stream));
+    ADVSTEP_REQUIRE(wino_sizes_ok(N, H, W, Cout, 0, 0));
+    return launch_wino<Epi::Store, Src::Dense>(gout, nullptr, U, nullptr, nullptr, nullptr, gx, nullptr, N, Cout, H, W, Cin,
+                                               (int)ceil_div(Cin, 32), as_stream(stream));
 }
 
 int advstep_conv3x3_mfm_pool2_backward_f32(const float *gy, const uint8_t *idx, const float *U, float *gx, int64_t N,
@@ -937,9 +911,9 @@ int advstep_conv3x3_mfm_pool2_backward_f32(const float *gy, const uint8_t *idx, 
         return hipMemsetAsync(gx, 0, (size_t)N * Cin * H * W * sizeof(float), as_stream(stream)) == hipSuccess ? ADVSTEP_OK
                                                                                                                : ADVSTEP_ELAUNCH;
     ADVSTEP_REQUIRE(gy && idx && U);
-    ADVSTEP_REQUIRE((uint64_t)N * C * (H / 2) * (W / 2) < (1ull << 29) && (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
-    return launch_wino<0, 1>(gy, idx, U, nullptr, nullptr, nullptr, gx, nullptr, N, 2 * C, H, W, Cin, (int)ceil_div(Cin, 32),
-                             as_stream(stream));
+    ADVSTEP_REQUIRE(wino_sizes_ok(N, H, W, 0, C, 0));
+    return launch_wino<Epi::Store, Src::MfmPooled>(gy, idx, U, nullptr, nullptr, nullptr, gx, nullptr, N, 2 * C, H, W, Cin,
+                                                   (int)ceil_div(Cin, 32), as_stream(stream));
 }
 
 // ---- plain 3x3 convolutions of the detectors' residual blocks (include/advstep_detector.h) -----------------------------
@@ -966,8 +940,7 @@ int advstep_resconv_prepare_f32(const float *w3, const float *w1, const float *r
 static int resconv_check(const float *x1, const float *x2, const float *U, const void *y, int64_t N, int64_t K1, int64_t K2,
                          int64_t rows, int64_t H, int64_t W) {
     ADVSTEP_REQUIRE(x1 && U && y && (K2 == 0 || x2));
-    ADVSTEP_REQUIRE((uint64_t)N * (K1 > K2 ? K1 : K2) * H * W * 4 < (1ull << 31) && (uint64_t)N * rows * H * W * 4 < (1ull << 33) &&
-                    (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
+    ADVSTEP_REQUIRE(wino_sizes_ok(N, H, W, K1 > K2 ? K1 : K2, 0, rows));
     return ADVSTEP_OK;
 }
 
@@ -977,9 +950,9 @@ int advstep_resconv_forward_act_f32(const float *x1, const float *x2, const floa
     ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K1, K2, rows));
     if (N == 0 || H == 0 || W == 0) return ADVSTEP_OK;
     if (const int st = resconv_check(x1, x2, U, y, N, K1, K2, rows, H, W)) return st;
-    const int64_t K = (K1 + K2 <= 8) ? 8 : ceil_div(K1 + K2, 4) * 4;      // at least two k-steps; an odd count is fine
-    return launch_wino<3, 0, true>(x1, nullptr, U, shift, nullptr, nullptr, y, act, N, K, H, W, rows, (int)ceil_div(rows, 32),
-                                   as_stream(stream), GenArgs{x2, (int)K1, (int)(K1 + K2), slope, 0, 0, 0});
+    return launch_wino<Epi::ShiftLrelu, Src::Dense, true>(x1, nullptr, U, shift, nullptr, nullptr, y, act, N, padded_k(K1 + K2), H,
+                                                          W, rows, (int)ceil_div(rows, 32), as_stream(stream),
+                                                          GenArgs{x2, (int)K1, (int)(K1 + K2), slope, 0, 0, 0});
 }
 
 int advstep_resconv_forward_f32(const float *x1, const float *x2, const float *U, const float *shift, float slope, float *y,
@@ -995,11 +968,12 @@ int advstep_resconv_pool2_forward_f32(const float *x1, const float *x2, const fl
     if (N == 0 || H / 2 == 0 || W / 2 == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(sel);
     if (const int st = resconv_check(x1, x2, U, y, N, K1, K2, rows, H, W)) return st;
-    const int64_t K = (K1 + K2 <= 8) ? 8 : ceil_div(K1 + K2, 4) * 4;      // at least two k-steps; an odd count is fine
-    return launch_wino<4, 0, true>(x1, nullptr, U, bias, nullptr, nullptr, y, sel, N, K, H, W, rows, (int)ceil_div(rows, 32),
-                                   as_stream(stream), GenArgs{x2, (int)K1, (int)(K1 + K2), 1.0f, 0, 0, 0});
+    return launch_wino<Epi::BiasPool, Src::Dense, true>(x1, nullptr, U, bias, nullptr, nullptr, y, sel, N, padded_k(K1 + K2), H, W,
+                                                        rows, (int)ceil_div(rows, 32), as_stream(stream),
+                                                        GenArgs{x2, (int)K1, (int)(K1 + K2), 1.0f, 0, 0, 0});
 }
 
+// h: the activation's output, act: its sign bytes; at most one of them (neither: no activation factor)
 static int pooled_grad(const float *gy, const uint8_t *sel, const float *U, const float *h, const uint8_t *act, float slope,
                        float *g, int64_t N, int64_t K, int64_t rows, int64_t H, int64_t W, advstep_stream_t stream) {
     ADVSTEP_REQUIRE(N >= 0 && H >= 0 && W >= 0 && advstep_resconv_supported(K, 0, rows));
@@ -1009,18 +983,18 @@ static int pooled_grad(const float *gy, const uint8_t *sel, const float *U, cons
         return hipMemsetAsync(g, 0, (size_t)N * rows * H * W * sizeof(float), as_stream(stream)) == hipSuccess ? ADVSTEP_OK
                                                                                                                 : ADVSTEP_ELAUNCH;
     ADVSTEP_REQUIRE(gy && sel && U);
-    ADVSTEP_REQUIRE((uint64_t)N * K * (H / 2) * (W / 2) < (1ull << 29) && (uint64_t)N * rows * H * W * 4 < (1ull << 33) &&
-                    (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) < (1ull << 31));
-    const int64_t Kp = K <= 8 ? 8 : ceil_div(K, 4) * 4;
+    ADVSTEP_REQUIRE(wino_sizes_ok(N, H, W, 0, K, rows));
+    const int64_t Kp = padded_k(K);
+    const int slices = (int)ceil_div(rows, 32);
     const GenArgs ga{nullptr, (int)K, (int)K, slope, 0, 0, 0};
     if (act)
-        return launch_wino<6, 2, true>(gy, sel, U, nullptr, nullptr, nullptr, g, const_cast<uint8_t *>(act), N, Kp, H, W, rows,
-                                       (int)ceil_div(rows, 32), as_stream(stream), ga);
-    if (h)
-        return launch_wino<5, 2, true>(gy, sel, U, nullptr, h, nullptr, g, nullptr, N, Kp, H, W, rows, (int)ceil_div(rows, 32),
-                                       as_stream(stream), ga);
-    return launch_wino<0, 2, true>(gy, sel, U, nullptr, nullptr, nullptr, g, nullptr, N, Kp, H, W, rows, (int)ceil_div(rows, 32),
-                                   as_stream(stream), ga);
+        return launch_wino<Epi::LreluGradBytes, Src::Pooled, true>(gy, sel, U, nullptr, nullptr, nullptr, g, act, N, Kp, H, W, rows,
+                                                                   slices, as_stream(stream), ga);
+    if (h)      // in the `bn_mean` slot: see wino3x3_kernel
+        return launch_wino<Epi::LreluGradH, Src::Pooled, true>(gy, sel, U, nullptr, h, nullptr, g, nullptr, N, Kp, H, W, rows, slices,
+                                                               as_stream(stream), ga);
+    return launch_wino<Epi::Store, Src::Pooled, true>(gy, sel, U, nullptr, nullptr, nullptr, g, nullptr, N, Kp, H, W, rows, slices,
+                                                      as_stream(stream), ga);
 }
 
 int advstep_resconv_pool2_forward_few_f32(const float *x1, const float *x2, const float *U, const float *wd, const float *bias,
@@ -1030,9 +1004,10 @@ int advstep_resconv_pool2_forward_few_f32(const float *x1, const float *x2, cons
     if (N == 0 || H / 2 == 0 || W / 2 == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(sel && x2 && wd);
     if (const int st = resconv_check(x1, nullptr, U, y, N, K1, 0, rows, H, W)) return st;
-    const int64_t K = K1 <= 8 ? 8 : ceil_div(K1, 4) * 4;
-    return launch_wino<7, 0, true>(x1, nullptr, U, bias, wd, nullptr, y, sel, N, K, H, W, rows, (int)ceil_div(rows, 32),
-                                   as_stream(stream), GenArgs{x2, (int)K1, (int)K1, 1.0f, 0, (int)K2, 0});
+    // wd, the 1x1 weights, in the `bn_mean` slot: see wino3x3_kernel
+    return launch_wino<Epi::BiasPoolFew, Src::Dense, true>(x1, nullptr, U, bias, wd, nullptr, y, sel, N, padded_k(K1), H, W, rows,
+                                                           (int)ceil_div(rows, 32), as_stream(stream),
+                                                           GenArgs{x2, (int)K1, (int)K1, 1.0f, 0, (int)K2, 0});
 }
 
 int advstep_resconv_pooled_grad_f32(const float *gy, const uint8_t *sel, const float *U, const float *h, float slope, float *g,

@@ -461,3 +461,103 @@ def test_in_flight_defaults_and_cpu_lanes(monkeypatch):
     assert evaluation.default_in_flight(pgd, "cuda:0", False) == 1         # eager launches keep the host busy: nothing to overlap
     monkeypatch.setenv("ADVSTEP_IN_FLIGHT", "3")
     assert evaluation.default_in_flight(cw, "cuda:0", True) == 3
+
+
+# ---- csrc/lcnn_wino_plan.h: which launches one Winograd convolution becomes -------------------------------------------------
+
+_WINO_PLAN_PROBE = r"""
+#include <stdio.h>
+#include "lcnn_wino_plan.h"
+int main() {
+    int epi, src, gen, slices;
+    long long N, K, H, W, Cout;
+    while (scanf("%d %d %d %lld %lld %lld %lld %lld %d", &epi, &src, &gen, &N, &K, &H, &W, &Cout, &slices) == 9) {
+        const WinoPlan p = plan_wino((Epi)epi, (Src)src, gen != 0, N, K, H, W, Cout, slices, read_wino_knobs());
+        for (int i = 0; i < p.count; ++i) {
+            const WinoLaunch &l = p.launch[i];
+            printf("%d %d %d %d %d %d %d %d %zu;", l.NT, (int)l.stream, (int)l.wodd, l.halves, l.n_slices, l.slice0, l.ranges, l.xcd,
+                   l.lds);
+        }
+        printf("\n");
+    }
+    return 0;
+}
+"""
+
+
+def _wino_launches_before_the_plan(epi, src, gen, N, K, H, W, Cout, slices, env):
+    """What launch_wino launched before plan_wino existed, restated from that function: (NT, stream, wodd, halves, slices of the
+    launch, first slice, ranges, xcd, LDS bytes) per launch, in launch order."""
+    def cdiv(a, b):
+        return -(-a // b)
+
+    def off(name):
+        return env.get(name, "")[:1] == "0"
+    chunks = cdiv(K, 16)
+    stream = chunks > 4
+    groups = cdiv(N * ((H + 1) // 2) * ((W + 1) // 2), 16)
+    lds = ((4 if src == 1 else 2) if stream else chunks) * 16 * 16 * 32 * 4
+    wodd = src == 0 and W % 2 == 1
+    m = env.get("ADVSTEP_WINO_RANGE_MULT", "")[:1]
+    mult = int(m) if m and "1" <= m <= "8" else 1
+    out = []
+
+    def go(NT, halves, n_slices, slice0):
+        ranges = mult * 256 // n_slices
+        if ranges * 8 > groups:
+            ranges = cdiv(groups, 8)
+        ranges = max(ranges, 1)
+        xcd, r8 = 0, ranges & ~7
+        if not off("ADVSTEP_WINO_XCD") and n_slices > 1 and r8 >= 8 and cdiv(groups, r8 * 8) == cdiv(groups, ranges * 8):
+            ranges, xcd = r8, 1
+        out.append((NT, int(stream), int(wodd), halves, n_slices, slice0, ranges, xcd, lds))
+    full = slices
+    if epi in (0, 3, 5, 6) and Cout - (slices - 1) * 32 <= 16 and not off("ADVSTEP_WINO_HALF_SLICE"):
+        full = slices - 1
+        go(1, 0, 1, slices - 1)
+    if (epi == 0 and src == 1 and not gen and full == 1 and slices == 1 and Cout == 32 and groups <= 256 * 8 // 2
+            and not off("ADVSTEP_WINO_HALVES")):
+        go(1, 1, 2, 0)
+        return out
+    if full > 0:
+        go(2, 0, full, 0)
+    return out
+
+
+def test_wino_launch_plan_is_what_launch_wino_used_to_decide(tmp_path):
+    """plan_wino (plain host C++) against a restatement of the launch logic it replaced, for every epilogue / source pair the
+    library launches, at model shapes and at shapes where the range count is capped, under every setting of the four knobs it
+    reads: the half-empty last slice on its own, the two-halves launch, ranges rounded to a multiple of 8 with xcd set,
+    ADVSTEP_WINO_RANGE_MULT."""
+    import os
+    import shutil
+    import subprocess
+    from audio_deepfake_adversarial_attacks_amd import build as B
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    src_file, exe = tmp_path / "wino_plan_probe.cpp", tmp_path / "wino_plan_probe"
+    src_file.write_text(_WINO_PLAN_PROBE)
+    subprocess.run([hipcc, "--cuda-host-only", "-x", "hip", "-std=c++17", "-O0", f"-I{B.ROOT / 'include'}", f"-I{B.PKG / 'csrc'}",
+                    str(src_file), "-o", str(exe)], check=True, capture_output=True)
+    pairs = [(1, 0, 0), (2, 0, 0), (0, 0, 0), (0, 1, 0), (3, 0, 1), (4, 0, 1), (7, 0, 1), (0, 2, 1), (5, 2, 1), (6, 2, 1)]   # (Epi, Src, GEN)
+    shapes = [  # (N, K, H, W, Cout, slices)
+        (128, 32, 202, 40, 48, 3), (128, 128, 101, 20, 48, 2), (128, 64, 50, 10, 32, 1), (128, 96, 50, 10, 32, 1),
+        (129, 64, 50, 10, 32, 1), (128, 24, 80, 404, 20, 1), (128, 84, 20, 101, 64, 2), (128, 64, 5, 25, 64, 2),
+        (2, 64, 7, 10, 48, 2), (3, 128, 6, 9, 80, 3), (1, 8, 2, 2, 16, 1), (1, 256, 8, 6, 256, 8), (16, 20, 20, 101, 33, 2),
+    ]
+    cases = [(e, s, g) + sh for e, s, g in pairs for sh in shapes]
+    knobs = [{}, {"ADVSTEP_WINO_HALF_SLICE": "0"}, {"ADVSTEP_WINO_HALVES": "0"}, {"ADVSTEP_WINO_XCD": "0"},
+             {"ADVSTEP_WINO_RANGE_MULT": "2"}, {"ADVSTEP_WINO_RANGE_MULT": "4", "ADVSTEP_WINO_XCD": "0"},
+             {"ADVSTEP_WINO_RANGE_MULT": "9"}, {"ADVSTEP_WINO_HALVES": "1", "ADVSTEP_WINO_XCD": "1"}]
+    stdin = "".join(" ".join(map(str, c)) + "\n" for c in cases)
+    seen = set()
+    for env in knobs:
+        clean = {k: v for k, v in os.environ.items() if not k.startswith("ADVSTEP_WINO_")}
+        got = subprocess.run([str(exe)], input=stdin, env={**clean, **env}, check=True, capture_output=True, text=True).stdout
+        lines = got.splitlines()
+        assert len(lines) == len(cases)
+        for c, line in zip(cases, lines):
+            plan = [tuple(int(v) for v in part.split()) for part in line.split(";") if part]
+            assert plan == _wino_launches_before_the_plan(*c, env), (c, env)
+            seen.update((l[0], l[3], l[7]) for l in plan)
+    # the branches the cases are there for: one-tile last slice, the two halves, xcd placement, and plain two-tile launches
+    assert {(1, 0, 0), (1, 1, 0), (2, 0, 1), (2, 0, 0)} <= seen       # (NT, halves, xcd)

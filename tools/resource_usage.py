@@ -17,7 +17,9 @@ for line in out.splitlines():
     m = re.search(r"remark: Function Name: (\S+)", line)
     if m:
         cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-        cur = re.sub(r"\(.*", "", cur.replace("(anonymous namespace)::", "").replace("void ", ""))
+        cur = cur.replace("(anonymous namespace)::", "").replace("void ", "")
+        cur = re.sub(r"\(\w+\)(-?\d+)", r"\1", cur)          # enumeration template arguments as their values: (Epi)1 -> 1
+        cur = re.sub(r"\(.*", "", cur)
         rows[cur] = {}
         continue
     m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
