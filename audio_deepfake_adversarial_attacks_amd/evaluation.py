@@ -13,7 +13,8 @@ log line.  What is different is how the work is placed on the machine:
     :261-265); one D2H copy per run;
   * the final aggregate is the only communication: an all-reduce(SUM) of the two counters and one all-gather of
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
-    (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts).
+    (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
+    all-gather of the six per-utterance perturbation planes).
 """
 from __future__ import annotations
 
@@ -99,6 +100,17 @@ def aggregate_across_ranks(y_pred: torch.Tensor, y_pred_label: torch.Tensor, y: 
     return host[:, 0].astype(np.float32), host[:, 1].astype(np.int32), host[:, 2].astype(np.int64), int(c[0]), int(c[1])
 
 
+def gather_rows_across_ranks(rows: torch.Tensor) -> np.ndarray:
+    """This rank's (n_local, k) per-utterance rows on the compute device -> the whole job's (N, k) numpy array, ordered by
+    rank like the arrays of `aggregate_across_ranks` (one all-gather; every rank holds the same n_local: drop_last=True)."""
+    rows = rows.contiguous()
+    if rank_and_world()[1] > 1:
+        parts = [torch.empty_like(rows) for _ in range(rank_and_world()[1])]
+        dist.all_gather(parts, rows)
+        rows = torch.cat(parts, dim=0)
+    return rows.cpu().numpy()
+
+
 # ---------------------------------------------------------------------------------------------------------
 # per-batch body
 # ---------------------------------------------------------------------------------------------------------
@@ -121,6 +133,12 @@ def format_report(report: Dict[str, float]) -> str:
     """The reference's final log line (:295-298)."""
     order = ("eer", "accuracy", "precision", "recall", "f1_score", "auc")
     return ", ".join(f"adv_eval/{k}: {report['adv_eval/' + k]:.4f}" for k in order)
+
+
+def format_perturbation(report: Dict[str, float]) -> str:
+    """The second log line of a `perturbation_stats=True` run: the summary over all utterances (metrics.perturbation_summary)."""
+    keys = [k for k in report if k.startswith("perturbation/") and not k.startswith("perturbation/misclassified/")]
+    return ", ".join(f"{k}: {report[k]}" if k.endswith("nan_rows") else f"{k}: {report[k]:.4g}" for k in keys)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -296,6 +314,7 @@ def generate_attacks(
     return_scores: bool = False,
     on_batch_queued: Optional[Callable[[int], None]] = None,
     in_flight: Optional[int] = None,
+    perturbation_stats: bool = False,
 ) -> Dict[str, float]:
     """Reference signature (:146-157) plus additive keywords: `dataset` (a ready Dataset yielding the reference's
     4-tuple; without it the `DetectionDataset` over `datasets_paths` is built as in the reference's `get_dataset`,
@@ -307,7 +326,12 @@ def generate_attacks(
     per-utterance `y_pred`, `y_pred_label`, `y` arrays, in rank order, to the returned report under "scores") and
     `on_batch_queued(i)` (called when batch i's kernels have been queued, under the stream they were queued on — no
     synchronisation, no extra work: measurements) and `in_flight` (batches processed concurrently on streams of their own,
-    `_Lanes`; None = `default_in_flight`: 2 for the graph-replayed attacks, else 1; same scores either way).
+    `_Lanes`; None = `default_in_flight`: 2 for the graph-replayed attacks, else 1; same scores either way) and
+    `perturbation_stats` (one more row pass per batch, `hip_ops.perturbation_stats`, over the loop's own waveform-domain
+    tensors — the batch and what the detector is given after `revert_minmax`, so the min-max round trip's rounding of samples
+    the attack did not move is part of the figure; adds the `perturbation/*` keys of `metrics.perturbation_summary`, a
+    second log line and, with `return_scores`, the per-utterance planes under `scores["perturbation"]`; off: the report, the
+    launches of a batch and the log are exactly those of a run without the keyword).
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -360,7 +384,9 @@ def generate_attacks(
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
     seen_total = 0
-    y_pred, y_pred_label, y = [], [], []
+    y_pred, y_pred_label, y, perturbation = [], [], [], []
+    if perturbation_stats:
+        from . import hip_ops
 
     for i, (batch_x, batch_sr, batch_y, batch_metadata, ready) in enumerate(_device_batches(test_loader, device)):
       with lanes.batch(i, tuple(batch_x.shape), ready, (batch_x, batch_y)) as lane:
@@ -372,6 +398,9 @@ def generate_attacks(
         else:
             batch_x_attacked = torch.clone(batch_x)
         batch_x_noproc, batch_x_attacked_noproc = batch_x, batch_x_attacked  # :223-224 (nothing below writes in place)
+        if perturbation_stats:
+            perturbation.append(hip_ops.perturbation_stats(batch_x, batch_x_attacked))       # (6, B), on this lane's stream
+            lanes.keep(perturbation[-1])
 
         if raw_sample_from_dataset:  # :229-234 — the dataset's default preprocessing, after the attack
             batch_x_attacked, _ = SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(
@@ -413,15 +442,25 @@ def generate_attacks(
             dist.all_reduce(remaining, op=dist.ReduceOp.SUM)     # next to the counters' all-reduce: (n_members + 1) int64
         remaining = remaining.tolist()
 
+    if perturbation_stats:
+        planes = gather_rows_across_ranks(torch.cat(perturbation, dim=1).t()).T                    # (6, N), rank order
+        planes = {name: np.ascontiguousarray(planes[k], dtype=np.float32) for k, name in enumerate(metrics.PERTURBATION_PLANES)}
+
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
     if return_scores:
         report["scores"] = {"y_pred": all_pred, "y_pred_label": all_label, "y": all_y}
+    if perturbation_stats:
+        report.update(metrics.perturbation_summary(planes, all_label != all_y))
+        if return_scores:
+            report["scores"]["perturbation"] = planes
     if multi is not None:
         report["multi_attack/remaining"] = remaining
     if rank == 0:
         if multi is not None:
             LOGGER.info(multi._return_sr_record(remaining))
         LOGGER.info(format_report(report))
+        if perturbation_stats:
+            LOGGER.info(format_perturbation(report))
     return report

@@ -15,6 +15,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   ce2_loss_grad                      .../attacks/pgd.py:62,50,68 (and the same lines of fgsm.py / pgdl2.py)
   mi_step / vt_*                     .../attacks/mifgsm.py:70-76, nifgsm.py:56,67-71, vmifgsm.py:77-101
   multi_route                        .../attacks/multiattack.py:55-66
+  perturbation_stats                 src/aa/qualitative/attacks_postanalysis.py (the distortion figures beside the WAV pairs)
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .metrics import PERTURBATION_PLANES  # noqa: F401  (re-exported: the planes of perturbation_stats)
 
 NAME = "hip"
 
@@ -30,7 +32,7 @@ NAME = "hip"
 # plumbing
 # ---------------------------------------------------------------------------------------------------------
 
-_workspaces: Dict[Tuple[int, int, int, int], torch.Tensor] = {}     # (device, stream handle, B, T) -> row-reduction scratch
+_workspaces: Dict[tuple, torch.Tensor] = {}     # (device, stream handle, B, T) -> row-reduction scratch; (..., "perturb") -> perturbation_stats' partials
 _profile: Optional[Dict[str, List[Tuple[torch.cuda.Event, torch.cuda.Event]]]] = None
 _profile_work: Dict[str, List[float]] = {}      # per bracketed launch: the arithmetic the caller says it did (flop), or 0
 _profile_bytes: Dict[str, List[float]] = {}     # per bracketed launch: the bytes of the operands the caller named, or 0
@@ -83,11 +85,16 @@ def _workspace(device: torch.device, B: int, T: int) -> Tuple[int, int]:
     # was allocated and only ever used on the stream of its key, so the caching allocator re-issues its memory in stream order;
     # a captured graph OWNS the buffers it baked in (`release_stream_workspaces`), they are not in this table any more.
     key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(device), int(B), int(T))
+    # zero-filled ONCE: epoch 0, no row flagged (include/advstep.h)
+    return _scratch(key, lambda: torch.zeros(max(_lib.load().advstep_row_workspace_bytes(B, T), 256), dtype=torch.uint8,
+                                             device=device))
+
+
+def _scratch(key: tuple, alloc) -> Tuple[int, int]:
+    """The table's buffer of `key` = (device, stream handle, ...) as (pointer, bytes), allocated by `alloc` on a miss."""
     ws = _workspaces.pop(key, None)
     if ws is None:
-        need = _lib.load().advstep_row_workspace_bytes(B, T)
-        # zero-filled ONCE: epoch 0, no row flagged (include/advstep.h)
-        ws = torch.zeros(max(need, 256), dtype=torch.uint8, device=device)
+        ws = alloc()
         while len(_workspaces) >= _WORKSPACE_SLOTS:
             _workspaces.pop(next(iter(_workspaces)))                 # least recently used first (dicts keep insertion order)
     _workspaces[key] = ws                                            # (re-)inserted last = most recently used
@@ -751,3 +758,36 @@ def multi_route(adv, x, z, labels, rows, final, next_x=None, next_y=None, next_r
                                                  counts.data_ptr(), scratch.data_ptr(), n, B, T, _stream(adv.device))
     _lib.check(st, "advstep_multi_route_f32")
     return next_x, next_y, next_rows, counts
+
+
+# ---------------------------------------------------------------------------------------------------------
+# per-utterance perturbation report (include/advstep_perturb.h)
+# ---------------------------------------------------------------------------------------------------------
+
+# PERTURBATION_PLANES (imported above from the numpy-only metrics module): the rows of perturbation_stats' result, in order
+
+
+def perturbation_stats(x, adv, out=None):
+    """(6, B) float32, one row per name of PERTURBATION_PLANES, of d = adv - x per utterance: max |d|, mean |d|, ||d||_2,
+    sum x^2, 10 log10(sum x^2 / sum d^2) and the segmental SNR over full 256-sample segments, each clamped to [-10, 35] dB
+    (definitions and corner cases: include/advstep_perturb.h).  One read of x and adv, two launches on the current stream,
+    no synchronisation; reruns are bit-identical."""
+    _require(x, "x"), _require(adv, "adv")
+    _same_shape(("x", x), ("adv", adv))
+    B, T = _rows(x, "x")
+    if out is None:
+        out = torch.empty((len(PERTURBATION_PLANES), B), dtype=torch.float32, device=x.device)
+    _require(out, "out")
+    if out.shape != (len(PERTURBATION_PLANES), B) or out.device != x.device:
+        raise ValueError(f"out must be ({len(PERTURBATION_PLANES)}, {B}) on {x.device}, got {tuple(out.shape)}@{out.device}")
+    lib = _lib.load()
+    with _Launch("perturbation_stats", x.device, tensors=(x, adv)):
+        # partials only, rewritten by every call: keyed by stream like the row workspace (two lanes never share one), and
+        # handed to a captured graph by release_stream_workspaces with the rest of its stream's buffers
+        key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), _stream(x.device), int(B), int(T),
+               "perturb")
+        ws, ws_bytes = _scratch(key, lambda: torch.empty(max(lib.advstep_perturb_stats_workspace_bytes(B, T), 256),
+                                                         dtype=torch.uint8, device=x.device))
+        st = lib.advstep_perturb_stats_f32(x.data_ptr(), adv.data_ptr(), out.data_ptr(), ws, ws_bytes, B, T, _stream(x.device))
+    _lib.check(st, "advstep_perturb_stats_f32")
+    return out

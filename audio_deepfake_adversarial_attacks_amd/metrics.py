@@ -1,8 +1,9 @@
 """Final aggregate of the evaluation loop (reference: src/metrics.py:9-14 and the sklearn calls of
 evaluate_models_on_adversarial_attacks.py:267-293), restated in numpy so the GPU box needs neither sklearn nor
 scipy.  Each function documents the library routine it reproduces; tests pin them against values the
-reference's own calls produced (tests/golden/metrics.npz)."""
-from typing import Tuple
+reference's own calls produced (tests/golden/metrics.npz).  `perturbation_summary` is this package's own: the run-level
+digest of the per-utterance perturbation report (include/advstep_perturb.h)."""
+from typing import Dict, Tuple
 
 import numpy as np
 
@@ -121,3 +122,42 @@ def adversarial_report(y: np.ndarray, y_pred: np.ndarray, y_pred_label: np.ndarr
     _, eer, _, _ = calculate_eer(y=1 - y, y_score=y_pred)  # "For EER flip values" (:282-283)
     return {"adv_eval/eer": eer, "adv_eval/accuracy": accuracy, "adv_eval/precision": precision,
             "adv_eval/recall": recall, "adv_eval/f1_score": f1, "adv_eval/auc": auc}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# perturbation report
+# ---------------------------------------------------------------------------------------------------------
+
+# the planes of hip_ops.perturbation_stats, in the order of include/advstep_perturb.h
+PERTURBATION_PLANES = ("linf", "l1_mean", "l2", "energy", "snr_db", "seg_snr_db")
+# (key, plane, statistic) of the summary; the same eight once more under perturbation/misclassified/
+_PERTURBATION_SUMMARY = (("linf_max", "linf", np.max), ("linf_mean", "linf", np.mean),
+                         ("l2_mean", "l2", np.mean), ("l2_median", "l2", np.median),
+                         ("snr_db_median", "snr_db", np.median), ("snr_db_min", "snr_db", np.min),
+                         ("seg_snr_db_mean", "seg_snr_db", np.mean), ("seg_snr_db_min", "seg_snr_db", np.min))
+
+
+def perturbation_summary(stats, misclassified) -> Dict[str, float]:
+    """Run-level digest of the per-utterance perturbation planes.  `stats`: {plane name: (N,) array} or a (6, N) array in the
+    order of PERTURBATION_PLANES; `misclassified`: (N,) bool, the utterances whose post-attack label differs from y.
+
+    A row with a NaN in any of the four summarised planes (linf, l2, snr_db, seg_snr_db) is a NaN row: it is left out of every
+    statistic, of both groups, and counted in perturbation/nan_rows.  Infinite SNRs (an utterance the attack did not move:
+    +inf) take part as they are, so a median stays finite while most rows are finite.  A group without rows — no
+    misclassified utterance, or NaN rows only — has NaN for every value."""
+    if not isinstance(stats, dict):
+        stats = dict(zip(PERTURBATION_PLANES, np.asarray(stats)))
+    planes = {name: np.asarray(stats[name], dtype=np.float64).ravel() for _, name, _ in _PERTURBATION_SUMMARY}
+    wrong = np.asarray(misclassified).ravel().astype(bool)
+    nan_row = np.zeros(wrong.shape, dtype=bool)
+    for v in planes.values():
+        if v.shape != wrong.shape:
+            raise ValueError(f"planes and misclassified must hold one value per utterance, got {v.shape} and {wrong.shape}")
+        nan_row |= np.isnan(v)
+    out: Dict[str, float] = {}
+    with np.errstate(invalid="ignore"):                  # a median between +inf and -inf is NaN, quietly
+        for prefix, rows in (("perturbation/", ~nan_row), ("perturbation/misclassified/", ~nan_row & wrong)):
+            for key, name, stat in _PERTURBATION_SUMMARY:
+                out[prefix + key] = float(stat(planes[name][rows])) if rows.any() else float("nan")
+    out["perturbation/nan_rows"] = int(nan_row.sum())
+    return out

@@ -73,6 +73,10 @@ def parse_arguments(argv=None):
                              "iteration replays from a hipGraph - PGD, PGDL2 -, else 1; same scores either way)")
     parser.add_argument("--share_weights", default=False, action="store_true",
                         help="copy the target model's weights into the attack model (white-box, no checkpoints)")
+    parser.add_argument("--perturbation_stats", default=False, action="store_true",
+                        help="report how large the perturbation is per utterance (L-inf, L2, SNR and segmental SNR in dB of the "
+                             "waveform the detector is given): perturbation/* keys and a second log line; with --qual also "
+                             "perturbation_metrics.csv beside the WAV pairs")
     return parser.parse_args(argv)
 
 
@@ -104,7 +108,7 @@ def main(args):
         results_folder = f"attack_{args.attack}_{Path(args.attack_model_config).stem}_on_{Path(args.config).stem}"
         if world > 1:   # one folder per rank: ranks analyse disjoint shards and must not overwrite each other's files
             results_folder = f"{results_folder}/rank{int(os.environ.get('RANK', '0'))}"
-        attack_analyser = AttackAnalyser(Path("qualitative_results") / results_folder)
+        attack_analyser = AttackAnalyser(Path("qualitative_results") / results_folder, stats_csv=args.perturbation_stats)
         on_attack_end_callback = attack_analyser.analyse
     corpora = [args.asv_path, args.wavefake_path, args.celeb_path]
     if args.synthetic is None and all(p is None for p in corpora):
@@ -129,6 +133,7 @@ def main(args):
         wave_fake_trim=False if args.no_trim else None,
         num_workers=args.num_workers,
         in_flight=args.in_flight,
+        perturbation_stats=args.perturbation_stats,
     )
     if world > 1:
         dist.destroy_process_group()
