@@ -77,4 +77,12 @@ class AttackEnum(Enum):
 
     WORSTCASE40_eps003 = (torchattacks.MultiAttack.on_model, _worst_case_linf(0.003, steps=40, apgd_steps=100))  # PGD40_eps003's radius
 
+    # --- additive members: the radius at which each utterance breaks, in one run (torchattacks.MinRadiusPGD: a bisection per
+    # utterance on [0, eps_max]); report_at = the radii of the PGD / PGDL2 triplets above, whose robust accuracies the run reports ---
+    MINRADIUS = (torchattacks.MinRadiusPGD, {"norm": "Linf", "eps_max": 0.001, "search_steps": 6, "steps": 10,
+                                             "report_at": (0.0005, 0.00075, 0.001)})
+    MINRADIUS_L2 = (torchattacks.MinRadiusPGD, {"norm": "L2", "eps_max": 0.2, "search_steps": 6, "steps": 10,
+                                                "report_at": (0.1, 0.15, 0.2)})
+    MINRADIUS40_eps003 = (torchattacks.MinRadiusPGD, {"norm": "Linf", "eps_max": 0.003, "search_steps": 8, "steps": 40})  # PGD40_eps003's radius
+
     NO_ATTACK = (None, {})

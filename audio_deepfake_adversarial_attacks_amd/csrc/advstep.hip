@@ -277,26 +277,11 @@ __global__ __launch_bounds__(kWgThreads) void minmax_revert_kernel(const float *
     store_tile<VEC>(out + b * T, T, tile, r);
 }
 
-// ---- row sum of squares (||grad||^2, ||normal||^2) ------------------------------------------------------------
-
-template <bool VEC>
-__global__ __launch_bounds__(kWgThreads) void sumsq_partial_kernel(const float *__restrict__ g, int64_t T,
-                                                               float *__restrict__ part) {
-    __shared__ float lds[4];
-    const int tile = blockIdx.x, C = gridDim.x;
-    const int64_t b = blockIdx.y;
-    float4 r[kVecs];
-    load_tile<VEC>(g + b * T, T, tile, 0.0f, r);
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) s += (r[j].x * r[j].x + r[j].y * r[j].y) + (r[j].z * r[j].z + r[j].w * r[j].w);
-    s = wg_sum(s, lds);
-    if (threadIdx.x == 0) part[b * C + tile] = s;
-}
+// (the row sum of squares, sumsq_partial_kernel, is row_tiles.h's: radius.hip launches it too)
 
 // ---- a6: PGD-L2 step ------------------------------------------------------------------------------------------
 
-// pass 2: gn from the grad partials; a = adv + alpha * (g / gn); d = a - orig; partial sum d^2
+// pass 2 and pass 3: the bodies are row_tiles.h's (radius.hip runs them with a radius per row)
 template <bool VEC>
 __global__ __launch_bounds__(kWgThreads) void pgd_l2_delta_kernel(const float *__restrict__ adv,
                                                               const float *__restrict__ grad,
@@ -304,38 +289,9 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_delta_kernel(const float *_
                                                               float eps_div, const float *__restrict__ gpart,
                                                               float *__restrict__ dpart, float *__restrict__ gnorm) {
     __shared__ float lds[8];
-    const int tile = blockIdx.x, C = gridDim.x;
-    const int64_t b = blockIdx.y;
-    float4 a[kVecs], g[kVecs], x[kVecs];
-    load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
-    load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
-    load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
-    const float gsq = row_sum(gpart + b * C, C, lds);
-    const float gn_raw = sqrtf(gsq);
-    const float gn = gn_raw + eps_div;
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        float4 d;
-        d.x = (a[j].x + alpha * (g[j].x / gn)) - x[j].x;
-        d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
-        d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
-        d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-        // out-of-row lanes: a = g = x = 0 -> d = 0 when gn != 0; mask explicitly so gn == 0 / NaN cannot leak
-        if (!in_row(T, quad_of(tile, j), 0)) d.x = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 1)) d.y = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 2)) d.z = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 3)) d.w = 0.0f;
-        s += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-    }
-    s = wg_sum(s, lds + 4);
-    if (threadIdx.x == 0) {
-        dpart[b * C + tile] = s;
-        if (tile == 0 && gnorm) gnorm[b] = gn_raw;
-    }
+    l2_delta_pass<VEC>(adv, grad, orig, T, alpha, eps_div, gpart, dpart, gnorm, lds);
 }
 
-// pass 3: recompute d, f = min((1/dn) * eps, 1), out = clamp(orig + d * f, lo, hi)
 template <bool VEC>
 __global__ __launch_bounds__(kWgThreads) void pgd_l2_project_kernel(const float *__restrict__ adv,
                                                                 const float *__restrict__ grad,
@@ -345,29 +301,7 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_project_kernel(const float 
                                                                 const float *__restrict__ dpart,
                                                                 float *__restrict__ dnorm) {
     __shared__ float lds[8];
-    const int tile = blockIdx.x, C = gridDim.x;
-    const int64_t b = blockIdx.y;
-    float4 a[kVecs], g[kVecs], x[kVecs];
-    load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
-    load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
-    load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
-    const float gn = sqrtf(row_sum(gpart + b * C, C, lds)) + eps_div;
-    const float dn = sqrtf(row_sum(dpart + b * C, C, lds + 4));
-    const float f = min_nan((1.0f / dn) * eps, 1.0f);
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        float4 d;
-        d.x = (a[j].x + alpha * (g[j].x / gn)) - x[j].x;
-        d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
-        d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
-        d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-        a[j].x = clampf(x[j].x + d.x * f, lo, hi);
-        a[j].y = clampf(x[j].y + d.y * f, lo, hi);
-        a[j].z = clampf(x[j].z + d.z * f, lo, hi);
-        a[j].w = clampf(x[j].w + d.w * f, lo, hi);
-    }
-    store_tile<VEC>(out + b * T, T, tile, a);
-    if (tile == 0 && threadIdx.x == 0 && dnorm) dnorm[b] = dn;
+    l2_project_pass<VEC, false>(adv, grad, orig, out, T, alpha, eps, eps_div, lo, hi, gpart, dpart, dnorm, lds);
 }
 
 

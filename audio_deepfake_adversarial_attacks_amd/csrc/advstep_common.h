@@ -49,6 +49,11 @@ inline bool overlaps(const void *a, const void *b, size_t bytes) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + bytes && y < x + bytes;
 }
+// ... and for two buffers of different sizes (multiattack.hip, radius.hip)
+inline bool overlap2(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return p < q + b_bytes && q < p + a_bytes;
+}
 
 // ---- the row workspace of include/advstep.h (ABI 3): advstep.hip, apgd.hip and momentum.hip carve the same buffer ----------
 

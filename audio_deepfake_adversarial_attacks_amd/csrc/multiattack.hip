@@ -70,11 +70,6 @@ __global__ __launch_bounds__(kWgThreads) void multi_copy_kernel(const float *__r
     store_tile<VEC>(dst, T, tile, r);
 }
 
-inline bool overlap2(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-    return p < q + b_bytes && q < p + a_bytes;
-}
-
 }  // namespace
 
 extern "C" int advstep_multi_route_f32(const float *adv, const float *x, const float *z, const int64_t *labels,

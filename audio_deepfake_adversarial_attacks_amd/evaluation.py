@@ -14,7 +14,8 @@ log line.  What is different is how the work is placed on the machine:
   * the final aggregate is the only communication: an all-reduce(SUM) of the two counters and one all-gather of
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
     (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
-    all-gather of the six per-utterance perturbation planes).
+    all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD — one
+    all-gather of the per-utterance radii).
 """
 from __future__ import annotations
 
@@ -139,6 +140,11 @@ def format_perturbation(report: Dict[str, float]) -> str:
     """The second log line of a `perturbation_stats=True` run: the summary over all utterances (metrics.perturbation_summary)."""
     keys = [k for k in report if k.startswith("perturbation/") and not k.startswith("perturbation/misclassified/")]
     return ", ".join(f"{k}: {report[k]}" if k.endswith("nan_rows") else f"{k}: {report[k]:.4g}" for k in keys)
+
+
+def format_min_radius(report: Dict[str, float]) -> str:
+    """The log line of a run whose attack carries `last_radius` (MinRadiusPGD): the summary of metrics.radius_summary."""
+    return ", ".join(f"{k}: {v:.4g}" for k, v in report.items() if k.startswith("min_radius/"))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -332,6 +338,9 @@ def generate_attacks(
     the attack did not move is part of the figure; adds the `perturbation/*` keys of `metrics.perturbation_summary`, a
     second log line and, with `return_scores`, the per-utterance planes under `scores["perturbation"]`; off: the report, the
     launches of a batch and the log are exactly those of a run without the keyword).
+    An attack that carries `last_radius` (torchattacks.MinRadiusPGD: each utterance's minimal radius, on the device) adds the
+    `min_radius/*` keys of `metrics.radius_summary` at the attack's `report_at`, one more log line and, with `return_scores`,
+    the per-utterance radii under `scores["min_radius"]` (utterance order, like `y_pred`); any other attack: nothing.
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -384,7 +393,8 @@ def generate_attacks(
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
     seen_total = 0
-    y_pred, y_pred_label, y, perturbation = [], [], [], []
+    y_pred, y_pred_label, y, perturbation, radii = [], [], [], [], []
+    has_radius = atk is not None and hasattr(atk, "last_radius")
     if perturbation_stats:
         from . import hip_ops
 
@@ -395,6 +405,9 @@ def generate_attacks(
 
         if attack_model is not None:
             batch_x_attacked = attack_batch(atk, batch_x, batch_y)
+            if has_radius:
+                radii.append(atk.last_radius)                      # (B,), on this lane's stream; read after join()
+                lanes.keep(radii[-1])
         else:
             batch_x_attacked = torch.clone(batch_x)
         batch_x_noproc, batch_x_attacked_noproc = batch_x, batch_x_attacked  # :223-224 (nothing below writes in place)
@@ -446,6 +459,9 @@ def generate_attacks(
         planes = gather_rows_across_ranks(torch.cat(perturbation, dim=1).t()).T                    # (6, N), rank order
         planes = {name: np.ascontiguousarray(planes[k], dtype=np.float32) for k, name in enumerate(metrics.PERTURBATION_PLANES)}
 
+    if has_radius:
+        all_radii = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(radii).reshape(-1, 1))[:, 0], dtype=np.float32)
+
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
@@ -455,6 +471,10 @@ def generate_attacks(
         report.update(metrics.perturbation_summary(planes, all_label != all_y))
         if return_scores:
             report["scores"]["perturbation"] = planes
+    if has_radius:
+        report.update(metrics.radius_summary(all_radii, getattr(atk, "report_at", ())))
+        if return_scores:
+            report["scores"]["min_radius"] = all_radii
     if multi is not None:
         report["multi_attack/remaining"] = remaining
     if rank == 0:
@@ -463,4 +483,6 @@ def generate_attacks(
         LOGGER.info(format_report(report))
         if perturbation_stats:
             LOGGER.info(format_perturbation(report))
+        if has_radius:
+            LOGGER.info(format_min_radius(report))
     return report

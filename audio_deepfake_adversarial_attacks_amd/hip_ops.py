@@ -16,6 +16,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   mi_step / vt_*                     .../attacks/mifgsm.py:70-76, nifgsm.py:56,67-71, vmifgsm.py:77-101
   multi_route                        .../attacks/multiattack.py:55-66
   perturbation_stats                 src/aa/qualitative/attacks_postanalysis.py (the distortion figures beside the WAV pairs)
+  row_pgd_*_step / radius_*          no counterpart: the per-row radius steps and the bisection of torchattacks.MinRadiusPGD
 """
 from __future__ import annotations
 
@@ -790,4 +791,102 @@ def perturbation_stats(x, adv, out=None):
                                                          dtype=torch.uint8, device=x.device))
         st = lib.advstep_perturb_stats_f32(x.data_ptr(), adv.data_ptr(), out.data_ptr(), ws, ws_bytes, B, T, _stream(x.device))
     _lib.check(st, "advstep_perturb_stats_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# minimal-radius search (include/advstep_radius.h): PGD steps with a radius per row, and the bisection's bookkeeping
+# ---------------------------------------------------------------------------------------------------------
+
+RADIUS_PLANES = ("lo", "hi", "eps", "best")     # the rows of a search state, in the order of include/advstep_radius.h
+
+
+def _radius_state(t: torch.Tensor, name: str, B: int, device) -> torch.Tensor:
+    _require(t, name)
+    if t.shape != (len(RADIUS_PLANES), B) or t.device != device:
+        raise ValueError(f"{name} must be ({len(RADIUS_PLANES)}, {B}) on {device}, got {tuple(t.shape)}@{t.device}")
+    return t
+
+
+def row_pgd_linf_step(adv, grad, orig, eps_rows, alpha_abs: float, alpha_rel: float, lo: float = 0.0, hi: float = 1.0,
+                      out=None):
+    """pgd_linf_step with a radius per row: e = eps_rows[b], a = alpha_abs + alpha_rel * e,
+    out = clamp(orig + clamp((adv + a * sign(grad)) - orig, -e, e), lo, hi).  `out` may be `adv`."""
+    _require(adv, "adv"), _require(grad, "grad"), _require(orig, "orig")
+    _same_shape(("adv", adv), ("grad", grad), ("orig", orig))
+    B, T = _rows(adv, "adv")
+    _per_row(eps_rows, "eps_rows", B)
+    out = _out_like(adv, out)
+    with _Launch("row_pgd_linf_step", adv.device, tensors=(adv, grad, orig, out)):
+        st = _lib.load().advstep_row_pgd_linf_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), eps_rows.data_ptr(),
+                                                       alpha_abs, alpha_rel, lo, hi, out.data_ptr(), B, T, _stream(adv.device))
+    _lib.check(st, "advstep_row_pgd_linf_step_f32")
+    return out
+
+
+def row_pgd_l2_step(adv, grad, orig, eps_rows, alpha_abs: float, alpha_rel: float, eps_div: float = 1e-10, lo: float = 0.0,
+                    hi: float = 1.0, out=None, return_norms: bool = False):
+    """pgd_l2_step (three launches) with a radius per row: e = eps_rows[b], a = alpha_abs + alpha_rel * e; a row whose
+    step leaves it where `orig` is (||d|| = 0) comes back as clamp(orig), also at e = 0.  `out` may be `adv`."""
+    _require(adv, "adv"), _require(grad, "grad"), _require(orig, "orig")
+    _same_shape(("adv", adv), ("grad", grad), ("orig", orig))
+    B, T = _rows(adv, "adv")
+    _per_row(eps_rows, "eps_rows", B)
+    out = _out_like(adv, out)
+    gn = dn = None
+    if return_norms:
+        gn = torch.empty(B, dtype=torch.float32, device=adv.device)
+        dn = torch.empty(B, dtype=torch.float32, device=adv.device)
+    # compulsory traffic: grad three times, adv and orig twice, out once
+    with _Launch("row_pgd_l2_step", adv.device, tensors=(grad,) * 3 + (adv,) * 2 + (orig,) * 2 + (out,)):
+        ws, ws_bytes = _workspace(adv.device, B, T)
+        st = _lib.load().advstep_row_pgd_l2_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), eps_rows.data_ptr(),
+                                                     alpha_abs, alpha_rel, eps_div, lo, hi, out.data_ptr(),
+                                                     gn.data_ptr() if return_norms else None,
+                                                     dn.data_ptr() if return_norms else None, B, T, ws, ws_bytes,
+                                                     _stream(adv.device))
+    _lib.check(st, "advstep_row_pgd_l2_step_f32")
+    return (out, gn, dn) if return_norms else out
+
+
+def radius_begin(z0, labels, eps_max: float, state=None):
+    """The search state (4, B) = lo, hi, eps, best (RADIUS_PLANES) from the clean logits: a row the model already gets wrong
+    ((z0 > 0) != label) starts and stays at radius 0 with best = 0; every other row starts at eps_max with best = +inf."""
+    _require(z0, "z0")
+    B = z0.numel()
+    _per_row(labels, "labels", B, torch.int64)
+    if not float(eps_max) >= 0.0:
+        raise ValueError(f"eps_max must be a radius >= 0, got {eps_max}")
+    if state is None:
+        state = torch.empty((len(RADIUS_PLANES), B), dtype=torch.float32, device=z0.device)
+    _radius_state(state, "state", B, z0.device)
+    with _Launch("radius_begin", z0.device):
+        st = _lib.load().advstep_radius_begin_f32(z0.data_ptr(), labels.data_ptr(), eps_max, state.data_ptr(), B,
+                                                  _stream(z0.device))
+    _lib.check(st, "advstep_radius_begin_f32")
+    return state
+
+
+def radius_round(adv, z, labels, first: bool, state, best_adv, out=None):
+    """One round of the bisection after the attempt `adv` at the radii state[2] was judged (z = the logit of model(adv)):
+    flipped and eps < best -> best = hi = eps and the row is copied into best_adv; not flipped -> lo = eps and the row is
+    copied iff `first`; then eps = (lo + hi) / 2.  Returns the NEW state, written to `out` (another (4, B) buffer than `state`:
+    the launch only reads `state`); best_adv is updated in place.  One launch, no host read.  Empty work (B == 0 or rows of no
+    samples) launches nothing and writes nothing, `out` included, as the library defines it."""
+    _require(adv, "adv"), _require(z, "z"), _require(best_adv, "best_adv")
+    _same_shape(("adv", adv), ("best_adv", best_adv))
+    B, T = _rows(adv, "adv")
+    if z.numel() != B or z.device != adv.device:
+        raise ValueError(f"z must hold one logit per row of adv ({B}) on {adv.device}, got {tuple(z.shape)}@{z.device}")
+    _per_row(labels, "labels", B, torch.int64)
+    _radius_state(state, "state", B, adv.device)
+    if out is None:
+        out = torch.empty_like(state)
+    _radius_state(out, "out", B, adv.device)
+    # compulsory traffic: at most one read and one write of every row (only the rows that improve move)
+    with _Launch("radius_round", adv.device, tensors=(adv, best_adv)):
+        st = _lib.load().advstep_radius_round_f32(adv.data_ptr(), z.data_ptr(), labels.data_ptr(), 1 if first else 0,
+                                                  state.data_ptr(), out.data_ptr(), best_adv.data_ptr(), B, T,
+                                                  _stream(adv.device))
+    _lib.check(st, "advstep_radius_round_f32")
     return out

@@ -2,8 +2,9 @@
 evaluate_models_on_adversarial_attacks.py:267-293), restated in numpy so the GPU box needs neither sklearn nor
 scipy.  Each function documents the library routine it reproduces; tests pin them against values the
 reference's own calls produced (tests/golden/metrics.npz).  `perturbation_summary` is this package's own: the run-level
-digest of the per-utterance perturbation report (include/advstep_perturb.h)."""
-from typing import Dict, Tuple
+digest of the per-utterance perturbation report (include/advstep_perturb.h); so is `radius_summary`, the digest of the
+per-utterance minimal radii of torchattacks.MinRadiusPGD."""
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 
@@ -160,4 +161,51 @@ def perturbation_summary(stats, misclassified) -> Dict[str, float]:
             for key, name, stat in _PERTURBATION_SUMMARY:
                 out[prefix + key] = float(stat(planes[name][rows])) if rows.any() else float("nan")
     out["perturbation/nan_rows"] = int(nan_row.sum())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# minimal-radius report
+# ---------------------------------------------------------------------------------------------------------
+
+def _quantile_keeping_inf(ordered: np.ndarray, q: float) -> float:
+    """The q-quantile of an ascending vector by linear interpolation between order statistics (numpy's default), with
+    +inf taking part as a value: the result is +inf as soon as the upper neighbour carries weight and is +inf (numpy's own
+    interpolation would turn inf - inf into NaN)."""
+    pos = q * (len(ordered) - 1)
+    i = int(np.floor(pos))
+    frac = pos - i
+    lo, hi = float(ordered[i]), float(ordered[min(i + 1, len(ordered) - 1)])
+    if frac == 0.0 or lo == hi:
+        return lo
+    if np.isinf(hi):
+        return hi
+    return lo + (hi - lo) * frac
+
+
+def radius_summary(radii, report_at: Sequence[float] = ()) -> Dict[str, float]:
+    """Run-level digest of the per-utterance minimal radii of torchattacks.MinRadiusPGD (`last_radius`: 0 = the clean input is
+    already misclassified, +inf = no radius up to eps_max flipped the utterance, in the attack's domain: the min-max-normalised
+    waveform).
+
+    min_radius/median, p10, p90      quantiles over ALL rows; +inf stays +inf (more than half unflipped: the median is +inf)
+    min_radius/unflipped_share       the share of +inf rows, in [0, 1]
+    min_radius/already_wrong_share   the share of rows with radius 0
+    min_radius/robust_acc@<eps>      100 x the share of rows whose radius is > eps, for every eps of report_at, compared as
+                                     float32 (the precision of the search state, so a radius that IS the grid point eps
+                                     counts as broken at eps): the accuracy a PGD run at radius eps would leave, were success
+                                     monotone in the radius (an upper bound otherwise: the radii are witnessed, not minimal)
+    An empty vector gives NaN everywhere."""
+    r32 = np.sort(np.asarray(radii, dtype=np.float32).ravel())
+    r = r32.astype(np.float64)
+    n = r.size
+    out: Dict[str, float] = {}
+    for key, q in (("median", 0.5), ("p10", 0.1), ("p90", 0.9)):
+        out[f"min_radius/{key}"] = _quantile_keeping_inf(r, q) if n else float("nan")
+    out["min_radius/unflipped_share"] = float(np.mean(np.isinf(r))) if n else float("nan")
+    out["min_radius/already_wrong_share"] = float(np.mean(r == 0.0)) if n else float("nan")
+    for eps in report_at:
+        # in the radii's own precision: the search's grid points are float32 (float32(0.001) > 0.001 as a float64), and a row
+        # that flipped AT eps is not robust at eps
+        out[f"min_radius/robust_acc@{eps:g}"] = 100.0 * float(np.mean(r32 > np.float32(eps))) if n else float("nan")
     return out

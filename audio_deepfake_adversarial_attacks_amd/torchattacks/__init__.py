@@ -2,8 +2,8 @@
 
 The attacks the north-star path names — FGSM, PGD, PGDL2, CW — FAB (the attack that completes the
 reference's AttackEnum), APGD (the step-size-free gradient attack of AutoAttack) and the momentum attacks made for
-transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms) and MultiAttack (the worst case over a list
-of them), with the reference's constructor
+transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), MultiAttack (the worst case over a list
+of them) and MinRadiusPGD (each utterance's minimal radius, by bisection on the device), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -11,6 +11,7 @@ from .attacks.cw import CW
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
 from .attacks.mifgsm import MIFGSM
+from .attacks.minradius import MinRadiusPGD
 from .attacks.multiattack import MultiAttack
 from .attacks.nifgsm import NIFGSM
 from .attacks.pgd import PGD
@@ -20,4 +21,4 @@ from .attacks.vnifgsm import VNIFGSM
 
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
-           "MultiAttack"]
+           "MultiAttack", "MinRadiusPGD"]
