@@ -85,4 +85,14 @@ class AttackEnum(Enum):
                                                 "report_at": (0.1, 0.15, 0.2)})
     MINRADIUS40_eps003 = (torchattacks.MinRadiusPGD, {"norm": "Linf", "eps_max": 0.003, "search_steps": 8, "steps": 40})  # PGD40_eps003's radius
 
+    # --- additive members: the L1 threat model (torchattacks.APGDL1, l1-APGD).  eps_1 = 20 is a mean |delta| of 3.1e-4 over the
+    # 64 600 samples of an utterance, the scale of L-inf 0.0005 and of L2 0.1 (RMS 3.9e-4): a choice of scale, not a measured
+    # equivalence between the threat models ---
+    APGDL1 = (torchattacks.APGDL1, {"eps": 20.0, "steps": 10})
+    APGDL1_eps30 = (torchattacks.APGDL1, {"eps": 30.0, "steps": 10})
+    APGDL1_eps40 = (torchattacks.APGDL1, {"eps": 40.0, "steps": 10})
+
+    WORSTCASE_L1 = (torchattacks.MultiAttack.on_model, {"members": [("APGDL1", {"eps": 20.0, "steps": 10}),
+                                                                    ("FAB", {"norm": "L1", "n_classes": 2, "eps": 20.0})]})
+
     NO_ATTACK = (None, {})

@@ -5,7 +5,8 @@
 // the forward kernels (lcnn_conv0.hip, lcnn_wino.hip, lcnn_mfm.hip) and read back by the backward ones (lcnn_mfm.hip),
 // and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The four attack files (advstep.hip,
 // apgd.hip, momentum.hip, fab.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the
-// host's rows_vec / overlaps; what depends on the 256-thread (tile, row) geometry is in row_tiles.h, which fab.hip does not use.
+// host's rows_vec / overlaps; what depends on the 256-thread (tile, row) geometry is in row_tiles.h, which fab.hip does not use;
+// fab.hip and apgdl1.hip give a row to one 1024-thread workgroup instead: row_workgroup.h.
 
 #ifndef ADVSTEP_COMMON_H
 #define ADVSTEP_COMMON_H
@@ -131,8 +132,8 @@ __device__ __forceinline__ float softplusf(float t) { return (t > 0.0f ? t : 0.0
 // ---- reductions: wave64 xor shuffles (offsets 32 -> 1), then over a 256-thread workgroup one LDS slot per wave, combined as
 // ((l0 . l1) . l2) . l3.  All threads receive the result; `lds` holds >= 4 floats, and two calls in a row must use different
 // slots (each ends on a barrier over its own).  Partials that separate kernels re-reduce must agree bit for bit: this is the
-// one body.  (fab.hip's 1024-thread row_reduce is built on wave_reduce and states its own contract: 16 slots per value, several
-// values per barrier pair, a trailing barrier.)
+// one body.  (row_workgroup.h's 1024-thread row_reduce is built on wave_reduce and states its own contract: 16 slots per value,
+// several values per barrier pair, a trailing barrier.)
 constexpr int kWgThreads = 256;
 template <class Op>
 __device__ __forceinline__ float wave_reduce(float v, Op op) {

@@ -1,0 +1,340 @@
+// apgdl1.hip — gfx950 (MI355X / CDNA4) kernels of l1-APGD (Croce & Hein, "Mind the box: l1-APGD for sparse adversarial
+// attacks on image classifiers", ICML 2021) + the C ABI declared in include/advstep_apgdl1.h: the exact projection onto the
+// L1 ball intersected with the box [0, 1], the sparse top-k sign step fused with it, the random start and the sparsity
+// checkpoint.  The per-row loss / flags and the best-point tracking are apgd.hip's (advstep_apgd_eval / _track).
+//
+// Layout as fab.hip (row_workgroup.h): one workgroup of 1024 threads per row, the row re-read from L2 by every pass, float4
+// loads where the rows allow, fixed-order reductions.  No sort: both per-row searches walk the 31 bits of a non-negative
+// float's pattern kDigit bits at a time, one streaming pass per digit with 2^kDigit - 1 candidates, always all 11 passes.
+// A thread only ever re-reads samples it wrote itself (the traversal gives every pass the same sample -> thread map), so
+// the passes over the output row need no barrier beyond the reductions'.
+//
+// Algorithmic bytes per row sample: step 4 x 12 (grad) + 12 + 4 (cur, grad, x -> u) + 8 x 12 (x, u) + 4 = 164 B, of which
+// 20 B are first touches and the rest L2 / Infinity-Cache re-reads; projection alone 8 x 13 + 4; checkpoint 8 B.
+// Built with -ffp-contract=off; divisions are IEEE.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "advstep_apgdl1.h"
+#include "advstep_common.h"
+#include "row_workgroup.h"
+
+namespace {
+
+constexpr int kDigit = 3, kCand = (1 << kDigit) - 1;   // candidates per streaming pass
+constexpr uint8_t kImproved = 2, kReset = 4;           // the flag bits of include/advstep_apgd.h
+
+// ---- the projection --------------------------------------------------------------------------------------------------
+
+// m_i(lam) = min(max(|d_i| - lam, 0), cap_i): how far coordinate i moves from x_i towards u_i.  The median of the three is
+// that value whenever 0 <= cap (x in [0, 1]), in one instruction instead of two; the searches' passes are VALU-bound.
+__device__ __forceinline__ float l1_move(float ad, float cap, float lam) {
+    return __builtin_amdgcn_fmed3f(ad - lam, 0.0f, cap);
+}
+__device__ __forceinline__ float l1_cap(float d, float xi) { return d > 0.0f ? 1.0f - xi : xi; }
+
+// visit_rows for the search passes: f(s) with s[k] = the sample of row in[k], in visit_rows' order and sample -> thread map, but
+// with the next element's loads issued before this element's arithmetic (with one quad per thread in flight a pass waits out
+// a full L2 latency per quad).
+template <bool VEC, int N, class F>
+__device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], int64_t T, F f) {
+    using Elem = std::conditional_t<VEC, float4, float>;
+    const int64_t n = VEC ? T >> 2 : T;
+    int64_t e = threadIdx.x;
+    Elem next[N];
+    if (e < n) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e];
+    }
+    for (; e < n; e += kRow) {
+        Elem v[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = next[k];
+        if (e + kRow < n) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e + kRow];
+        }
+        float s[N];
+        if constexpr (VEC) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].x;
+            f(s);
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].y;
+            f(s);
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].z;
+            f(s);
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].w;
+            f(s);
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k];
+            f(s);
+        }
+    }
+}
+
+// out row = P(u row; x row, eps), phi0 = phi(0) as the caller's pass over (x, u) summed it.  ur may be outr.
+template <bool VEC>
+__device__ __forceinline__ void l1_box_project_row(const float *xr, const float *ur, float *outr, int64_t T, float eps,
+                                                   float phi0, float *lds) {
+    float lam = 0.0f;
+    if (phi0 > eps) {                                          // workgroup-uniform: every thread holds the same phi0
+        // rho = the largest bit pattern with phi > eps (phi(0) > eps: it exists); lam* is the next float
+        uint32_t rho = 0;
+        for (int top = 31; top > 0; top -= kDigit) {           // bits [shift, top) of the pattern: 11 passes
+            const int shift = top >= kDigit ? top - kDigit : 0;
+            const uint32_t limit = (1u << (top - shift)) - 1u; // candidates j = 1 .. limit
+            float cand[kCand], h[kCand];
+#pragma unroll
+            for (int k = 0; k < kCand; ++k) {
+                cand[k] = __uint_as_float(rho | ((uint32_t)(k + 1) << shift));
+                h[k] = 0.0f;
+            }
+            visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float (&xu)[2]) {
+                const float d = xu[1] - xu[0], ad = fabsf(d), cap = l1_cap(d, xu[0]);
+#pragma unroll
+                for (int k = 0; k < kCand; ++k) h[k] += l1_move(ad, cap, cand[k]);
+            });
+            row_reduce<kCand>(h, SumOp(), lds);
+            uint32_t pick = 0;
+            for (uint32_t j = 1; j <= limit; ++j) {            // phi is non-increasing: the first j that fits ends the scan
+                if (h[j - 1] > eps) pick = j;
+                else break;
+            }
+            rho |= pick << shift;
+        }
+        lam = __uint_as_float(rho + 1u);
+    }
+    map_rows<VEC>({xr, ur}, outr, T, [&](float xi, float ui) {
+        const float d = ui - xi;
+        return clampf(xi + sgn(d) * l1_move(fabsf(d), l1_cap(d, xi), lam), 0.0f, 1.0f);
+    });
+}
+
+// one term of phi(0) for the sample (x_i, u_i)
+__device__ __forceinline__ float l1_move0(float xi, float ui) {
+    const float d = ui - xi;
+    return l1_move(fabsf(d), l1_cap(d, xi), 0.0f);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kRow) void l1_box_project_kernel(const float *__restrict__ x, const float *u, float *out,
+                                                              int64_t B, int64_t T, float eps) {
+    __shared__ float lds[kCand * kRowWaves];
+    for (int64_t row = blockIdx.x; row < B; row += gridDim.x) {
+        const float *xr = x + row * T, *ur = u + row * T;
+        float phi[1] = {0.0f};
+        visit_rows<VEC>({xr, ur}, T, [&](float xi, float ui) { phi[0] += l1_move0(xi, ui); });
+        row_reduce<1>(phi, SumOp(), lds);
+        l1_box_project_row<VEC>(xr, ur, out + row * T, T, eps, phi[0], lds);
+    }
+}
+
+// ---- the step: top-k threshold by radix selection, sparse sign step, projection -------------------------------------------
+
+template <bool VEC>
+__global__ __launch_bounds__(kRow) void apgdl1_step_kernel(const float *cur, const float *__restrict__ grad,
+                                                           const float *__restrict__ x,
+                                                           const float *__restrict__ step_size,
+                                                           const float *__restrict__ topk, float *out,
+                                                           float *__restrict__ stats, int64_t B, int64_t T, float eps) {
+    __shared__ float lds[kCand * kRowWaves];
+    for (int64_t row = blockIdx.x; row < B; row += gridDim.x) {
+        const float *cr = cur + row * T, *gr = grad + row * T, *xr = x + row * T;
+        float *orow = out + row * T;
+        // n = the rank of the threshold in the ascending order of |g|, as a float (T < 2^24: exact)
+        float n = truncf(clampf((1.0f - topk[row]) * (float)T, 0.0f, (float)(T - 1)));
+        if (!(n >= 0.0f)) n = 0.0f;                            // a NaN topk
+        // rho = the largest key with #{key_i < rho} <= n, which is the key of rank n; `below` is that count
+        uint32_t rho = 0;
+        float below = 0.0f;
+        for (int top = 31; top > 0; top -= kDigit) {
+            const int shift = top >= kDigit ? top - kDigit : 0;
+            const uint32_t limit = (1u << (top - shift)) - 1u;
+            float h[kCand];
+#pragma unroll
+            for (int k = 0; k < kCand; ++k) h[k] = 0.0f;
+            visit_rows_ahead<VEC, 1>({gr}, T, [&](const float (&gi)[1]) {
+                const uint32_t key = __float_as_uint(gi[0]) & 0x7FFFFFFFu;   // |g|'s pattern: NaN sorts above +inf
+                if (key >= rho) {
+                    const uint32_t q = (key - rho) >> shift;   // lies below every candidate j > q
+#pragma unroll
+                    for (int k = 0; k < kCand; ++k) h[k] += (q == (uint32_t)k) ? 1.0f : 0.0f;
+                }
+            });
+            row_reduce<kCand>(h, SumOp(), lds);
+            float run = below;
+            uint32_t pick = 0;
+            for (uint32_t j = 1; j <= limit; ++j) {            // #{key < candidate j} = below + h[0..j)
+                run += h[j - 1];
+                if (run <= n) {
+                    pick = j;
+                    below = run;
+                } else {
+                    break;
+                }
+            }
+            rho |= pick << shift;
+        }
+        const float thr = __uint_as_float(rho);
+        float cnt[1] = {0.0f};
+        visit_rows<VEC>({gr}, T, [&](float gi) { cnt[0] += (fabsf(gi) >= thr && gi != 0.0f) ? 1.0f : 0.0f; });
+        row_reduce<1>(cnt, SumOp(), lds);
+        if (threadIdx.x == 0 && stats) {
+            stats[2 * row] = thr;
+            stats[2 * row + 1] = cnt[0];
+        }
+        // u into the output row, phi(0) on the way
+        const float st = step_size[row], den = cnt[0] + 1e-10f;
+        float phi[1] = {0.0f};
+        map_rows<VEC>({cr, gr, xr}, orow, T, [&](float ci, float gi, float xi) {
+            const float s = fabsf(gi) >= thr ? sgn(gi) : 0.0f;
+            const float ui = ci + (st * s) / den;
+            phi[0] += l1_move0(xi, ui);
+            return ui;
+        });
+        row_reduce<1>(phi, SumOp(), lds);
+        l1_box_project_row<VEC>(xr, orow, orow, T, eps, phi[0], lds);
+    }
+}
+
+// ---- the random start ------------------------------------------------------------------------------------------------------
+
+// u = x + t into the output row in the traversal's order (quads q = threadIdx.x, += kRow; samples likewise), t from the
+// caller's draw or the Philox normals of quad q of the row; then the projection.
+template <bool VEC, bool PHILOX>
+__global__ __launch_bounds__(kRow) void apgdl1_init_kernel(const float *__restrict__ x, const float *draw, float *out,
+                                                           int64_t B, int64_t T, float eps, uint64_t seed,
+                                                           uint64_t offset) {
+    __shared__ float lds[kCand * kRowWaves];
+    for (int64_t row = blockIdx.x; row < B; row += gridDim.x) {
+        const float *xr = x + row * T;
+        float *orow = out + row * T;
+        float phi[1] = {0.0f};
+        if constexpr (VEC) {
+            const int64_t n4 = T >> 2;
+            for (int64_t q = threadIdx.x; q < n4; q += kRow) {
+                const float4 xv = reinterpret_cast<const float4 *>(xr)[q];
+                float4 t;
+                if constexpr (PHILOX) t = philox_normal4((uint32_t)q, (uint32_t)row, seed, offset);
+                else t = reinterpret_cast<const float4 *>(draw + row * T)[q];
+                const float4 u = make_float4(xv.x + t.x, xv.y + t.y, xv.z + t.z, xv.w + t.w);
+                phi[0] += l1_move0(xv.x, u.x);
+                phi[0] += l1_move0(xv.y, u.y);
+                phi[0] += l1_move0(xv.z, u.z);
+                phi[0] += l1_move0(xv.w, u.w);
+                reinterpret_cast<float4 *>(orow)[q] = u;
+            }
+        } else {
+            for (int64_t i = threadIdx.x; i < T; i += kRow) {
+                float t;
+                if constexpr (PHILOX) {
+                    const float4 n4 = philox_normal4((uint32_t)(i >> 2), (uint32_t)row, seed, offset);
+                    const int k = (int)(i & 3);
+                    t = k == 0 ? n4.x : (k == 1 ? n4.y : (k == 2 ? n4.z : n4.w));
+                } else {
+                    t = draw[row * T + i];
+                }
+                const float xi = xr[i], ui = xi + t;
+                phi[0] += l1_move0(xi, ui);
+                orow[i] = ui;
+            }
+        }
+        row_reduce<1>(phi, SumOp(), lds);
+        l1_box_project_row<VEC>(xr, orow, orow, T, eps, phi[0], lds);
+    }
+}
+
+// ---- the sparsity checkpoint ---------------------------------------------------------------------------------------------
+
+template <bool VEC>
+__global__ __launch_bounds__(kRow) void apgdl1_checkpoint_kernel(const float *__restrict__ cur,
+                                                                 const float *__restrict__ x_best,
+                                                                 const float *__restrict__ x, uint8_t *flags, float *sp_old,
+                                                                 float *topk, float *step_size, int64_t B, int64_t T,
+                                                                 float eps) {
+    __shared__ float lds[kRowWaves];
+    for (int64_t row = blockIdx.x; row < B; row += gridDim.x) {
+        const uint8_t f = flags[row];                          // read by every thread before thread 0 writes it below
+        const float *br = ((f & kImproved) ? cur : x_best) + row * T;
+        float sp[1] = {0.0f};
+        visit_rows<VEC>({br, x + row * T}, T, [&](float bi, float xi) { sp[0] += (bi - xi != 0.0f) ? 1.0f : 0.0f; });
+        row_reduce<1>(sp, SumOp(), lds);
+        if (threadIdx.x == 0) {
+            const bool red = (sp[0] / sp_old[row]) < 0.95f;
+            topk[row] = (sp[0] / (float)T) / 1.5f;
+            step_size[row] = clampf(red ? eps : step_size[row] / 1.5f, eps / 10.0f, eps);
+            sp_old[row] = sp[0];
+            flags[row] = (uint8_t)((f & ~kReset) | (red ? kReset : 0));
+        }
+    }
+}
+
+constexpr int64_t kMaxRowLength = int64_t(1) << 24;            // per-row counts are carried as exact floats
+
+template <bool PHILOX>
+int apgdl1_init(const float *x, const float *draw, float *out, int64_t B, int64_t T, float eps, uint64_t seed,
+                uint64_t offset, advstep_stream_t stream) {
+    static constexpr decltype(&apgdl1_init_kernel<true, PHILOX>) kernels[2] = {apgdl1_init_kernel<false, PHILOX>,
+                                                                               apgdl1_init_kernel<true, PHILOX>};
+    return launch_rows(kernels, rows_vec(T, {x, draw, out}), B, stream, x, draw, out, B, T, eps, seed, offset);
+}
+
+}  // namespace
+
+extern "C" {
+
+int advstep_l1_box_project_f32(const float *x, const float *u, float *out, float eps, int64_t B, int64_t T,
+                               advstep_stream_t stream) {
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && T < kMaxRowLength && eps > 0.0f);
+    if (B == 0) return ADVSTEP_OK;
+    ADVSTEP_REQUIRE(T >= 1 && x && u && out && !overlaps(out, x, (size_t)B * T * sizeof(float)));
+    return launch_rows(ROW_KERNEL_PAIR(l1_box_project_kernel), rows_vec(T, {x, u, out}), B, stream, x, u, out, B, T, eps);
+}
+
+int advstep_apgdl1_step_f32(const float *cur, const float *grad, const float *x, const float *step_size, const float *topk,
+                            float *out, float *stats, int64_t B, int64_t T, float eps, advstep_stream_t stream) {
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && T < kMaxRowLength && eps > 0.0f);
+    if (B == 0) return ADVSTEP_OK;
+    ADVSTEP_REQUIRE(T >= 1 && cur && grad && x && step_size && topk && out);
+    const size_t bytes = (size_t)B * T * sizeof(float);
+    ADVSTEP_REQUIRE(!overlaps(out, grad, bytes) && !overlaps(out, x, bytes));
+    ADVSTEP_REQUIRE(!stats || !overlap2(stats, (size_t)B * 2 * sizeof(float), out, bytes));
+    return launch_rows(ROW_KERNEL_PAIR(apgdl1_step_kernel), rows_vec(T, {cur, grad, x, out}), B, stream, cur, grad, x,
+                       step_size, topk, out, stats, B, T, eps);
+}
+
+int advstep_apgdl1_init_f32(const float *x, const float *draw, float *out, int64_t B, int64_t T, float eps,
+                            advstep_stream_t stream) {
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && T < kMaxRowLength && eps > 0.0f);
+    if (B == 0) return ADVSTEP_OK;
+    ADVSTEP_REQUIRE(T >= 1 && x && draw && out && !overlaps(out, x, (size_t)B * T * sizeof(float)));
+    return apgdl1_init<false>(x, draw, out, B, T, eps, 0, 0, stream);
+}
+
+int advstep_apgdl1_init_philox_f32(const float *x, float *out, int64_t B, int64_t T, float eps, uint64_t seed,
+                                   uint64_t offset, advstep_stream_t stream) {
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && T < kMaxRowLength && eps > 0.0f);
+    if (B == 0) return ADVSTEP_OK;
+    ADVSTEP_REQUIRE(T >= 1 && x && out && !overlaps(out, x, (size_t)B * T * sizeof(float)));
+    return apgdl1_init<true>(x, nullptr, out, B, T, eps, seed, offset, stream);
+}
+
+int advstep_apgdl1_checkpoint_f32(const float *cur, const float *x_best, const float *x, uint8_t *flags, float *sp_old,
+                                  float *topk, float *step_size, int64_t B, int64_t T, float eps,
+                                  advstep_stream_t stream) {
+    ADVSTEP_REQUIRE(B >= 0 && T >= 0 && T < kMaxRowLength && eps > 0.0f);
+    if (B == 0) return ADVSTEP_OK;
+    ADVSTEP_REQUIRE(T >= 1 && cur && x_best && x && flags && sp_old && topk && step_size);
+    return launch_rows(ROW_KERNEL_PAIR(apgdl1_checkpoint_kernel), rows_vec(T, {cur, x_best, x}), B, stream, cur, x_best, x,
+                       flags, sp_old, topk, step_size, B, T, eps);
+}
+
+}  // extern "C"

@@ -10,7 +10,8 @@
 // keeps the data-dependent iteration counts workgroup-uniform.
 //
 // From advstep_common.h: the NaN-propagating maximum, the reduction operators, the wave butterfly, rows_vec, kMaxGridY.
-// Private to this file, because no other file has 1024-thread rows: row_reduce, the row traversal and launch_rows.
+// From row_workgroup.h (shared with apgdl1.hip, the other file with 1024-thread rows): kRow, row_reduce, the row traversal
+// (visit_rows / map_rows) and launch_rows.
 //
 // No sort: see include/advstep_fab.h.  Algorithmic bytes per row sample: hyperplane 8 B, projection 12 B (t, w in, d
 // out; the re-reads of the fixed-point iteration hit L2), combine 20 B, backward step 8-20 B.
@@ -19,90 +20,14 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <type_traits>
-#include <utility>
-
 #include "advstep_fab.h"
 #include "advstep_common.h"
+#include "row_workgroup.h"
 
 namespace {
 
-constexpr int kRow = 1024;       // threads per row workgroup
-constexpr int kRowWaves = kRow / 64;
 constexpr int kMaxNewton = 64;   // the iteration is finite (<= number of breakpoints); in practice 3-8 passes
 constexpr float kBig = 1e12f;
-
-// Reduce NV per-thread values over the 1024-thread workgroup with advstep_common.h's wave_reduce, then one LDS slot per wave and
-// value, combined as ((w0 . w1) . w2) ... w15; every thread receives the results.  Against wg_reduce: 16 waves instead of 4, NV
-// values per barrier pair (lds: NV * kRowWaves floats), and a trailing barrier that frees the slots, so two calls in a row may
-// use the same ones.
-template <int NV, class Op>
-__device__ __forceinline__ void row_reduce(float (&v)[NV], Op op, float *lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const float x = wave_reduce(v[k], op);
-        if (lane == 0) lds[k * kRowWaves + wave] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        float r = lds[k * kRowWaves];
-#pragma unroll
-        for (int w = 1; w < kRowWaves; ++w) r = op(r, lds[k * kRowWaves + w]);
-        v[k] = r;
-    }
-    __syncthreads();
-}
-
-// The one row traversal: f(a_i, b_i, ...) over the samples of the N rows `in`, or f(i, a_i, b_i, ...) where f takes the sample
-// index.  The index form is chosen iff f is callable with N + 1 arguments, so f must have a fixed arity (no generic lambda).
-// VEC: quads q = threadIdx.x, += kRow, lanes x, y, z, w in order, one float4 load per row; otherwise samples
-// i = threadIdx.x, += kRow.  That order is each thread's accumulation order, so part of every reduced result's bits.
-// STORE: out_i = f(...), one float4 store per quad after all of the quad's loads.  out may alias an input (no __restrict__).
-template <size_t>
-using Sample = float;
-
-template <bool VEC, bool STORE, class F, size_t... K>
-__device__ __forceinline__ void traverse(const float *const (&in)[sizeof...(K)], float *out, int64_t T, F f,
-                                         std::index_sequence<K...>) {
-    auto at = [&](int64_t i, Sample<K>... s) {
-        if constexpr (std::is_invocable_v<F, int64_t, Sample<K>...>) return f(i, s...);
-        else return f(s...);
-    };
-    if constexpr (VEC) {
-        const int64_t n4 = T >> 2;
-        for (int64_t q = threadIdx.x; q < n4; q += kRow) {
-            const float4 v[] = {reinterpret_cast<const float4 *>(in[K])[q]...};
-            if constexpr (STORE) {
-                float4 o;
-                o.x = at(4 * q, v[K].x...);
-                o.y = at(4 * q + 1, v[K].y...);
-                o.z = at(4 * q + 2, v[K].z...);
-                o.w = at(4 * q + 3, v[K].w...);
-                reinterpret_cast<float4 *>(out)[q] = o;
-            } else {
-                at(4 * q, v[K].x...);
-                at(4 * q + 1, v[K].y...);
-                at(4 * q + 2, v[K].z...);
-                at(4 * q + 3, v[K].w...);
-            }
-        }
-    } else {
-        for (int64_t i = threadIdx.x; i < T; i += kRow) {
-            if constexpr (STORE) out[i] = at(i, in[K][i]...);
-            else at(i, in[K][i]...);
-        }
-    }
-}
-template <bool VEC, size_t N, class F>
-__device__ __forceinline__ void visit_rows(const float *const (&in)[N], int64_t T, F f) {
-    traverse<VEC, false>(in, nullptr, T, f, std::make_index_sequence<N>());
-}
-template <bool VEC, size_t N, class F>
-__device__ __forceinline__ void map_rows(const float *const (&in)[N], float *out, int64_t T, F f) {
-    traverse<VEC, true>(in, out, T, f, std::make_index_sequence<N>());
-}
 
 __device__ __forceinline__ float dual_norm_finish(float v, int kind) { return kind == ADVSTEP_FAB_L2 ? sqrtf(v) : v; }
 
@@ -519,17 +444,6 @@ __global__ __launch_bounds__(kRow) void fab_backward_step_kernel(float *x1, cons
     }
 }
 
-inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }
-
-// One kRow-thread workgroup per row (the kernels stride on past kMaxGridY rows): k[1] where the rows are float4-addressable.
-// FAB_KERNEL_PAIR is the only place that writes the pair, so its order is fixed once.
-#define FAB_KERNEL_PAIR(KERNEL) {KERNEL<false>, KERNEL<true>}
-template <class... P, class... A>
-int launch_rows(void (*const (&k)[2])(P...), bool vec, int64_t rows, advstep_stream_t stream, A... args) {
-    hipLaunchKernelGGL(k[vec], dim3(grid_rows(rows)), dim3(kRow), 0, as_stream(stream), args...);
-    return status_after_launch();
-}
-
 }  // namespace
 
 extern "C" {
@@ -540,7 +454,7 @@ int advstep_fab_hyperplane_f32(const float *gz, const float *x, const float *z, 
     ADVSTEP_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (B == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(gz && x && ((z == nullptr) == (labels == nullptr)) && (!z || (wscale && b)));
-    return launch_rows(FAB_KERNEL_PAIR(fab_hyperplane_kernel), rows_vec(T, {gz, x}), B, stream, gz, x, z,
+    return launch_rows(ROW_KERNEL_PAIR(fab_hyperplane_kernel), rows_vec(T, {gz, x}), B, stream, gz, x, z,
                        labels, wscale, b, gnorm, gdot, B, T, norm_kind);
 }
 
@@ -552,8 +466,8 @@ int advstep_fab_projection_f32(const float *t, const float *w, const float *wsca
     ADVSTEP_REQUIRE(t && w && b && d && d != t && d != w && w_rows >= 1 && T >= 1 && T < (int64_t(1) << 24));
     static_assert(ADVSTEP_FAB_LINF == 0 && ADVSTEP_FAB_L2 == 1 && ADVSTEP_FAB_L1 == 2, "the table's row order");
     static constexpr decltype(&fab_projection_linf_kernel<true>) kernels[3][2] = {   // [norm_kind][vec]
-        FAB_KERNEL_PAIR(fab_projection_linf_kernel), FAB_KERNEL_PAIR(fab_projection_l2_kernel),
-        FAB_KERNEL_PAIR(fab_projection_l1_kernel)};
+        ROW_KERNEL_PAIR(fab_projection_linf_kernel), ROW_KERNEL_PAIR(fab_projection_l2_kernel),
+        ROW_KERNEL_PAIR(fab_projection_l1_kernel)};
     return launch_rows(kernels[norm_kind], rows_vec(T, {t, w, d}), R, stream, t, w, wscale, b, d, dnorm, R, w_rows, T);
 }
 
@@ -563,7 +477,7 @@ int advstep_fab_combine_f32(const float *x1, const float *x0, const float *d1, c
     ADVSTEP_REQUIRE(B >= 0 && T >= 0);
     if (B == 0 || T == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x1 && x0 && d1 && d2 && n1 && n2 && out);
-    return launch_rows(FAB_KERNEL_PAIR(fab_combine_kernel), rows_vec(T, {x1, x0, d1, d2, out}), B, stream, x1,
+    return launch_rows(ROW_KERNEL_PAIR(fab_combine_kernel), rows_vec(T, {x1, x0, d1, d2, out}), B, stream, x1,
                        x0, d1, d2, n1, n2, out, B, T, eta, alpha_max);
 }
 
@@ -572,7 +486,7 @@ int advstep_fab_backward_step_f32(float *x1, const float *x0, float *adv, float 
     ADVSTEP_REQUIRE(B >= 0 && T >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (B == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x1 && x0 && adv && res2 && is_adv);
-    return launch_rows(FAB_KERNEL_PAIR(fab_backward_step_kernel), rows_vec(T, {x1, x0, adv}), B, stream,
+    return launch_rows(ROW_KERNEL_PAIR(fab_backward_step_kernel), rows_vec(T, {x1, x0, adv}), B, stream,
                        x1, x0, adv, res2, is_adv, B, T, beta, norm_kind);
 }
 

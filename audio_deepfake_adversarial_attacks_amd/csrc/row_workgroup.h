@@ -1,0 +1,110 @@
+// row_workgroup.h — the one-workgroup-per-row geometry of fab.hip and apgdl1.hip (internal: not part of the C ABI in include/).
+//
+// One workgroup of kRow = 1024 threads (16 wave64) owns one row of T samples and makes several passes over it; at the repo's
+// T = 64 600 a row is 258 KB: it does not fit LDS, but stays L2 / Infinity-Cache resident between the passes, so only the first
+// pass reads HBM.  This header holds what those kernels share: the 16-wave reduction, the row traversal (whose order is part of
+// every reduced result's bits) and the launch helper.  Include after advstep_common.h (wave_reduce, status_after_launch,
+// kMaxGridY).  The 256-thread (tile, row) geometry of the other attack files is row_tiles.h.
+
+#ifndef ADVSTEP_ROW_WORKGROUP_H
+#define ADVSTEP_ROW_WORKGROUP_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+#include <utility>
+
+#include "advstep_common.h"
+
+namespace {
+
+constexpr int kRow = 1024;       // threads per row workgroup
+constexpr int kRowWaves = kRow / 64;
+
+// Reduce NV per-thread values over the 1024-thread workgroup with advstep_common.h's wave_reduce, then one LDS slot per wave and
+// value, combined as ((w0 . w1) . w2) ... w15; every thread receives the results.  Against wg_reduce: 16 waves instead of 4, NV
+// values per barrier pair (lds: NV * kRowWaves floats), and a trailing barrier that frees the slots, so two calls in a row may
+// use the same ones.
+template <int NV, class Op>
+__device__ __forceinline__ void row_reduce(float (&v)[NV], Op op, float *lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const float x = wave_reduce(v[k], op);
+        if (lane == 0) lds[k * kRowWaves + wave] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        float r = lds[k * kRowWaves];
+#pragma unroll
+        for (int w = 1; w < kRowWaves; ++w) r = op(r, lds[k * kRowWaves + w]);
+        v[k] = r;
+    }
+    __syncthreads();
+}
+
+// The one row traversal: f(a_i, b_i, ...) over the samples of the N rows `in`, or f(i, a_i, b_i, ...) where f takes the sample
+// index.  The index form is chosen iff f is callable with N + 1 arguments, so f must have a fixed arity (no generic lambda).
+// VEC: quads q = threadIdx.x, += kRow, lanes x, y, z, w in order, one float4 load per row; otherwise samples
+// i = threadIdx.x, += kRow.  That order is each thread's accumulation order, so part of every reduced result's bits.
+// STORE: out_i = f(...), one float4 store per quad after all of the quad's loads.  out may alias an input (no __restrict__).
+template <size_t>
+using Sample = float;
+
+template <bool VEC, bool STORE, class F, size_t... K>
+__device__ __forceinline__ void traverse(const float *const (&in)[sizeof...(K)], float *out, int64_t T, F f,
+                                         std::index_sequence<K...>) {
+    auto at = [&](int64_t i, Sample<K>... s) {
+        if constexpr (std::is_invocable_v<F, int64_t, Sample<K>...>) return f(i, s...);
+        else return f(s...);
+    };
+    if constexpr (VEC) {
+        const int64_t n4 = T >> 2;
+        for (int64_t q = threadIdx.x; q < n4; q += kRow) {
+            const float4 v[] = {reinterpret_cast<const float4 *>(in[K])[q]...};
+            if constexpr (STORE) {
+                float4 o;
+                o.x = at(4 * q, v[K].x...);
+                o.y = at(4 * q + 1, v[K].y...);
+                o.z = at(4 * q + 2, v[K].z...);
+                o.w = at(4 * q + 3, v[K].w...);
+                reinterpret_cast<float4 *>(out)[q] = o;
+            } else {
+                at(4 * q, v[K].x...);
+                at(4 * q + 1, v[K].y...);
+                at(4 * q + 2, v[K].z...);
+                at(4 * q + 3, v[K].w...);
+            }
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < T; i += kRow) {
+            if constexpr (STORE) out[i] = at(i, in[K][i]...);
+            else at(i, in[K][i]...);
+        }
+    }
+}
+template <bool VEC, size_t N, class F>
+__device__ __forceinline__ void visit_rows(const float *const (&in)[N], int64_t T, F f) {
+    traverse<VEC, false>(in, nullptr, T, f, std::make_index_sequence<N>());
+}
+template <bool VEC, size_t N, class F>
+__device__ __forceinline__ void map_rows(const float *const (&in)[N], float *out, int64_t T, F f) {
+    traverse<VEC, true>(in, out, T, f, std::make_index_sequence<N>());
+}
+
+inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }
+
+// One kRow-thread workgroup per row (the kernels stride on past kMaxGridY rows): k[1] where the rows are float4-addressable.
+// ROW_KERNEL_PAIR is the only place that writes the pair, so its order is fixed once.
+#define ROW_KERNEL_PAIR(KERNEL) {KERNEL<false>, KERNEL<true>}
+template <class... P, class... A>
+int launch_rows(void (*const (&k)[2])(P...), bool vec, int64_t rows, advstep_stream_t stream, A... args) {
+    hipLaunchKernelGGL(k[vec], dim3(grid_rows(rows)), dim3(kRow), 0, as_stream(stream), args...);
+    return status_after_launch();
+}
+
+}  // namespace
+
+#endif  // ADVSTEP_ROW_WORKGROUP_H

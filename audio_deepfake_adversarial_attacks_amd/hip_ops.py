@@ -17,6 +17,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   multi_route                        .../attacks/multiattack.py:55-66
   perturbation_stats                 src/aa/qualitative/attacks_postanalysis.py (the distortion figures beside the WAV pairs)
   row_pgd_*_step / radius_*          no counterpart: the per-row radius steps and the bisection of torchattacks.MinRadiusPGD
+  l1_box_project / apgdl1_*          no counterpart: l1-APGD (Croce & Hein, ICML 2021), torchattacks.APGDL1
 """
 from __future__ import annotations
 
@@ -638,6 +639,91 @@ def apgd_l2_step(cur, prev, grad, x, step_size, eps: float, a: float, out=None, 
                                                   ws_bytes, _stream(cur.device))
     _lib.check(st, "advstep_apgd_l2_step_f32")
     return (out, norms) if return_norms else out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# l1-APGD (include/advstep_apgdl1.h; Croce & Hein, "Mind the box", ICML 2021 — no counterpart in the reference tree).
+# apgd_eval and apgd_track above serve it unchanged.
+# ---------------------------------------------------------------------------------------------------------
+
+def _positive_eps(eps: float) -> float:
+    if not eps > 0:
+        raise ValueError(f"the L1 radius must be positive, got {eps!r}")
+    return eps
+
+
+def l1_box_project(x, u, eps: float, out=None):
+    """Euclidean projection of each row of u onto {z : ||z - x||_1 <= eps, 0 <= z <= 1} (x in [0, 1]); `out` may be `u`."""
+    _require(x, "x"), _require(u, "u")
+    _same_shape(("x", x), ("u", u))
+    B, T = _rows(x, "x")
+    out = _out_like(u, out)
+    with _Launch("l1_box_project", x.device, tensors=(x, u, out)):
+        st = _lib.load().advstep_l1_box_project_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), _positive_eps(eps), B, T,
+                                                    _stream(x.device))
+    _lib.check(st, "advstep_l1_box_project_f32")
+    return out
+
+
+def apgdl1_init(x, eps: float, draw=None, seed: Optional[int] = None, offset: int = 0, out=None):
+    """The random start of l1-APGD: the projection of x + t, t ~ N(0, 1) from the caller's (B, T) `draw` or a Philox `seed`
+    (the normal stream of pgd_l2_init)."""
+    _require(x, "x")
+    B, T = _rows(x, "x")
+    out = _out_like(x, out)
+    with _Launch("apgdl1_init", x.device, tensors=(x, draw, out)):
+        if draw is not None:
+            _require(draw, "draw")
+            _same_shape(("x", x), ("draw", draw))
+            st = _lib.load().advstep_apgdl1_init_f32(x.data_ptr(), draw.data_ptr(), out.data_ptr(), B, T, _positive_eps(eps),
+                                                     _stream(x.device))
+            what = "advstep_apgdl1_init_f32"
+        else:
+            if seed is None:
+                raise ValueError("apgdl1_init needs either `draw` or a Philox `seed`")
+            st = _lib.load().advstep_apgdl1_init_philox_f32(x.data_ptr(), out.data_ptr(), B, T, _positive_eps(eps), seed,
+                                                            offset, _stream(x.device))
+            what = "advstep_apgdl1_init_philox_f32"
+    _lib.check(st, what)
+    return out
+
+
+def apgdl1_step(cur, grad, x, step_size, topk, eps: float, out=None, return_stats: bool = False):
+    """One l1-APGD iteration: the sign step on the coordinates whose |grad| reaches the row's top-k threshold, spread over
+    their count, then the projection about x; `out` may be `cur`.  return_stats: also (B, 2) = threshold, count per row."""
+    named = (("cur", cur), ("grad", grad), ("x", x))
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    B, T = _rows(cur, "cur")
+    _per_row(step_size, "step_size", B), _per_row(topk, "topk", B)
+    out = _out_like(cur, out)
+    stats = torch.empty((B, 2), dtype=torch.float32, device=cur.device) if return_stats else None
+    with _Launch("apgdl1_step", cur.device, tensors=(cur, grad, x, out)):
+        st = _lib.load().advstep_apgdl1_step_f32(cur.data_ptr(), grad.data_ptr(), x.data_ptr(), step_size.data_ptr(),
+                                                 topk.data_ptr(), out.data_ptr(), stats.data_ptr() if return_stats else None,
+                                                 B, T, _positive_eps(eps), _stream(cur.device))
+    _lib.check(st, "advstep_apgdl1_step_f32")
+    return (out, stats) if return_stats else out
+
+
+def apgdl1_checkpoint(cur, x_best, x, state, eps: float) -> None:
+    """In place on `state` (flags, sp_old, topk, step_size): the sparsity checkpoint of l1-APGD, from the best point including
+    this iteration's improvement (`cur` where flags bit 1 is set, else `x_best`).  Call it before apgd_track."""
+    named = (("cur", cur), ("x_best", x_best), ("x", x))
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    B, T = _rows(cur, "cur")
+    for name, dt in (("flags", torch.uint8), ("sp_old", torch.float32), ("topk", torch.float32),
+                     ("step_size", torch.float32)):
+        _per_row(getattr(state, name), name, B, dt)
+    with _Launch("apgdl1_checkpoint", cur.device, tensors=(cur, x)):
+        st = _lib.load().advstep_apgdl1_checkpoint_f32(cur.data_ptr(), x_best.data_ptr(), x.data_ptr(),
+                                                       state.flags.data_ptr(), state.sp_old.data_ptr(),
+                                                       state.topk.data_ptr(), state.step_size.data_ptr(), B, T,
+                                                       _positive_eps(eps), _stream(cur.device))
+    _lib.check(st, "advstep_apgdl1_checkpoint_f32")
 
 
 # ---------------------------------------------------------------------------------------------------------

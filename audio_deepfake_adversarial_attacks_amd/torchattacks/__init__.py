@@ -1,12 +1,13 @@
 """Attack plugin API of the hot path (reference: adversarial_attacks/torchattacks/__init__.py).
 
 The attacks the north-star path names — FGSM, PGD, PGDL2, CW — FAB (the attack that completes the
-reference's AttackEnum), APGD (the step-size-free gradient attack of AutoAttack) and the momentum attacks made for
+reference's AttackEnum), APGD (the step-size-free gradient attack of AutoAttack), APGDL1 (its L1 member) and the momentum attacks made for
 transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), MultiAttack (the worst case over a list
 of them) and MinRadiusPGD (each utterance's minimal radius, by bisection on the device), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
+from .attacks.apgdl1 import APGDL1
 from .attacks.cw import CW
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
@@ -20,5 +21,5 @@ from .attacks.vmifgsm import VMIFGSM
 from .attacks.vnifgsm import VNIFGSM
 
 __version__ = "3.2.7+advstep"
-__all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
+__all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD"]
