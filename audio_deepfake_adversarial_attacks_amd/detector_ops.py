@@ -719,10 +719,18 @@ def res_block_shape_supported(x_shape, cout: int) -> bool:
 
 
 def res_block_plan(block, conv1, bn2, conv2, down, slope: float) -> ResBlockPlan:
+    """The block's plan under the parameters / buffers as they are and the current ADVSTEP_RESBLOCK_FEW.  One plan PER VALUE OF
+    THE SWITCH is kept while the state stands: a captured attack iteration (torchattacks/graphed.py) bakes the addresses of a
+    plan's tensors, survives a flip of the switch and is replayed when it is flipped back, so the other form's run must not
+    free them.  A changed parameter or buffer (version counters never come back) drops both."""
     tensors = [t for m in (conv1, bn2, conv2, down) if m is not None for t in list(m.parameters()) + list(m.buffers())]
-    key = tuple((t.data_ptr(), t._version) for t in tensors) + (_few_epilogue_enabled(),)
+    key = tuple((t.data_ptr(), t._version) for t in tensors)
+    few = _few_epilogue_enabled()
     if getattr(block, "_advstep_plan_key", None) != key:
-        block._advstep_plan_key, block._advstep_plan = key, ResBlockPlan(conv1, bn2, conv2, down, slope)
+        block._advstep_plan_key, block._advstep_plans = key, {}
+    if few not in block._advstep_plans:
+        block._advstep_plans[few] = ResBlockPlan(conv1, bn2, conv2, down, slope)
+    block._advstep_plan = block._advstep_plans[few]
     return block._advstep_plan
 
 

@@ -19,11 +19,33 @@ that alternate batches get a capture each — a capture owns its static buffers 
 two batches at once — over the same read-only model.
 
 What is baked into a captured graph and therefore part of its key: the device pointers of the static input buffers (owned
-here), of the model's parameters and of every cache derived from them (prepared Winograd weights, packed GRU weights,
-filterbank tables) — so the key carries the parameters' version counters and the modules' train/eval flags; the ADVSTEP_* switches and the labels'
-dtype / shape; a graph is captured only when the same key shows up a second time (an adversarial-training step changes the
-weights before every attack call: those calls stay eager), and capturing a workload under a new state drops the captures of
-the same workload under older states (each holds a private memory pool).  Random starts are drawn OUTSIDE the graph (a fresh Philox key per call).
+here), of the model's parameters and buffers and of every cache derived from them (prepared Winograd weights, `bn_eval_affine`
+pairs, RawNet3's chain plans, packed GRU weights, filterbank tables).  The key has two parts:
+    family  what makes two calls the same workload AND may come back: the model's identity, the attack class and its
+            hyper-parameters, targeted mode, the batch shape, the labels' dtype / shape, the launch stream, the graph form, every
+            module's train/eval flag and every ADVSTEP_* switch (an A/B run flips a switch and flips it back; an attack in eval
+            mode alternates with one in train mode on the same model);
+    state   the (address, version counter) of every parameter and buffer.  Version counters only grow: a capture under an
+            older state can never be replayed again.
+A graph is captured only when the same key shows up a second time (an adversarial-training step changes the weights before
+every attack call: those calls stay eager), and capturing a family under a new state drops the captures of the same family
+under older states (each holds a private memory pool).  Captures of one workload under other flags or switches are kept,
+so the caches they bake must stay where they are while the other path runs: the caches are keyed by parameter / buffer
+versions, not by the switches, and the one that is built per switch value, a residual block's plan under
+ADVSTEP_RESBLOCK_FEW, keeps a plan per value (detector_ops.res_block_plan).  Random starts are drawn OUTSIDE the graph (a
+fresh Philox key per call).
+
+Lifetime: a capture dies with its model.  The tables are keyed by id(model), an integer that CPython hands to the next object
+at that address, and by addresses and version counters that an equally built later model can reproduce; a capture that
+outlived its model would keep its private pool (the whole forward + backward activation set) and could be replayed for a
+stranger.  So the first call on a model registers a `weakref.finalize` on it that drops the model's captures and its entries
+in `_SEEN` / `_FAILED`.  No strong reference to the model is held here: that would keep the pool alive for good.
+
+Hazards the suite pins (tests/test_gpu_graph_detectors.py on RawNet3, SpecRNet and LCNN; tests/test_graph_keys_host.py for the
+pure parts): in-place parameter changes, buffer-only changes (BatchNorm running statistics), `load_state_dict` of equal values,
+an ADVSTEP_* switch flipped and flipped back with live captures, train/eval flags, targeted mode, the labels' dtype, a partial
+batch between replays, eviction at `_MAX_GRAPHS`, weights that change before every call, and the model's death.  Not run: a
+failing capture (it would have to raise inside a stream capture); that branch is covered by reading.
 
 Eager fallback, always bit-identical: CPU op tables / checked ops (tests), launch profiling of kernels INSIDE the model
 part (hip_ops.start_profile without graph_ok: bench.py's per-family brackets), ADVSTEP_ATTACK_GRAPH=0, the attack's own off
@@ -32,6 +54,7 @@ from __future__ import annotations
 
 import os
 import warnings
+import weakref
 from typing import Callable, Dict, Optional, Tuple
 
 import torch
@@ -40,6 +63,7 @@ _GRAPHS: Dict[tuple, "_Captured"] = {}
 _SEEN: Dict[tuple, int] = {}
 _FAILED: set = set()          # family keys (model, attack, shape, hyper-parameters) whose capture failed: they stay eager
 _MAX_GRAPHS = 8
+_WATCHED: Dict[int, weakref.finalize] = {}     # id(model) -> the finalizer that drops the model's entries when it dies
 
 
 def _toggles() -> Tuple:
@@ -62,6 +86,25 @@ def _state_signature(model: torch.nn.Module) -> Tuple:
     buffers = tuple((b.data_ptr(), b._version) for b in model.buffers())
     flags = tuple(m.training for m in model.modules())
     return versions, buffers, flags
+
+
+def _forget_model(model_id: int) -> None:
+    """Drop everything keyed by `model_id` (the first component of every family): captures with their pools, sightings, failures."""
+    _WATCHED.pop(model_id, None)
+    for table in (_GRAPHS, _SEEN):
+        for key in [k for k in table if k[0] == model_id]:
+            del table[key]
+    for family in [f for f in _FAILED if f[0] == model_id]:
+        _FAILED.discard(family)
+
+
+def _watch(model: torch.nn.Module) -> None:
+    """Tie the table entries of `model` to its lifetime (module docstring, "Lifetime").  The callback gets the id, not the
+    model; not run at interpreter exit, where the HIP runtime may already be gone."""
+    if id(model) not in _WATCHED:
+        fin = weakref.finalize(model, _forget_model, id(model))
+        fin.atexit = False
+        _WATCHED[id(model)] = fin
 
 
 class _Captured:
@@ -157,13 +200,15 @@ def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torc
                  and not torch.cuda.is_current_stream_capturing() and not (fused and step_has_state))
     done = 0
     if use_graph:
-        # family: what makes two calls the same workload; state: what a capture bakes in beyond that (parameter / buffer
-        # storage and versions, train/eval flags, the ADVSTEP_* switches the kernels read at call time)
+        # family: what makes two calls the same workload and may come back (train/eval flags and the ADVSTEP_* switches the
+        # kernels read at call time included); state: parameter / buffer storage and versions, which never come back
         # ... and the launch stream: a capture serves ONE batch at a time (its static buffers, its activation pool), so two
         # streams with a batch in flight each (evaluation.generate_attacks) hold a capture each
+        versions, buffers, flags = _state_signature(attack.model)
         family = (id(attack.model), attack.__class__.__name__, hyper, attack._targeted, tuple(adv.shape), str(adv.device),
-                  labels.dtype, tuple(labels.shape), torch.cuda.current_stream(adv.device).cuda_stream, fused)
-        key = family + (_state_signature(attack.model), _toggles())
+                  labels.dtype, tuple(labels.shape), torch.cuda.current_stream(adv.device).cuda_stream, fused, flags, _toggles())
+        key = family + ((versions, buffers),)
+        _watch(attack.model)
         cap = _GRAPHS.get(key)
         if cap is None and family not in _FAILED:
             _SEEN[key] = _SEEN.get(key, 0) + 1
@@ -171,7 +216,7 @@ def run_iterations(attack, adv: torch.Tensor, images: torch.Tensor, labels: torc
                 _SEEN.clear()
             if _SEEN.get(key, 0) >= 2:
                 # a capture of this family under ANOTHER state can never be replayed again once the state moved on (training
-                # changed the weights, a switch was flipped): drop it now — each holds a private pool with the whole
+                # changed the weights or the running statistics): drop it now — each holds a private pool with the whole
                 # forward + backward activation set
                 for stale in [k for k in _GRAPHS if k[:len(family)] == family]:
                     del _GRAPHS[stale]
@@ -205,3 +250,6 @@ def clear() -> None:
     _GRAPHS.clear()
     _SEEN.clear()
     _FAILED.clear()
+    for fin in list(_WATCHED.values()):
+        fin.detach()
+    _WATCHED.clear()

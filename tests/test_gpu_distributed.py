@@ -179,12 +179,15 @@ data = SyntheticDetectionDataset(32)
 attack = {"eps": 0.003, "steps": 6, "random_start": False}
 
 
+held = []                                                      # captures held as each batch is queued: the attacked model is alive
+
+
 def evaluate():
     set_seed(42)
     graphed.clear()
     return generate_attacks([None, None, None], cfg, "cuda:0", attack_model_config=cfg, attack_method=torchattacks.PGD,
                             attack_params=dict(attack), batch_size=8, dataset=data, share_weights=True, shuffle=True,
-                            num_workers=0, return_scores=True)
+                            num_workers=0, return_scores=True, on_batch_queued=lambda i: held.append(len(graphed._GRAPHS)))
 
 
 def table(n, seed):
@@ -197,7 +200,7 @@ def table(n, seed):
 
 plain_table = aggregate_across_ranks(*table(50, 3))
 plain = evaluate()                                             # no process group: the non-distributed path
-plain_graphs = len(graphed._GRAPHS)
+plain_graphs = held[-1]
 
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)      # RCCL communicator on cuda:0
 with warnings.catch_warnings(record=True) as caught:
@@ -209,7 +212,7 @@ with warnings.catch_warnings(record=True) as caught:
     dist.barrier()
     rccl_table = aggregate_across_ranks(*table(50, 3))
     sharded = evaluate()                                        # generate_attacks under the process group, hipGraph path on
-    rccl_graphs = len(graphed._GRAPHS)
+    rccl_graphs = held[-1]
 dist.destroy_process_group()
 out = {"all_reduce": t.tolist(), "all_gather": parts[0].tolist(), "graphs_plain": plain_graphs, "graphs_rccl": rccl_graphs,
        "capture_warnings": [str(w.message) for w in caught if "capture" in str(w.message)],

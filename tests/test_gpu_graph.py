@@ -1,6 +1,7 @@
 """`-m gpu`: hipGraph replay of the PGD / PGDL2 inner loop (torchattacks/graphed.py) against the eager launches — same
-kernels, same order, so the adversarial waveforms must be bit-identical; stale-graph hazards (changed weights, changed
-train/eval flags, active launch profiling) must fall back to eager."""
+kernels, same order, so the adversarial waveforms must be bit-identical; stale-graph hazards (changed weights, active
+launch profiling) must fall back to eager.  Every detector, every replayed attack and the rest of the capture key:
+tests/test_gpu_graph_detectors.py."""
 import pytest
 import torch
 
@@ -163,10 +164,13 @@ def test_two_batches_in_flight_give_the_same_scores(cuda, fresh_graphs):
     def evaluate(in_flight):
         torch.manual_seed(5)                             # the random starts' Philox keys come from the global generator
         fresh_graphs.clear()
+        held = []                                        # captures held as each batch is queued: the attacked model is alive
         rep = generate_attacks([None, None, None], cfg, str(cuda), attack_model_config=cfg, attack_method=torchattacks.PGD,
                                attack_params={"eps": 0.003, "steps": 6}, batch_size=4, dataset=SyntheticDetectionDataset(32),
-                               share_weights=True, shuffle=False, num_workers=0, return_scores=True, in_flight=in_flight)
-        return rep, len(fresh_graphs._GRAPHS)
+                               share_weights=True, shuffle=False, num_workers=0, return_scores=True, in_flight=in_flight,
+                               on_batch_queued=lambda i: held.append(len(fresh_graphs._GRAPHS)))
+        assert len(held) == 8 and len(fresh_graphs._GRAPHS) == 0      # the loop's models are gone, and their captures with them
+        return rep, held[-1]
 
     one, g1 = evaluate(1)
     two, g2 = evaluate(2)
