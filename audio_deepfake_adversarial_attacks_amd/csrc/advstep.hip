@@ -309,7 +309,7 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_project_kernel(const float 
 // 16 B per sample (adv, grad, orig read once; out written once) instead of 32.  A row is 16 workgroups (T = 64 600); its
 // two norms are exchanged INSIDE the launch through 8-byte {tag, value} granules (one per workgroup and phase, written by ONE
 // agent-scope store, re-read with agent-scope loads until every tag of the row shows the phase: the data is the flag, no
-// fence — /opt/skills/guides/cdna_hip_programming.md Guideline 16, form R2).  tag = {call epoch, phase}: the workspace's first
+// fence — the CDNA HIP programming guide's Guideline 16, form R2).  tag = {call epoch, phase}: the workspace's first
 // word counts the single-pass calls that used it (the repair kernel behind every call advances it), so a granule of an earlier
 // call — or a word some other user of the scratch left there — never carries this call's tag and nothing has to be cleaned
 // between calls (round 5; rounds 2-3 zeroed the granules with a memset node, round 4 in the repair kernel).  The partial sums
@@ -406,10 +406,7 @@ __global__ __launch_bounds__(kWgThreads, 8) void pgd_l2_fused_kernel(const float
     }
     load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
     load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) s += (g[j].x * g[j].x + g[j].y * g[j].y) + (g[j].z * g[j].z + g[j].w * g[j].w);
-    s = wg_sum(s, lds);
+    float s = wg_sum(tile_sumsq(g), lds);
     const unsigned base = exchange_tag_base(epoch);
     const float gsq = row_exchange_sum(gran_g + b * C, C, tile, s, base, 1u, spin_limit, lds + 4, &failed);
     if (failed) {
@@ -420,38 +417,19 @@ __global__ __launch_bounds__(kWgThreads, 8) void pgd_l2_fused_kernel(const float
     const float gn = gn_raw + eps_div;
     s = 0.0f;
 #pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        const float4 x = xs[j * kWgThreads + threadIdx.x];
-        float4 m;
-        m.x = (a[j].x + alpha * (g[j].x / gn)) - x.x;
-        m.y = (a[j].y + alpha * (g[j].y / gn)) - x.y;
-        m.z = (a[j].z + alpha * (g[j].z / gn)) - x.z;
-        m.w = (a[j].w + alpha * (g[j].w / gn)) - x.w;
-        if (!in_row(T, quad_of(tile, j), 0)) m.x = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 1)) m.y = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 2)) m.z = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 3)) m.w = 0.0f;
-        s += (m.x * m.x + m.y * m.y) + (m.z * m.z + m.w * m.w);
-    }
+    for (int j = 0; j < kVecs; ++j)
+        s += sumsq4(zero_outside_row(l2_move4(a[j], g[j], xs[j * kWgThreads + threadIdx.x], alpha, gn), T, quad_of(tile, j)));
     s = wg_sum(s, lds + 8);
     const float dn = sqrtf(row_exchange_sum(gran_d + b * C, C, tile, s, base, 2u, spin_limit, lds + 4, &failed));
     if (failed) {
         row_exchange_abandon(fail, b, nullptr, gran_d + b * C, tile, base);
         return;
     }
-    const float f = min_nan((1.0f / dn) * eps, 1.0f);
+    const float f = l2_scale_factor<false>(dn, eps);
 #pragma unroll
-    for (int j = 0; j < kVecs; ++j) {      // d recomputed (same expressions, same bits) rather than kept across the exchange
+    for (int j = 0; j < kVecs; ++j) {      // d recomputed (l2_move4 again: same bits) rather than kept across the exchange
         const float4 x = xs[j * kWgThreads + threadIdx.x];
-        float4 d;
-        d.x = (a[j].x + alpha * (g[j].x / gn)) - x.x;
-        d.y = (a[j].y + alpha * (g[j].y / gn)) - x.y;
-        d.z = (a[j].z + alpha * (g[j].z / gn)) - x.z;
-        d.w = (a[j].w + alpha * (g[j].w / gn)) - x.w;
-        a[j].x = clampf(x.x + d.x * f, lo, hi);
-        a[j].y = clampf(x.y + d.y * f, lo, hi);
-        a[j].z = clampf(x.z + d.z * f, lo, hi);
-        a[j].w = clampf(x.w + d.w * f, lo, hi);
+        a[j] = l2_project4(x, l2_move4(a[j], g[j], x, alpha, gn), f, lo, hi);
     }
     store_tile<VEC>(out + b * T, T, tile, a);
     if (tile == 0 && threadIdx.x == 0) {
@@ -481,8 +459,8 @@ __device__ __forceinline__ unsigned take_flag(unsigned *fail, unsigned *last, un
 }
 
 // Repair pass of the single-pass step: one workgroup per row, returns at once unless the row's flag is up.  The row's tiles
-// are visited in sequence with the three-kernel path's own expressions and reductions (sumsq_partial / pgd_l2_delta /
-// pgd_l2_project), so a repaired row carries the same bits as any other.  adv / orig / grad are re-read from global memory:
+// are visited in sequence with the three-kernel path's own expressions (row_tiles.h's per-quad helpers) and reductions, so a
+// repaired row carries the same bits as any other.  adv / orig / grad are re-read from global memory:
 // the single-pass path is not taken when `out` aliases an input.
 template <bool VEC>
 __global__ __launch_bounds__(kWgThreads) void pgd_l2_repair_kernel(const float *__restrict__ adv, const float *__restrict__ grad,
@@ -496,10 +474,7 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_repair_kernel(const float *
     float4 a[kVecs], g[kVecs], x[kVecs];
     for (int tile = 0; tile < C; ++tile) {
         load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j) s += (g[j].x * g[j].x + g[j].y * g[j].y) + (g[j].z * g[j].z + g[j].w * g[j].w);
-        s = wg_sum(s, lds);
+        const float s = wg_sum(tile_sumsq(g), lds);
         if (threadIdx.x == 0) gpart[tile] = s;
         __syncthreads();
     }
@@ -511,40 +486,19 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_repair_kernel(const float *
         load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
         float s = 0.0f;
 #pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            float4 d;
-            d.x = (a[j].x + alpha * (g[j].x / gn)) - x[j].x;
-            d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
-            d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
-            d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-            if (!in_row(T, quad_of(tile, j), 0)) d.x = 0.0f;
-            if (!in_row(T, quad_of(tile, j), 1)) d.y = 0.0f;
-            if (!in_row(T, quad_of(tile, j), 2)) d.z = 0.0f;
-            if (!in_row(T, quad_of(tile, j), 3)) d.w = 0.0f;
-            s += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-        }
+        for (int j = 0; j < kVecs; ++j) s += sumsq4(zero_outside_row(l2_move4(a[j], g[j], x[j], alpha, gn), T, quad_of(tile, j)));
         s = wg_sum(s, lds);
         if (threadIdx.x == 0) dpart[tile] = s;
         __syncthreads();
     }
     const float dn = sqrtf(row_sum(dpart, C, lds + 8));
-    const float f = min_nan((1.0f / dn) * eps, 1.0f);
+    const float f = l2_scale_factor<false>(dn, eps);
     for (int tile = 0; tile < C; ++tile) {
         load_tile<VEC>(adv + b * T, T, tile, 0.0f, a);
         load_tile<VEC>(grad + b * T, T, tile, 0.0f, g);
         load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
 #pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            float4 d;
-            d.x = (a[j].x + alpha * (g[j].x / gn)) - x[j].x;
-            d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
-            d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
-            d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-            a[j].x = clampf(x[j].x + d.x * f, lo, hi);
-            a[j].y = clampf(x[j].y + d.y * f, lo, hi);
-            a[j].z = clampf(x[j].z + d.z * f, lo, hi);
-            a[j].w = clampf(x[j].w + d.w * f, lo, hi);
-        }
+        for (int j = 0; j < kVecs; ++j) a[j] = l2_project4(x[j], l2_move4(a[j], g[j], x[j], alpha, gn), f, lo, hi);
         store_tile<VEC>(out + b * T, T, tile, a);
     }
     if (threadIdx.x == 0) {
@@ -579,32 +533,11 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_init_noise_kernel(const flo
     load_tile<VEC>(normal + b * T, T, tile, 0.0f, nz);
     const float nrm = sqrtf(row_sum(npart + b * C, C, lds));
     const float scale = (r[b] / nrm) * eps;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        xv[j].x = clampf(xv[j].x + nz[j].x * scale, lo, hi);
-        xv[j].y = clampf(xv[j].y + nz[j].y * scale, lo, hi);
-        xv[j].z = clampf(xv[j].z + nz[j].z * scale, lo, hi);
-        xv[j].w = clampf(xv[j].w + nz[j].w * scale, lo, hi);
-    }
+    l2_start_apply(xv, nz, scale, lo, hi);
     store_tile<VEC>(out + b * T, T, tile, xv);
 }
 
-// Philox normals for this thread's kVecs quads of (row b, tile); out-of-row samples are zeroed.
-__device__ __forceinline__ void philox_normal_tile(int64_t T, int tile, uint32_t b, uint64_t seed, uint64_t offset,
-                                                   float4 (&nz)[kVecs]) {
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        const int64_t q = quad_of(tile, j);
-        if (in_row(T, q, 0)) {
-            nz[j] = philox_normal4((uint32_t)q, b, seed, offset);
-            if (!in_row(T, q, 1)) nz[j].y = 0.0f;
-            if (!in_row(T, q, 2)) nz[j].z = 0.0f;
-            if (!in_row(T, q, 3)) nz[j].w = 0.0f;
-        } else {
-            nz[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-    }
-}
+// (philox_normal_tile, philox_start_scale and l2_start_apply are row_tiles.h's)
 
 __global__ __launch_bounds__(kWgThreads) void philox_normal_sumsq_kernel(int64_t T, uint64_t seed, uint64_t offset,
                                                                      float *__restrict__ part) {
@@ -613,11 +546,7 @@ __global__ __launch_bounds__(kWgThreads) void philox_normal_sumsq_kernel(int64_t
     const int64_t b = blockIdx.y;
     float4 nz[kVecs];
     philox_normal_tile(T, tile, (uint32_t)b, seed, offset, nz);
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j)
-        s += (nz[j].x * nz[j].x + nz[j].y * nz[j].y) + (nz[j].z * nz[j].z + nz[j].w * nz[j].w);
-    s = wg_sum(s, lds);
+    const float s = wg_sum(tile_sumsq(nz), lds);
     if (threadIdx.x == 0) part[b * C + tile] = s;
 }
 
@@ -633,17 +562,8 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_init_philox_kernel(const fl
     load_tile<VEC>(x + b * T, T, tile, 0.0f, xv);
     philox_normal_tile(T, tile, (uint32_t)b, seed, offset, nz);
     const float nrm = sqrtf(row_sum(npart + b * C, C, lds));
-    const uint64_t off1 = offset + 1;
-    const Quad rq = philox4x32_10((uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)off1, (uint32_t)(off1 >> 32),
-                                  (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float scale = (u01(rq.v[0]) / nrm) * eps;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        xv[j].x = clampf(xv[j].x + nz[j].x * scale, lo, hi);
-        xv[j].y = clampf(xv[j].y + nz[j].y * scale, lo, hi);
-        xv[j].z = clampf(xv[j].z + nz[j].z * scale, lo, hi);
-        xv[j].w = clampf(xv[j].w + nz[j].w * scale, lo, hi);
-    }
+    const float scale = philox_start_scale(b, seed, offset, nrm, eps);
+    l2_start_apply(xv, nz, scale, lo, hi);
     store_tile<VEC>(out + b * T, T, tile, xv);
 }
 
@@ -663,11 +583,7 @@ __global__ __launch_bounds__(kWgThreads, 8) void pgd_l2_init_philox_fused_kernel
     const int64_t b = blockIdx.y;
     float4 nz[kVecs];
     philox_normal_tile(T, tile, (uint32_t)b, seed, offset, nz);
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j)
-        s += (nz[j].x * nz[j].x + nz[j].y * nz[j].y) + (nz[j].z * nz[j].z + nz[j].w * nz[j].w);
-    s = wg_sum(s, lds);
+    const float s = wg_sum(tile_sumsq(nz), lds);
     // the tile of x is requested BEFORE the exchange (16-byte path): its HBM latency then runs under the wait for the row's other
     // workgroups; the scalar path (rows not 16-byte addressable) keeps it behind - 16 more live registers make it spill
     float4 xv[kVecs];
@@ -678,18 +594,9 @@ __global__ __launch_bounds__(kWgThreads, 8) void pgd_l2_init_philox_fused_kernel
         row_exchange_abandon(fail, b, gran + b * C, nullptr, tile, base);
         return;
     }
-    const uint64_t off1 = offset + 1;
-    const Quad rq = philox4x32_10((uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)off1, (uint32_t)(off1 >> 32),
-                                  (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float scale = (u01(rq.v[0]) / nrm) * eps;
+    const float scale = philox_start_scale(b, seed, offset, nrm, eps);
     if constexpr (!VEC) load_tile<VEC>(x + b * T, T, tile, 0.0f, xv);
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        xv[j].x = clampf(xv[j].x + nz[j].x * scale, lo, hi);
-        xv[j].y = clampf(xv[j].y + nz[j].y * scale, lo, hi);
-        xv[j].z = clampf(xv[j].z + nz[j].z * scale, lo, hi);
-        xv[j].w = clampf(xv[j].w + nz[j].w * scale, lo, hi);
-    }
+    l2_start_apply(xv, nz, scale, lo, hi);
     store_tile<VEC>(out + b * T, T, tile, xv);
 }
 
@@ -706,29 +613,16 @@ __global__ __launch_bounds__(kWgThreads) void pgd_l2_init_philox_repair_kernel(c
     float4 nz[kVecs], xv[kVecs];
     for (int tile = 0; tile < C; ++tile) {
         philox_normal_tile(T, tile, (uint32_t)b, seed, offset, nz);
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j)
-            s += (nz[j].x * nz[j].x + nz[j].y * nz[j].y) + (nz[j].z * nz[j].z + nz[j].w * nz[j].w);
-        s = wg_sum(s, lds);
+        const float s = wg_sum(tile_sumsq(nz), lds);
         if (threadIdx.x == 0) npart[tile] = s;
         __syncthreads();
     }
     const float nrm = sqrtf(row_sum(npart, C, lds + 4));
-    const uint64_t off1 = offset + 1;
-    const Quad rq = philox4x32_10((uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)off1, (uint32_t)(off1 >> 32),
-                                  (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float scale = (u01(rq.v[0]) / nrm) * eps;
+    const float scale = philox_start_scale(b, seed, offset, nrm, eps);
     for (int tile = 0; tile < C; ++tile) {
         load_tile<VEC>(x + b * T, T, tile, 0.0f, xv);
         philox_normal_tile(T, tile, (uint32_t)b, seed, offset, nz);
-#pragma unroll
-        for (int j = 0; j < kVecs; ++j) {
-            xv[j].x = clampf(xv[j].x + nz[j].x * scale, lo, hi);
-            xv[j].y = clampf(xv[j].y + nz[j].y * scale, lo, hi);
-            xv[j].z = clampf(xv[j].z + nz[j].z * scale, lo, hi);
-            xv[j].w = clampf(xv[j].w + nz[j].w * scale, lo, hi);
-        }
+        l2_start_apply(xv, nz, scale, lo, hi);
         store_tile<VEC>(out + b * T, T, tile, xv);
     }
 }
@@ -870,6 +764,12 @@ inline int flat_vecs() {
     return v;
 }
 
+// The repair kernel behind a single-pass launch: one workgroup per row.
+template <class... P, class... A>
+void launch_row_repair(void (*const (&pair)[2])(P...), bool vec, int64_t B, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(pair[vec], dim3((unsigned)B), dim3(kWgThreads), 0, st, args...);
+}
+
 template <int NIN, int VECS, class Op>
 void launch_flat_vec(const float *in0, const float *in1, const float *in2, float *out, int64_t n4, Op op,
                      hipStream_t st) {
@@ -910,20 +810,6 @@ int launch_flat(const float *in0, const float *in1, const float *in2, float *out
 // C ABI
 // ---------------------------------------------------------------------------------------------------------
 
-// Launch a row kernel over all B rows in slabs of <= kMaxGridY rows (grid.y is 16 bits); `ARGS` may use `b0` (first row of
-// the slab).  Only this file slabs: apgd.hip and momentum.hip reject B > kMaxGridY.
-#define ADV_LAUNCH_ROWS(KERNEL, VECFLAG, B, T, st, ...)                                                    \
-    do {                                                                                                   \
-        const int C_ = ws_tiles_per_row(T);                                                                \
-        for (int64_t b0 = 0; b0 < (B); b0 += kMaxGridY) {                                                  \
-            const int64_t nb_ = ((B)-b0 < kMaxGridY) ? ((B)-b0) : kMaxGridY;                               \
-            if (VECFLAG)                                                                                   \
-                hipLaunchKernelGGL((KERNEL<true>), dim3(C_, (unsigned)nb_), dim3(kWgThreads), 0, st, __VA_ARGS__);  \
-            else                                                                                           \
-                hipLaunchKernelGGL((KERNEL<false>), dim3(C_, (unsigned)nb_), dim3(kWgThreads), 0, st, __VA_ARGS__); \
-        }                                                                                                  \
-    } while (0)
-
 extern "C" {
 
 int advstep_abi_version(void) { return ADVSTEP_ABI_VERSION; }
@@ -963,9 +849,13 @@ int advstep_minmax_normalize_f32(const float *x, float *x01, float *mn, float *m
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x, x01});
     const int C = ws_tiles_per_row(T);
-    ADV_LAUNCH_ROWS(minmax_partial_kernel, vec, B, T, st, x + b0 * T, T, w.p0 + b0 * C, w.p1 + b0 * C);
-    ADV_LAUNCH_ROWS(minmax_apply_kernel, vec, B, T, st, x + b0 * T, x01 + b0 * T, mn + b0, mx + b0, T, w.p0 + b0 * C,
-                    w.p1 + b0 * C);
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(minmax_partial_kernel), vec, nb, T, st, x + b0 * T, T, w.p0 + b0 * C, w.p1 + b0 * C);
+    });
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(minmax_apply_kernel), vec, nb, T, st, x + b0 * T, x01 + b0 * T, mn + b0, mx + b0, T,
+                     w.p0 + b0 * C, w.p1 + b0 * C);
+    });
     return status_after_launch();
 }
 
@@ -976,7 +866,9 @@ int advstep_minmax_revert_f32(const float *x01, const float *mn, const float *mx
     ADVSTEP_REQUIRE(x01 && mn && mx && out);
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x01, out});
-    ADV_LAUNCH_ROWS(minmax_revert_kernel, vec, B, T, st, x01 + b0 * T, mn + b0, mx + b0, out + b0 * T, T);
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(minmax_revert_kernel), vec, nb, T, st, x01 + b0 * T, mn + b0, mx + b0, out + b0 * T, T);
+    });
     return status_after_launch();
 }
 
@@ -1040,9 +932,13 @@ int advstep_pgd_l2_init_noise_f32(const float *x, const float *normal, const flo
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x, normal, out});
     const int C = ws_tiles_per_row(T);
-    ADV_LAUNCH_ROWS(sumsq_partial_kernel, vec, B, T, st, normal + b0 * T, T, w.p0 + b0 * C);
-    ADV_LAUNCH_ROWS(pgd_l2_init_noise_kernel, vec, B, T, st, x + b0 * T, normal + b0 * T, r + b0, out + b0 * T, T, eps,
-                    lo, hi, w.p0 + b0 * C);
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(sumsq_partial_kernel), vec, nb, T, st, normal + b0 * T, T, w.p0 + b0 * C);
+    });
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(pgd_l2_init_noise_kernel), vec, nb, T, st, x + b0 * T, normal + b0 * T, r + b0, out + b0 * T, T,
+                     eps, lo, hi, w.p0 + b0 * C);
+    });
     return status_after_launch();
 }
 
@@ -1058,26 +954,17 @@ int advstep_pgd_l2_init_philox_f32(const float *x, float *out, int64_t B, int64_
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {x, out});
     const int C = ws_tiles_per_row(T);
-    const void *fused = vec ? (const void *)pgd_l2_init_philox_fused_kernel<true> : (const void *)pgd_l2_init_philox_fused_kernel<false>;
+    static constexpr decltype(&pgd_l2_init_philox_fused_kernel<true>) fused[2] = ROW_KERNEL_PAIR(pgd_l2_init_philox_fused_kernel);
     if (l2_single_pass() && C <= 64 && !overlaps(x, out, (size_t)B * T * sizeof(float)) &&
-        B * C <= l2_resident_capacity(vec ? kCapInitVec : kCapInitScalar, fused)) {
+        B * C <= l2_resident_capacity(vec ? kCapInitVec : kCapInitScalar, (const void *)fused[vec])) {
         // the repair kernel behind the launch serves flagged rows, lowers their flags and advances the epoch (closes the call)
-        const unsigned spins = l2_spin_limit();
-        if (vec) {
-            hipLaunchKernelGGL(pgd_l2_init_philox_fused_kernel<true>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, x, out, T, eps, lo,
-                               hi, seed, offset, w.gran0, w.fail, w.epoch, spins);
-            hipLaunchKernelGGL(pgd_l2_init_philox_repair_kernel<true>, dim3((unsigned)B), dim3(kWgThreads), 0, st, x, out, T, C, eps,
-                               lo, hi, seed, offset, w.fail, w.last, w.epoch);
-        } else {
-            hipLaunchKernelGGL(pgd_l2_init_philox_fused_kernel<false>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, x, out, T, eps, lo,
-                               hi, seed, offset, w.gran0, w.fail, w.epoch, spins);
-            hipLaunchKernelGGL(pgd_l2_init_philox_repair_kernel<false>, dim3((unsigned)B), dim3(kWgThreads), 0, st, x, out, T, C, eps,
-                               lo, hi, seed, offset, w.fail, w.last, w.epoch);
-        }
+        launch_tiles(fused, vec, B, T, st, x, out, T, eps, lo, hi, seed, offset, w.gran0, w.fail, w.epoch, l2_spin_limit());
+        launch_row_repair(ROW_KERNEL_PAIR(pgd_l2_init_philox_repair_kernel), vec, B, st, x, out, T, C, eps, lo, hi, seed, offset,
+                          w.fail, w.last, w.epoch);
         return status_after_launch();
     }
     hipLaunchKernelGGL(philox_normal_sumsq_kernel, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, T, seed, offset, w.p0);
-    ADV_LAUNCH_ROWS(pgd_l2_init_philox_kernel, vec, B, T, st, x, out, T, eps, lo, hi, seed, offset, w.p0);
+    launch_tiles(ROW_KERNEL_PAIR(pgd_l2_init_philox_kernel), vec, B, T, st, x, out, T, eps, lo, hi, seed, offset, w.p0);
     return status_after_launch();
 }
 
@@ -1092,31 +979,30 @@ int advstep_pgd_l2_step_f32(const float *adv, const float *grad, const float *or
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, grad, orig, out});
     const int C = ws_tiles_per_row(T);
-    const void *fused = vec ? (const void *)pgd_l2_fused_kernel<true> : (const void *)pgd_l2_fused_kernel<false>;
+    static constexpr decltype(&pgd_l2_fused_kernel<true>) fused[2] = ROW_KERNEL_PAIR(pgd_l2_fused_kernel);
     const size_t row_bytes = (size_t)B * T * sizeof(float);
     if (l2_single_pass() && C <= 64 && !overlaps(adv, out, row_bytes) && !overlaps(grad, out, row_bytes) &&
-        !overlaps(orig, out, row_bytes) && B * C <= l2_resident_capacity(vec ? kCapStepVec : kCapStepScalar, fused)) {
+        !overlaps(orig, out, row_bytes) &&
+        B * C <= l2_resident_capacity(vec ? kCapStepVec : kCapStepScalar, (const void *)fused[vec])) {
         // the launch fits the device's resident capacity for this kernel: one launch, 16 B per sample; the repair kernel behind
         // it serves rows whose exchange was abandoned, lowers their flags and advances the epoch (no memset node, nothing cleaned)
-        const unsigned spins = l2_spin_limit();
-        if (vec) {
-            hipLaunchKernelGGL(pgd_l2_fused_kernel<true>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, alpha,
-                               eps, eps_div, lo, hi, w.gran0, w.gran1, w.fail, w.epoch, spins, gnorm, dnorm);
-            hipLaunchKernelGGL(pgd_l2_repair_kernel<true>, dim3((unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, C, alpha,
-                               eps, eps_div, lo, hi, w.fail, w.last, w.epoch, gnorm, dnorm);
-        } else {
-            hipLaunchKernelGGL(pgd_l2_fused_kernel<false>, dim3(C, (unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, alpha,
-                               eps, eps_div, lo, hi, w.gran0, w.gran1, w.fail, w.epoch, spins, gnorm, dnorm);
-            hipLaunchKernelGGL(pgd_l2_repair_kernel<false>, dim3((unsigned)B), dim3(kWgThreads), 0, st, adv, grad, orig, out, T, C, alpha,
-                               eps, eps_div, lo, hi, w.fail, w.last, w.epoch, gnorm, dnorm);
-        }
+        launch_tiles(fused, vec, B, T, st, adv, grad, orig, out, T, alpha, eps, eps_div, lo, hi, w.gran0, w.gran1, w.fail, w.epoch,
+                     l2_spin_limit(), gnorm, dnorm);
+        launch_row_repair(ROW_KERNEL_PAIR(pgd_l2_repair_kernel), vec, B, st, adv, grad, orig, out, T, C, alpha, eps, eps_div, lo, hi,
+                          w.fail, w.last, w.epoch, gnorm, dnorm);
         return status_after_launch();
     }
-    ADV_LAUNCH_ROWS(sumsq_partial_kernel, vec, B, T, st, grad + b0 * T, T, w.p0 + b0 * C);
-    ADV_LAUNCH_ROWS(pgd_l2_delta_kernel, vec, B, T, st, adv + b0 * T, grad + b0 * T, orig + b0 * T, T, alpha, eps_div,
-                    w.p0 + b0 * C, w.p1 + b0 * C, gnorm ? gnorm + b0 : nullptr);
-    ADV_LAUNCH_ROWS(pgd_l2_project_kernel, vec, B, T, st, adv + b0 * T, grad + b0 * T, orig + b0 * T, out + b0 * T, T,
-                    alpha, eps, eps_div, lo, hi, w.p0 + b0 * C, w.p1 + b0 * C, dnorm ? dnorm + b0 : nullptr);
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(sumsq_partial_kernel), vec, nb, T, st, grad + b0 * T, T, w.p0 + b0 * C);
+    });
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(pgd_l2_delta_kernel), vec, nb, T, st, adv + b0 * T, grad + b0 * T, orig + b0 * T, T, alpha,
+                     eps_div, w.p0 + b0 * C, w.p1 + b0 * C, gnorm ? gnorm + b0 : nullptr);
+    });
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(pgd_l2_project_kernel), vec, nb, T, st, adv + b0 * T, grad + b0 * T, orig + b0 * T,
+                     out + b0 * T, T, alpha, eps, eps_div, lo, hi, w.p0 + b0 * C, w.p1 + b0 * C, dnorm ? dnorm + b0 : nullptr);
+    });
     return status_after_launch();
 }
 
@@ -1148,7 +1034,10 @@ int advstep_cw_tanh_sqdist_f32(const float *w, const float *x, float *adv, float
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {w, x, adv});
     const int C = ws_tiles_per_row(T);
-    ADV_LAUNCH_ROWS(cw_tanh_sqdist_kernel, vec, B, T, st, w + b0 * T, x + b0 * T, adv + b0 * T, T, wsp.p0 + b0 * C);
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(cw_tanh_sqdist_kernel), vec, nb, T, st, w + b0 * T, x + b0 * T, adv + b0 * T, T,
+                     wsp.p0 + b0 * C);
+    });
     hipLaunchKernelGGL(row_partials_sum_kernel, dim3((unsigned)B), dim3(64), 0, st, wsp.p0, C, l2);
     return status_after_launch();
 }
@@ -1195,7 +1084,9 @@ int advstep_cw_best_update_f32(const float *adv, const float *mask, float *best,
     ADVSTEP_REQUIRE(adv && mask && best);
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, best});
-    ADV_LAUNCH_ROWS(cw_best_update_kernel, vec, B, T, st, adv + b0 * T, mask + b0, best + b0 * T, T);
+    for_row_slabs(B, [&](int64_t b0, int64_t nb) {
+        launch_tiles(ROW_KERNEL_PAIR(cw_best_update_kernel), vec, nb, T, st, adv + b0 * T, mask + b0, best + b0 * T, T);
+    });
     return status_after_launch();
 }
 

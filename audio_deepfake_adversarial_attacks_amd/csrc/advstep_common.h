@@ -3,10 +3,10 @@
 // Each .hip file is its own translation unit and includes this once, so every helper keeps internal linkage.  Some of
 // these are rules that separate kernels must agree on bit for bit: the max-feature-map / 2x2 pool selection written by
 // the forward kernels (lcnn_conv0.hip, lcnn_wino.hip, lcnn_mfm.hip) and read back by the backward ones (lcnn_mfm.hip),
-// and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The four attack files (advstep.hip,
-// apgd.hip, momentum.hip, fab.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the
-// host's rows_vec / overlaps; what depends on the 256-thread (tile, row) geometry is in row_tiles.h, which fab.hip does not use;
-// fab.hip and apgdl1.hip give a row to one 1024-thread workgroup instead: row_workgroup.h.
+// and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The attack files (advstep.hip, apgd.hip,
+// momentum.hip, radius.hip, perturb.hip, multiattack.hip, fab.hip, apgdl1.hip) share the scalar semantics, the reduction operators
+// with the wave butterfly, and the host's rows_vec / ROW_KERNEL_PAIR / overlaps; what depends on the 256-thread (tile, row)
+// geometry is in row_tiles.h; fab.hip and apgdl1.hip give a row to one 1024-thread workgroup instead: row_workgroup.h.
 
 #ifndef ADVSTEP_COMMON_H
 #define ADVSTEP_COMMON_H
@@ -45,6 +45,10 @@ inline bool rows_vec(int64_t T, std::initializer_list<const void *> ptrs) {
         if (p && !aligned16(p)) return false;
     return true;
 }
+// The two instantiations of a row kernel whose first template parameter is VEC, indexed by rows_vec(...); further arguments are
+// the kernel's further template arguments: ROW_KERNEL_PAIR(K, 2) = {K<false, 2>, K<true, 2>}.  The only place that writes the
+// pair, so its order is fixed once; row_tiles.h's launch_tiles and row_workgroup.h's launch_rows take it.
+#define ROW_KERNEL_PAIR(KERNEL, ...) {KERNEL<false, ##__VA_ARGS__>, KERNEL<true, ##__VA_ARGS__>}
 
 inline bool overlaps(const void *a, const void *b, size_t bytes) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kWgThreads) void apgd_init_reduce_kernel(const floa
         if (norm == kNormLinf)
             acc = max_nan(acc, max_nan(max_nan(fabsf(t.x), fabsf(t.y)), max_nan(fabsf(t.z), fabsf(t.w))));
         else
-            acc += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
+            acc += sumsq4(t);
     }
     acc = (norm == kNormLinf) ? wg_max_nan(acc, lds) : wg_sum(acc, lds);
     if (threadIdx.x == 0) part[b * C + tile] = acc;
@@ -231,22 +231,7 @@ __global__ __launch_bounds__(kWgThreads) void apgd_linf_step_kernel(const float 
 
 // ---- L2 step: four row passes --------------------------------------------------------------------------------------------
 
-// pass 1: partial sum g^2
-template <bool VEC>
-__global__ __launch_bounds__(kWgThreads) void apgd_l2_gsq_kernel(const float *__restrict__ grad, int64_t T,
-                                                                 float *__restrict__ part) {
-    __shared__ float lds[4];
-    const int tile = blockIdx.x, C = gridDim.x;
-    const int64_t b = blockIdx.y;
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        const float4 g = load4<VEC>(grad + b * T, T, quad_of(tile, j), 0.0f);
-        s += (g.x * g.x + g.y * g.y) + (g.z * g.z + g.w * g.w);
-    }
-    s = wg_sum(s, lds);
-    if (threadIdx.x == 0) part[b * C + tile] = s;
-}
+// pass 1, the partial sums of g^2, is row_tiles.h's sumsq_partial_kernel
 
 struct L2Row {
     float st, gn, n1, n2, eps, a, oma;
@@ -312,10 +297,7 @@ __global__ __launch_bounds__(kWgThreads) void apgd_l2_pass_kernel(const float *_
         if (STAGE == 3) {
             store4<VEC>(out + o, T, q, v);
         } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (!in_row(T, q, k)) lane(v, k) = 0.0f;  // out-of-row lanes must not leak a 0/0 into the sum
-            s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            s += sumsq4(zero_outside_row(v, T, q));  // out-of-row lanes must not leak a 0/0 into the sum
         }
     }
     if (STAGE != 3) {
@@ -331,33 +313,11 @@ int apgd_init(const float *x, const float *draw, float *out, int64_t B, int64_t 
               uint64_t seed, uint64_t offset, void *ws, size_t ws_bytes, hipStream_t st) {
     RowWs w;
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
-    const dim3 grid = row_grid(B, T);
-    if (rows_vec(T, {x, draw, out})) {
-        hipLaunchKernelGGL((apgd_init_reduce_kernel<true, PHILOX>), grid, dim3(kWgThreads), 0, st, draw, T, norm, seed, offset,
-                           w.p0);
-        hipLaunchKernelGGL((apgd_init_apply_kernel<true, PHILOX>), grid, dim3(kWgThreads), 0, st, x, draw, out, T, norm, eps,
-                           lo, hi, seed, offset, (const float *)w.p0);
-    } else {
-        hipLaunchKernelGGL((apgd_init_reduce_kernel<false, PHILOX>), grid, dim3(kWgThreads), 0, st, draw, T, norm, seed,
-                           offset, w.p0);
-        hipLaunchKernelGGL((apgd_init_apply_kernel<false, PHILOX>), grid, dim3(kWgThreads), 0, st, x, draw, out, T, norm, eps,
-                           lo, hi, seed, offset, (const float *)w.p0);
-    }
+    const bool vec = rows_vec(T, {x, draw, out});
+    launch_tiles(ROW_KERNEL_PAIR(apgd_init_reduce_kernel, PHILOX), vec, B, T, st, draw, T, norm, seed, offset, w.p0);
+    launch_tiles(ROW_KERNEL_PAIR(apgd_init_apply_kernel, PHILOX), vec, B, T, st, x, draw, out, T, norm, eps, lo, hi, seed, offset,
+                 w.p0);
     return status_after_launch();
-}
-
-template <bool VEC>
-void launch_l2_passes(const float *cur, const float *prev, const float *grad, const float *x, const float *step_size,
-                      float *out, float *norms, int64_t B, int64_t T, float eps, float a, float oma, const RowWs &w,
-                      hipStream_t st) {
-    const dim3 grid = row_grid(B, T);
-    hipLaunchKernelGGL((apgd_l2_gsq_kernel<VEC>), grid, dim3(kWgThreads), 0, st, grad, T, w.p0);
-    hipLaunchKernelGGL((apgd_l2_pass_kernel<VEC, 1>), grid, dim3(kWgThreads), 0, st, cur, prev, grad, x, step_size, out,
-                       norms, T, eps, a, oma, (const float *)w.p0, w.p1);
-    hipLaunchKernelGGL((apgd_l2_pass_kernel<VEC, 2>), grid, dim3(kWgThreads), 0, st, cur, prev, grad, x, step_size, out,
-                       norms, T, eps, a, oma, (const float *)w.p1, w.p0);
-    hipLaunchKernelGGL((apgd_l2_pass_kernel<VEC, 3>), grid, dim3(kWgThreads), 0, st, cur, prev, grad, x, step_size, out,
-                       norms, T, eps, a, oma, (const float *)w.p0, (float *)nullptr);
 }
 
 }  // namespace
@@ -407,12 +367,8 @@ int advstep_apgd_track_f32(float *x_adv, float *grad, float *x_best, float *grad
     if (B == 0 || T == 0) return ADVSTEP_OK;
     ADVSTEP_REQUIRE(x_adv && grad && x_best && grad_best && x_best_adv && flags);
     hipStream_t st = as_stream(stream);
-    if (rows_vec(T, {x_adv, grad, x_best, grad_best, x_best_adv}))
-        hipLaunchKernelGGL(apgd_track_kernel<true>, row_grid(B, T), dim3(kWgThreads), 0, st, x_adv, grad, x_best, grad_best,
-                           x_best_adv, flags, T);
-    else
-        hipLaunchKernelGGL(apgd_track_kernel<false>, row_grid(B, T), dim3(kWgThreads), 0, st, x_adv, grad, x_best, grad_best,
-                           x_best_adv, flags, T);
+    launch_tiles(ROW_KERNEL_PAIR(apgd_track_kernel), rows_vec(T, {x_adv, grad, x_best, grad_best, x_best_adv}), B, T, st, x_adv,
+                 grad, x_best, grad_best, x_best_adv, flags, T);
     return status_after_launch();
 }
 
@@ -425,12 +381,8 @@ int advstep_apgd_linf_step_f32(const float *cur, const float *prev, const float 
     ADVSTEP_REQUIRE(!overlaps(out, cur, bytes) && !overlaps(out, grad, bytes) && !overlaps(out, x, bytes));
     hipStream_t st = as_stream(stream);
     const float af = (float)a, oma = (float)(1.0 - a);
-    if (rows_vec(T, {cur, prev, grad, x, out}))
-        hipLaunchKernelGGL(apgd_linf_step_kernel<true>, row_grid(B, T), dim3(kWgThreads), 0, st, cur, prev, grad, x, step_size,
-                           out, T, eps, af, oma);
-    else
-        hipLaunchKernelGGL(apgd_linf_step_kernel<false>, row_grid(B, T), dim3(kWgThreads), 0, st, cur, prev, grad, x, step_size,
-                           out, T, eps, af, oma);
+    launch_tiles(ROW_KERNEL_PAIR(apgd_linf_step_kernel), rows_vec(T, {cur, prev, grad, x, out}), B, T, st, cur, prev, grad, x,
+                 step_size, out, T, eps, af, oma);
     return status_after_launch();
 }
 
@@ -446,10 +398,14 @@ int advstep_apgd_l2_step_f32(const float *cur, const float *prev, const float *g
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const float af = (float)a, oma = (float)(1.0 - a);
-    if (rows_vec(T, {cur, prev, grad, x, out}))
-        launch_l2_passes<true>(cur, prev, grad, x, step_size, out, norms, B, T, eps, af, oma, w, st);
-    else
-        launch_l2_passes<false>(cur, prev, grad, x, step_size, out, norms, B, T, eps, af, oma, w, st);
+    const bool vec = rows_vec(T, {cur, prev, grad, x, out});
+    launch_tiles(ROW_KERNEL_PAIR(sumsq_partial_kernel), vec, B, T, st, grad, T, w.p0);
+    launch_tiles(ROW_KERNEL_PAIR(apgd_l2_pass_kernel, 1), vec, B, T, st, cur, prev, grad, x, step_size, out, norms, T, eps, af, oma,
+                 w.p0, w.p1);
+    launch_tiles(ROW_KERNEL_PAIR(apgd_l2_pass_kernel, 2), vec, B, T, st, cur, prev, grad, x, step_size, out, norms, T, eps, af, oma,
+                 w.p1, w.p0);
+    launch_tiles(ROW_KERNEL_PAIR(apgd_l2_pass_kernel, 3), vec, B, T, st, cur, prev, grad, x, step_size, out, norms, T, eps, af, oma,
+                 w.p0, nullptr);
     return status_after_launch();
 }
 

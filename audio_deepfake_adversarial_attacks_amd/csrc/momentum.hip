@@ -89,20 +89,6 @@ __global__ __launch_bounds__(kWgThreads) void mi_apply_kernel(const float *adv, 
     }
 }
 
-template <bool VEC, bool HASV>
-void launch_mi(const float *adv, const float *grad, const float *v, const float *orig, float *momentum, float *out,
-               float *nes_out, int64_t B, int64_t T, float alpha, float eps, float decay, float nes_scale, float lo, float hi,
-               float *gmean, const RowWs &w, hipStream_t st) {
-    const dim3 grid = row_grid(B, T);
-    hipLaunchKernelGGL((mi_abs_sum_kernel<VEC, HASV>), grid, dim3(kWgThreads), 0, st, grad, v, T, w.p0);
-    if (nes_out)
-        hipLaunchKernelGGL((mi_apply_kernel<VEC, HASV, true>), grid, dim3(kWgThreads), 0, st, adv, grad, v, orig, momentum, out,
-                           nes_out, T, alpha, eps, decay, nes_scale, lo, hi, gmean, (const float *)w.p0);
-    else
-        hipLaunchKernelGGL((mi_apply_kernel<VEC, HASV, false>), grid, dim3(kWgThreads), 0, st, adv, grad, v, orig, momentum, out,
-                           nes_out, T, alpha, eps, decay, nes_scale, lo, hi, gmean, (const float *)w.p0);
-}
-
 // ---- variance tuning: flat kernels, the buffer of n samples as one row of n ----------------------------------------------
 
 struct NeighborNoise {   // out = adv + draw
@@ -141,11 +127,8 @@ __global__ __launch_bounds__(kWgThreads) void flat_kernel(const float *in0, cons
 
 template <int NIN, class Op>
 int launch_flat(const float *in0, const float *in1, float *out, int64_t n, Op op, hipStream_t st) {
-    const dim3 grid((unsigned)ceil_div(n, kWsRowTile));
-    if (rows_vec(n, {in0, in1, out}))
-        hipLaunchKernelGGL((flat_kernel<true, NIN, Op>), grid, dim3(kWgThreads), 0, st, in0, in1, out, n, op);
-    else
-        hipLaunchKernelGGL((flat_kernel<false, NIN, Op>), grid, dim3(kWgThreads), 0, st, in0, in1, out, n, op);
+    // the buffer as one row of n samples: grid = (tiles, 1)
+    launch_tiles(ROW_KERNEL_PAIR(flat_kernel, NIN, Op), rows_vec(n, {in0, in1, out}), 1, n, st, in0, in1, out, n, op);
     return status_after_launch();
 }
 
@@ -174,14 +157,15 @@ int advstep_mi_step_f32(const float *adv, const float *grad, const float *v, con
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, grad, v, orig, momentum, out, nes_out});
-    if (vec && v)
-        launch_mi<true, true>(adv, grad, v, orig, momentum, out, nes_out, B, T, alpha, eps, decay, nes_scale, lo, hi, gmean, w, st);
-    else if (vec)
-        launch_mi<true, false>(adv, grad, v, orig, momentum, out, nes_out, B, T, alpha, eps, decay, nes_scale, lo, hi, gmean, w, st);
-    else if (v)
-        launch_mi<false, true>(adv, grad, v, orig, momentum, out, nes_out, B, T, alpha, eps, decay, nes_scale, lo, hi, gmean, w, st);
-    else
-        launch_mi<false, false>(adv, grad, v, orig, momentum, out, nes_out, B, T, alpha, eps, decay, nes_scale, lo, hi, gmean, w, st);
+    // [v given] and [v given][nes_out given]
+    static constexpr decltype(&mi_abs_sum_kernel<true, true>) abs_sum[2][2] = {ROW_KERNEL_PAIR(mi_abs_sum_kernel, false),
+                                                                               ROW_KERNEL_PAIR(mi_abs_sum_kernel, true)};
+    static constexpr decltype(&mi_apply_kernel<true, true, true>) apply[2][2][2] = {
+        {ROW_KERNEL_PAIR(mi_apply_kernel, false, false), ROW_KERNEL_PAIR(mi_apply_kernel, false, true)},
+        {ROW_KERNEL_PAIR(mi_apply_kernel, true, false), ROW_KERNEL_PAIR(mi_apply_kernel, true, true)}};
+    launch_tiles(abs_sum[v != nullptr], vec, B, T, st, grad, v, T, w.p0);
+    launch_tiles(apply[v != nullptr][nes_out != nullptr], vec, B, T, st, adv, grad, v, orig, momentum, out, nes_out, T, alpha, eps,
+                 decay, nes_scale, lo, hi, gmean, w.p0);
     return status_after_launch();
 }
 

@@ -85,12 +85,7 @@ extern "C" int advstep_multi_route_f32(const float *adv, const float *x, const f
     ADVSTEP_REQUIRE(!overlaps(next_y, labels, (size_t)n * sizeof(int64_t)) && !overlaps(next_rows, rows, (size_t)n * sizeof(int32_t)));
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(multi_select_kernel, dim3(1), dim3(64), 0, st, z, labels, rows, n, B, scratch, next_y, next_rows, counts);
-    const dim3 grid = row_grid(n, T);
-    if (rows_vec(T, {adv, x, final_rows, next_x}))
-        hipLaunchKernelGGL((multi_copy_kernel<true>), grid, dim3(kWgThreads), 0, st, adv, x, (const int32_t *)scratch,
-                           final_rows, next_x, T);
-    else
-        hipLaunchKernelGGL((multi_copy_kernel<false>), grid, dim3(kWgThreads), 0, st, adv, x, (const int32_t *)scratch,
-                           final_rows, next_x, T);
+    launch_tiles(ROW_KERNEL_PAIR(multi_copy_kernel), rows_vec(T, {adv, x, final_rows, next_x}), n, T, st, adv, x, scratch, final_rows,
+                 next_x, T);
     return status_after_launch();
 }

@@ -137,10 +137,7 @@ extern "C" int advstep_perturb_stats_f32(const float *x, const float *adv, float
         ADVSTEP_REQUIRE(!ranges_overlap(ws, need, stats, out));
         if (!aligned16(ws) || ws_bytes < need) return ADVSTEP_EWORKSPACE;
         float *part = static_cast<float *>(ws);
-        if (rows_vec(T, {x, adv}))
-            hipLaunchKernelGGL((perturb_partials_kernel<true>), row_grid(B, T), dim3(kWgThreads), 0, st, x, adv, T, part, plane);
-        else
-            hipLaunchKernelGGL((perturb_partials_kernel<false>), row_grid(B, T), dim3(kWgThreads), 0, st, x, adv, T, part, plane);
+        launch_tiles(ROW_KERNEL_PAIR(perturb_partials_kernel), rows_vec(T, {x, adv}), B, T, st, x, adv, T, part, plane);
     }
     hipLaunchKernelGGL(perturb_finish_kernel, dim3((unsigned)B), dim3(kWgThreads), 0, st, (const float *)ws, plane, C, T, stats);
     return status_after_launch();

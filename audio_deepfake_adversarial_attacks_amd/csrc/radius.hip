@@ -57,7 +57,8 @@ __global__ __launch_bounds__(kWgThreads) void row_linf_step_kernel(const float *
 
 // ---- b. L2 step ------------------------------------------------------------------------------------------------------------
 
-// pass 1 is row_tiles.h's sumsq_partial_kernel; passes 2 and 3 are its l2_delta_pass / l2_project_pass with the row's a and e
+// pass 1 is row_tiles.h's sumsq_partial_kernel; passes 2 and 3 are its l2_delta_pass / l2_project_pass (built on l2_move4,
+// l2_scale_factor and l2_project4, like advstep.hip's step kernels) with the row's a and e
 template <bool VEC>
 __global__ __launch_bounds__(kWgThreads) void row_l2_delta_kernel(const float *__restrict__ adv, const float *__restrict__ grad,
                                                                   const float *__restrict__ orig,
@@ -145,15 +146,6 @@ inline bool step_aliasing_ok(const float *adv, const float *grad, const float *o
     return true;
 }
 
-// One launch of a VEC-templated row kernel over the (tile, row) grid.
-#define RADIUS_LAUNCH(KERNEL, VECFLAG, B, T, st, ...)                                                        \
-    do {                                                                                                     \
-        if (VECFLAG)                                                                                         \
-            hipLaunchKernelGGL((KERNEL<true>), row_grid(B, T), dim3(kWgThreads), 0, st, __VA_ARGS__);        \
-        else                                                                                                 \
-            hipLaunchKernelGGL((KERNEL<false>), row_grid(B, T), dim3(kWgThreads), 0, st, __VA_ARGS__);       \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -167,7 +159,7 @@ int advstep_row_pgd_linf_step_f32(const float *adv, const float *grad, const flo
     ADVSTEP_REQUIRE(step_aliasing_ok(adv, grad, orig, out, B, T, {eps_rows}));
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, grad, orig, out});
-    RADIUS_LAUNCH(row_linf_step_kernel, vec, B, T, st, adv, grad, orig, eps_rows, out, T, alpha_abs, alpha_rel, lo, hi);
+    launch_tiles(ROW_KERNEL_PAIR(row_linf_step_kernel), vec, B, T, st, adv, grad, orig, eps_rows, out, T, alpha_abs, alpha_rel, lo, hi);
     return status_after_launch();
 }
 
@@ -182,11 +174,11 @@ int advstep_row_pgd_l2_step_f32(const float *adv, const float *grad, const float
     if (!carve_ws(ws, ws_bytes, B, T, &w)) return ADVSTEP_EWORKSPACE;
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, grad, orig, out});
-    RADIUS_LAUNCH(sumsq_partial_kernel, vec, B, T, st, grad, T, w.p0);
-    RADIUS_LAUNCH(row_l2_delta_kernel, vec, B, T, st, adv, grad, orig, eps_rows, T, alpha_abs, alpha_rel, eps_div,
-                  (const float *)w.p0, w.p1, gnorm);
-    RADIUS_LAUNCH(row_l2_project_kernel, vec, B, T, st, adv, grad, orig, eps_rows, out, T, alpha_abs, alpha_rel, eps_div, lo, hi,
-                  (const float *)w.p0, (const float *)w.p1, dnorm);
+    launch_tiles(ROW_KERNEL_PAIR(sumsq_partial_kernel), vec, B, T, st, grad, T, w.p0);
+    launch_tiles(ROW_KERNEL_PAIR(row_l2_delta_kernel), vec, B, T, st, adv, grad, orig, eps_rows, T, alpha_abs, alpha_rel, eps_div,
+                 w.p0, w.p1, gnorm);
+    launch_tiles(ROW_KERNEL_PAIR(row_l2_project_kernel), vec, B, T, st, adv, grad, orig, eps_rows, out, T, alpha_abs, alpha_rel,
+                 eps_div, lo, hi, w.p0, w.p1, dnorm);
     return status_after_launch();
 }
 
@@ -217,7 +209,7 @@ int advstep_radius_round_f32(const float *adv, const float *z, const int64_t *la
                     !overlap2(best_adv, rows, labels, (size_t)B * sizeof(int64_t)));
     hipStream_t st = as_stream(stream);
     const bool vec = rows_vec(T, {adv, best_adv});
-    RADIUS_LAUNCH(radius_round_kernel, vec, B, T, st, adv, z, labels, first, state, state_out, best_adv, B, T);
+    launch_tiles(ROW_KERNEL_PAIR(radius_round_kernel), vec, B, T, st, adv, z, labels, first, state, state_out, best_adv, B, T);
     return status_after_launch();
 }
 

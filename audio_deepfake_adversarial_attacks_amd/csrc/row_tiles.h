@@ -1,6 +1,7 @@
-// row_tiles.h — the (tile, row) addressing of every row kernel (advstep.hip, apgd.hip, momentum.hip, radius.hip) and the re-reduction of a
-// row's per-tile partials (internal, like advstep_common.h, which has the rules that do not depend on this 256-thread tile:
-// scalar semantics, reductions, rows_vec, overlaps).
+// row_tiles.h — the (tile, row) geometry of the 256-thread row kernels (advstep.hip, apgd.hip, momentum.hip, radius.hip, perturb.hip,
+// multiattack.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2 arithmetic that several kernels must
+// agree on bit for bit, and the launch on the (tile, row) grid (internal, like advstep_common.h, which has the rules that do not
+// depend on this tile: scalar semantics, reductions, rows_vec, ROW_KERNEL_PAIR, overlaps).
 //
 // grid = (C tiles of 4096 samples, B rows), 256 threads, 4 float4 per thread and stream; float4 q of a row is loaded whole when
 // the rows are float4-addressable (VEC) and sample by sample otherwise (T % 4 != 0 leaves rows 2 .. B unaligned).  Tile c of
@@ -91,7 +92,50 @@ __device__ __forceinline__ float row_min(const float *__restrict__ part, int C, 
     return wg_min_nan(v, lds);
 }
 
-// ---- row sum of squares (||grad||^2, ||normal||^2): one partial per (row, tile); advstep.hip and radius.hip launch it ------------
+// ---- the L2 arithmetic: one body per expression -------------------------------------------------------------------------------
+// Several kernels promise the same bits for the same row (the three-launch PGD-L2 step, its single-pass and repair kernels in
+// advstep.hip, radius.hip's per-row step, apgd.hip's row norms); what they must agree on is written once, here.  The helpers
+// work on one quad: the single-pass kernel reads `orig` back from LDS quad by quad, and the repair kernels loop over tiles.
+
+// A thread's sum of squares: a quad as (x^2 + y^2) + (z^2 + w^2), the tile's kVecs quads one after the other.  The order is part
+// of every norm's bits (radius.hip's header derives the tests' bounds from it).
+__device__ __forceinline__ float sumsq4(float4 v) { return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w); }
+__device__ __forceinline__ float tile_sumsq(const float4 (&r)[kVecs]) {
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) s += sumsq4(r[j]);
+    return s;
+}
+
+// Samples of quad q outside the row -> 0, where a neutral `fill` cannot be relied on (a 0 / 0 or a NaN norm must not leak into a sum).
+__device__ __forceinline__ float4 zero_outside_row(float4 d, int64_t T, int64_t q) {
+    if (!in_row(T, q, 0)) d.x = 0.0f;
+    if (!in_row(T, q, 1)) d.y = 0.0f;
+    if (!in_row(T, q, 2)) d.z = 0.0f;
+    if (!in_row(T, q, 3)) d.w = 0.0f;
+    return d;
+}
+
+// The PGD-L2 move of one quad: d = (adv + alpha * (g / gn)) - orig.
+__device__ __forceinline__ float4 l2_move4(float4 a, float4 g, float4 x, float alpha, float gn) {
+    return make_float4((a.x + alpha * (g.x / gn)) - x.x, (a.y + alpha * (g.y / gn)) - x.y, (a.z + alpha * (g.z / gn)) - x.z,
+                       (a.w + alpha * (g.w / gn)) - x.w);
+}
+
+// f = min((1 / dn) * eps, 1).  ZERO_NORM_KEEPS: f = 1 when dn == 0 — what min(inf * eps, 1) gives for every eps > 0 — also at
+// eps = 0, where inf * 0 would be NaN (radius.hip's radius-0 rows).
+template <bool ZERO_NORM_KEEPS>
+__device__ __forceinline__ float l2_scale_factor(float dn, float eps) {
+    return (ZERO_NORM_KEEPS && dn == 0.0f) ? 1.0f : min_nan((1.0f / dn) * eps, 1.0f);
+}
+
+// The projection of one quad: clamp(orig + d * f, lo, hi).
+__device__ __forceinline__ float4 l2_project4(float4 x, float4 d, float f, float lo, float hi) {
+    return make_float4(clampf(x.x + d.x * f, lo, hi), clampf(x.y + d.y * f, lo, hi), clampf(x.z + d.z * f, lo, hi),
+                       clampf(x.w + d.w * f, lo, hi));
+}
+
+// ---- row sum of squares (||grad||^2, ||normal||^2): one partial per (row, tile); advstep.hip, apgd.hip and radius.hip launch it ---
 
 template <bool VEC>
 __global__ __launch_bounds__(kWgThreads) void sumsq_partial_kernel(const float *__restrict__ g, int64_t T,
@@ -101,17 +145,14 @@ __global__ __launch_bounds__(kWgThreads) void sumsq_partial_kernel(const float *
     const int64_t b = blockIdx.y;
     float4 r[kVecs];
     load_tile<VEC>(g + b * T, T, tile, 0.0f, r);
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) s += (r[j].x * r[j].x + r[j].y * r[j].y) + (r[j].z * r[j].z + r[j].w * r[j].w);
-    s = wg_sum(s, lds);
+    const float s = wg_sum(tile_sumsq(r), lds);
     if (threadIdx.x == 0) part[b * C + tile] = s;
 }
 
 // ---- the PGD-L2 step's two row passes (advstep.hip: launch scalars alpha, eps; radius.hip: the row's a, e) ---------------------
 // One body each, so the fixed-radius and the per-row kernels agree bit for bit by construction.  `lds` holds >= 8 floats.
 
-// pass 2: gn from the grad partials; a = adv + alpha * (g / gn); d = a - orig; partial sum d^2
+// pass 2: gn from the grad partials; d = l2_move4; partial sum d^2
 template <bool VEC>
 __device__ __forceinline__ void l2_delta_pass(const float *__restrict__ adv, const float *__restrict__ grad,
                                               const float *__restrict__ orig, int64_t T, float alpha, float eps_div,
@@ -126,21 +167,10 @@ __device__ __forceinline__ void l2_delta_pass(const float *__restrict__ adv, con
     const float gsq = row_sum(gpart + b * C, C, lds);
     const float gn_raw = sqrtf(gsq);
     const float gn = gn_raw + eps_div;
+    // out-of-row lanes: a = g = x = 0 -> d = 0 when gn != 0; masked explicitly so gn == 0 / NaN cannot leak
     float s = 0.0f;
 #pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        float4 d;
-        d.x = (a[j].x + alpha * (g[j].x / gn)) - x[j].x;
-        d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
-        d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
-        d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-        // out-of-row lanes: a = g = x = 0 -> d = 0 when gn != 0; mask explicitly so gn == 0 / NaN cannot leak
-        if (!in_row(T, quad_of(tile, j), 0)) d.x = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 1)) d.y = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 2)) d.z = 0.0f;
-        if (!in_row(T, quad_of(tile, j), 3)) d.w = 0.0f;
-        s += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-    }
+    for (int j = 0; j < kVecs; ++j) s += sumsq4(zero_outside_row(l2_move4(a[j], g[j], x[j], alpha, gn), T, quad_of(tile, j)));
     s = wg_sum(s, lds + 4);
     if (threadIdx.x == 0) {
         dpart[b * C + tile] = s;
@@ -148,9 +178,8 @@ __device__ __forceinline__ void l2_delta_pass(const float *__restrict__ adv, con
     }
 }
 
-// pass 3: recompute d, f = min((1/dn) * eps, 1), out = clamp(orig + d * f, lo, hi).  out may be adv (a thread reads its own
-// samples before it writes them).  ZERO_NORM_KEEPS: f = 1 when dn == 0 — what min(inf * eps, 1) gives for every eps > 0 — also at
-// eps = 0, where inf * 0 would be NaN (radius.hip's radius-0 rows).
+// pass 3: recompute d, f = l2_scale_factor, out = l2_project4.  out may be adv (a thread reads its own samples before it writes
+// them).
 template <bool VEC, bool ZERO_NORM_KEEPS>
 __device__ __forceinline__ void l2_project_pass(const float *adv, const float *__restrict__ grad,
                                                 const float *__restrict__ orig, float *out, int64_t T, float alpha, float eps,
@@ -164,26 +193,68 @@ __device__ __forceinline__ void l2_project_pass(const float *adv, const float *_
     load_tile<VEC>(orig + b * T, T, tile, 0.0f, x);
     const float gn = sqrtf(row_sum(gpart + b * C, C, lds)) + eps_div;
     const float dn = sqrtf(row_sum(dpart + b * C, C, lds + 4));
-    const float f = (ZERO_NORM_KEEPS && dn == 0.0f) ? 1.0f : min_nan((1.0f / dn) * eps, 1.0f);
+    const float f = l2_scale_factor<ZERO_NORM_KEEPS>(dn, eps);
 #pragma unroll
-    for (int j = 0; j < kVecs; ++j) {
-        float4 d;
-        d.x = (a[j].x + alpha * (g[j].x / gn)) - x[j].x;
-        d.y = (a[j].y + alpha * (g[j].y / gn)) - x[j].y;
-        d.z = (a[j].z + alpha * (g[j].z / gn)) - x[j].z;
-        d.w = (a[j].w + alpha * (g[j].w / gn)) - x[j].w;
-        a[j].x = clampf(x[j].x + d.x * f, lo, hi);
-        a[j].y = clampf(x[j].y + d.y * f, lo, hi);
-        a[j].z = clampf(x[j].z + d.z * f, lo, hi);
-        a[j].w = clampf(x[j].w + d.w * f, lo, hi);
-    }
+    for (int j = 0; j < kVecs; ++j) a[j] = l2_project4(x[j], l2_move4(a[j], g[j], x[j], alpha, gn), f, lo, hi);
     store_tile<VEC>(out + b * T, T, tile, a);
     if (tile == 0 && threadIdx.x == 0 && dnorm) dnorm[b] = dn;
+}
+
+// ---- the PGD-L2 random start from Philox (advstep.hip's two-kernel, single-pass and repair kernels) ---------------------------
+
+// Philox normals for this thread's kVecs quads of (row b, tile); out-of-row samples are zeroed.
+__device__ __forceinline__ void philox_normal_tile(int64_t T, int tile, uint32_t b, uint64_t seed, uint64_t offset,
+                                                   float4 (&nz)[kVecs]) {
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) {
+        const int64_t q = quad_of(tile, j);
+        if (in_row(T, q, 0)) {
+            nz[j] = philox_normal4((uint32_t)q, b, seed, offset);
+            if (!in_row(T, q, 1)) nz[j].y = 0.0f;
+            if (!in_row(T, q, 2)) nz[j].z = 0.0f;
+            if (!in_row(T, q, 3)) nz[j].w = 0.0f;
+        } else {
+            nz[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+}
+
+// The row's scale (r / ||n||) * eps, r = the first uniform of counter (b, offset + 1).
+__device__ __forceinline__ float philox_start_scale(int64_t b, uint64_t seed, uint64_t offset, float nrm, float eps) {
+    const uint64_t off1 = offset + 1;
+    const Quad rq = philox4x32_10((uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)off1, (uint32_t)(off1 >> 32),
+                                  (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (u01(rq.v[0]) / nrm) * eps;
+}
+
+// xv = clamp(xv + nz * scale, lo, hi) over a tile (explicit draws and Philox alike).
+__device__ __forceinline__ void l2_start_apply(float4 (&xv)[kVecs], const float4 (&nz)[kVecs], float scale, float lo, float hi) {
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) {
+        xv[j].x = clampf(xv[j].x + nz[j].x * scale, lo, hi);
+        xv[j].y = clampf(xv[j].y + nz[j].y * scale, lo, hi);
+        xv[j].z = clampf(xv[j].z + nz[j].z * scale, lo, hi);
+        xv[j].w = clampf(xv[j].w + nz[j].w * scale, lo, hi);
+    }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 
 inline dim3 row_grid(int64_t B, int64_t T) { return dim3((unsigned)ws_tiles_per_row(T), (unsigned)B); }
+
+// One launch of pair[vec] (a ROW_KERNEL_PAIR: [1] where the rows are float4-addressable) on the (tile, row) grid of B rows.  The
+// arguments convert to the kernel's own parameter types, as in a direct call; the status is read by the caller after its last launch.
+template <class... P, class... A>
+void launch_tiles(void (*const (&pair)[2])(P...), bool vec, int64_t B, int64_t T, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(pair[vec], row_grid(B, T), dim3(kWgThreads), 0, stream, args...);
+}
+
+// f(b0, nb) for every slab of at most kMaxGridY rows (grid.y is 16 bits): rows b0 .. b0 + nb of B.  Only advstep.hip slabs; the
+// other files reject B > kMaxGridY.
+template <class F>
+void for_row_slabs(int64_t B, F f) {
+    for (int64_t b0 = 0; b0 < B; b0 += kMaxGridY) f(b0, B - b0 < kMaxGridY ? B - b0 : kMaxGridY);
+}
 
 }  // namespace
 

@@ -3,8 +3,8 @@
 // One workgroup of kRow = 1024 threads (16 wave64) owns one row of T samples and makes several passes over it; at the repo's
 // T = 64 600 a row is 258 KB: it does not fit LDS, but stays L2 / Infinity-Cache resident between the passes, so only the first
 // pass reads HBM.  This header holds what those kernels share: the 16-wave reduction, the row traversal (whose order is part of
-// every reduced result's bits) and the launch helper.  Include after advstep_common.h (wave_reduce, status_after_launch,
-// kMaxGridY).  The 256-thread (tile, row) geometry of the other attack files is row_tiles.h.
+// every reduced result's bits) and the launch helper.  Include after advstep_common.h (wave_reduce, ROW_KERNEL_PAIR,
+// status_after_launch, kMaxGridY).  The 256-thread (tile, row) geometry of the other attack files is row_tiles.h.
 
 #ifndef ADVSTEP_ROW_WORKGROUP_H
 #define ADVSTEP_ROW_WORKGROUP_H
@@ -96,9 +96,7 @@ __device__ __forceinline__ void map_rows(const float *const (&in)[N], float *out
 
 inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }
 
-// One kRow-thread workgroup per row (the kernels stride on past kMaxGridY rows): k[1] where the rows are float4-addressable.
-// ROW_KERNEL_PAIR is the only place that writes the pair, so its order is fixed once.
-#define ROW_KERNEL_PAIR(KERNEL) {KERNEL<false>, KERNEL<true>}
+// One kRow-thread workgroup per row (the kernels stride on past kMaxGridY rows): k is a ROW_KERNEL_PAIR (advstep_common.h).
 template <class... P, class... A>
 int launch_rows(void (*const (&k)[2])(P...), bool vec, int64_t rows, advstep_stream_t stream, A... args) {
     hipLaunchKernelGGL(k[vec], dim3(grid_rows(rows)), dim3(kRow), 0, as_stream(stream), args...);

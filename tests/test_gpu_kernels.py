@@ -397,6 +397,35 @@ def test_pgd_l2_repair_pass_when_the_exchange_is_abandoned(cuda, monkeypatch, B,
     assert torch.equal(want_init, rep_init) and torch.isfinite(rep[0]).all()
 
 
+@pytest.mark.parametrize("B,T", [(1, 257), (5, 4_099), (3, 8_192), (7, 12_289)])
+def test_row_gradient_norm_is_the_same_bits_on_every_route(cuda, monkeypatch, B, T):
+    """||grad|| of a row is one value however it is reached: pgd_l2_step's three-kernel, single-pass and repair paths,
+    row_pgd_l2_step and apgd_l2_step (column 0) all sum the squares with row_tiles.h's tile_sumsq and re-reduce the same
+    partials.  One tile and several, T % 4 zero and not, a last tile partly outside the row, one all-zero gradient row."""
+    from audio_deepfake_adversarial_attacks_amd import hip_ops
+    adv, grad, orig = _l2_inputs(B, T, cuda)
+    if B > 1:
+        grad[B - 1] = 0.0
+    gn = {}
+    for route, mode, spins in (("three kernels", "0", None), ("single pass", "1", None), ("repair", "1", "0")):
+        monkeypatch.setenv("ADVSTEP_L2_SINGLE_PASS", mode)
+        if spins is None:
+            monkeypatch.delenv("ADVSTEP_L2_SPIN_LIMIT", raising=False)
+        else:
+            monkeypatch.setenv("ADVSTEP_L2_SPIN_LIMIT", spins)
+        gn[route] = hip_ops.pgd_l2_step(adv, grad, orig, 0.2, 0.1, return_norms=True)[1]
+    assert hip_ops.pgd_l2_repaired_rows(adv) == B                   # the last call did go through the repair kernel
+    monkeypatch.delenv("ADVSTEP_L2_SPIN_LIMIT")
+    radii = torch.full((B,), 0.1, device=cuda)
+    gn["row step"] = hip_ops.row_pgd_l2_step(adv, grad, orig, radii, 0.0, 2.0, return_norms=True)[1]
+    steps = torch.full((B,), 0.05, device=cuda)
+    gn["apgd"] = hip_ops.apgd_l2_step(adv, orig, grad, orig, steps, 0.1, 0.75, return_norms=True)[1][:, 0].contiguous()
+    want = gn.pop("three kernels")
+    assert (want[:max(B - 1, 1)] > 0).all() and (B == 1 or want[B - 1] == 0)
+    for route, got in gn.items():
+        assert torch.equal(got, want), (route, (got - want).abs().max().item())
+
+
 def test_pgd_l2_single_pass_respects_device_capacity_and_aliasing(cuda, monkeypatch):
     """The single-pass path is taken only when the launch fits the device's resident capacity for the kernel (CU count x
     occupancy, queried from the runtime — ADVSTEP_L2_CAPACITY stands in for a smaller / partitioned device) and when `out`

@@ -6,7 +6,7 @@ which is the situation inside a PGD loop) and "cold" rotates over enough buffer 
 Times come from one HIP-event pair around a burst of back-to-back launches on torch's current stream.
 Also the target of the rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE per launch; see profiles/README.md).
 
-    python tools/kernel_microbench.py [--batch 128] [--launches 50] [--only pgd_linf_step] [--json out.json]
+    python tools/kernel_microbench.py [--batch 128] [--launches 50] [--only pgd_l2_step,mi_step] [--json out.json]
 """
 import argparse
 import json
@@ -27,9 +27,10 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--sets", type=int, default=5, help="buffer sets for the cold regime")
-    ap.add_argument("--only", default=None)
+    ap.add_argument("--only", default=None, help="comma-separated case names")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    only = set(a.only.split(",")) if a.only else None
     dev = torch.device("cuda:0")
     B, n_sets = a.batch, a.sets
     n = B * T
@@ -44,6 +45,8 @@ def main():
     mx = mn + 1.5
     mask = (torch.arange(B, device=dev) % 2).float()
     r = torch.rand(B, device=dev)
+    step = torch.full((B,), 0.05, device=dev)
+    radii = torch.full((B,), 0.1, device=dev)
 
     # name -> (callable(set index), algorithmic bytes per sample)
     cases = {
@@ -59,6 +62,12 @@ def main():
         "cw_tanh_sqdist": (lambda i: ops.cw_tanh_sqdist(w[i], x[i], adv_out=out[i]), 12),
         "cw_adam_step": (lambda i: ops.cw_adam_step(w[i], m[i], v[i], x[i], grad[i], 3), 32),
         "cw_best_update": (lambda i: ops.cw_best_update(adv[i], mask, best[i]), 12),
+        # four row passes: grad x4, cur x3, x x3, prev x2, out x1
+        "apgd_l2_step": (lambda i: ops.apgd_l2_step(adv[i], best[i], grad[i], x[i], step, 0.1, 0.75, out=out[i]), 52),
+        # three row passes: grad x3, adv x2, orig x2, out x1
+        "row_pgd_l2_step": (lambda i: ops.row_pgd_l2_step(adv[i], grad[i], x[i], radii, 0.0, 2.0, out=out[i]), 32),
+        # two row passes: grad x2, momentum in and back, adv, orig, out
+        "mi_step": (lambda i: ops.mi_step(adv[i], grad[i], x[i], m[i], 2 / 255, 8 / 255, 1.0, out=out[i]), 28),
     }
     # LCNN max-feature-map kernels at the first (largest) layer's shape: conv output (B, 64, 404, 80)
     from audio_deepfake_adversarial_attacks_amd import _lib, lcnn_ops  # noqa: F401
@@ -91,7 +100,7 @@ def main():
     }
     results = {}
     for name, (fn, total_bytes) in lcnn_cases.items():
-        if a.only and a.only != name:
+        if only and name not in only:
             continue
         row = {"algorithmic_bytes_per_launch": total_bytes}
         for regime, sets in (("hot", 1), ("cold", nsets2)):
@@ -112,7 +121,7 @@ def main():
               f"{row['cold_GBps']:7.0f} GB/s  (B x 64 x 404 x 80 conv output; {total_bytes / 1e6:.0f} MB algorithmic)", flush=True)
     del cx, gxb, y_m, y_p
     for name, (fn, bytes_per_sample) in cases.items():
-        if a.only and a.only != name:
+        if only and name not in only:
             continue
         row = {"algorithmic_bytes_per_launch": bytes_per_sample * n}
         for regime, sets in (("hot", 1), ("cold", n_sets)):
