@@ -95,4 +95,15 @@ class AttackEnum(Enum):
     WORSTCASE_L1 = (torchattacks.MultiAttack.on_model, {"members": [("APGDL1", {"eps": 20.0, "steps": 10}),
                                                                     ("FAB", {"norm": "L1", "n_classes": 2, "eps": 20.0})]})
 
+    # --- additive members: budgets in dB of waveform SNR (torchattacks.PGDSNR), per utterance (PGDSNR_*) or per 256-sample segment
+    # (PGDSEGSNR_*).  40 / 30 / 20 dB are the customary figures of audio work (barely audible, audible, plainly noisy): a choice of
+    # scale, not an equivalence to the `eps` members above, whose SNR differs by tens of dB from one utterance to the next ---
+    PGDSNR_40dB = (torchattacks.PGDSNR, {"snr_db": 40.0, "segmental": False, "steps": 10})
+    PGDSNR_30dB = (torchattacks.PGDSNR, {"snr_db": 30.0, "segmental": False, "steps": 10})
+    PGDSNR_20dB = (torchattacks.PGDSNR, {"snr_db": 20.0, "segmental": False, "steps": 10})
+
+    PGDSEGSNR_40dB = (torchattacks.PGDSNR, {"snr_db": 40.0, "segmental": True, "steps": 10})
+    PGDSEGSNR_30dB = (torchattacks.PGDSNR, {"snr_db": 30.0, "segmental": True, "steps": 10})
+    PGDSEGSNR_20dB = (torchattacks.PGDSNR, {"snr_db": 20.0, "segmental": True, "steps": 10})
+
     NO_ATTACK = (None, {})

@@ -119,6 +119,8 @@ def gather_rows_across_ranks(rows: torch.Tensor) -> np.ndarray:
 def attack_batch(atk, batch_x: torch.Tensor, batch_y: torch.Tensor) -> torch.Tensor:
     """Reference :218-221 — normalise each utterance to [0, 1], attack, map back to the original range."""
     x01, mn, mx = aa_utils.to_minmax(batch_x)
+    if getattr(atk, "wants_minmax", False):                # a budget stated in the waveform's domain (torchattacks.PGDSNR)
+        atk.set_minmax(mn, mx)
     adv01 = atk(x01, batch_y)
     return aa_utils.revert_minmax(adv01, mn, mx)
 

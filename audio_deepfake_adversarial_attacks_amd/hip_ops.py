@@ -18,6 +18,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   perturbation_stats                 src/aa/qualitative/attacks_postanalysis.py (the distortion figures beside the WAV pairs)
   row_pgd_*_step / radius_*          no counterpart: the per-row radius steps and the bisection of torchattacks.MinRadiusPGD
   l1_box_project / apgdl1_*          no counterpart: l1-APGD (Croce & Hein, ICML 2021), torchattacks.APGDL1
+  seg_pgd_step / snr_row_radius      no counterpart: PGD under an SNR or segmental-SNR budget, torchattacks.PGDSNR
 """
 from __future__ import annotations
 
@@ -975,4 +976,60 @@ def radius_round(adv, z, labels, first: bool, state, best_adv, out=None):
                                                   state.data_ptr(), out.data_ptr(), best_adv.data_ptr(), B, T,
                                                   _stream(adv.device))
     _lib.check(st, "advstep_radius_round_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# SNR-budget PGD (include/advstep_snr.h): the segmental step and the radii of the global budget
+# ---------------------------------------------------------------------------------------------------------
+
+def _snr_rho(rho: float) -> float:
+    if not float(rho) >= 0.0:
+        raise ValueError(f"rho = 10^(-snr_db / 20) must be >= 0, got {rho}")
+    return float(rho)
+
+
+def _offset_rows(offset_rows, B: int, device):
+    """The rows' c = mn / (mx - mn), (B,) or (B, 1), or None (c = 0) -> the pointer the library takes."""
+    if offset_rows is None:
+        return None
+    _per_row(offset_rows, "offset_rows", B)
+    if offset_rows.device != device:
+        raise ValueError(f"offset_rows lives on {offset_rows.device}, the rows on {device}")
+    return offset_rows.data_ptr()
+
+
+def seg_pgd_step(adv, grad, orig, offset_rows, rho: float, alpha_rel: float, eps_div: float, lo: float = 0.0, hi: float = 1.0,
+                 out=None):
+    """The PGD step under a segmental-SNR budget: every 256-sample segment of a row is an L2 ball of radius
+    r = rho * sqrt(sum (orig + c)^2) over the segment, c = offset_rows[b] (None: 0); the segment's gradient is normalised by its
+    own norm, the step is alpha_rel * r, and the segment is projected onto its own ball (include/advstep_snr.h).  One launch,
+    16 B per sample.  `out` may be `adv`."""
+    _require(adv, "adv"), _require(grad, "grad"), _require(orig, "orig")
+    _same_shape(("adv", adv), ("grad", grad), ("orig", orig))
+    B, T = _rows(adv, "adv")
+    c = _offset_rows(offset_rows, B, adv.device)
+    rho = _snr_rho(rho)
+    out = _out_like(adv, out)
+    with _Launch("seg_pgd_step", adv.device, tensors=(adv, grad, orig, out)):
+        st = _lib.load().advstep_seg_pgd_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), c, rho, alpha_rel, eps_div,
+                                                  lo, hi, out.data_ptr(), B, T, _stream(adv.device))
+    _lib.check(st, "advstep_seg_pgd_step_f32")
+    return out
+
+
+def snr_row_radius(x, offset_rows, rho: float, out=None):
+    """(B,) float32: rho * sqrt(sum_t (x + c)^2) per row, c = offset_rows[b] (None: 0) — the radii at which `row_pgd_l2_step`
+    is the PGD step under a global SNR budget.  Two launches, no host read."""
+    _require(x, "x")
+    B, T = _rows(x, "x")
+    c = _offset_rows(offset_rows, B, x.device)
+    rho = _snr_rho(rho)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+    _per_row(out, "out", B)
+    with _Launch("snr_row_radius", x.device, tensors=(x,)):
+        ws, ws_bytes = _workspace(x.device, B, T)
+        st = _lib.load().advstep_snr_row_radius_f32(x.data_ptr(), c, rho, out.data_ptr(), B, T, ws, ws_bytes, _stream(x.device))
+    _lib.check(st, "advstep_snr_row_radius_f32")
     return out

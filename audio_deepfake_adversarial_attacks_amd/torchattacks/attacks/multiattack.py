@@ -47,7 +47,12 @@ class MultiAttack(Attack):
         """MultiAttack over `members` = [(attack class name, kwargs), ...], each built on `model`: the form an AttackEnum
         value (callable, kwargs) needs for `attack_method(attack_model, **attack_params)`."""
         from ... import torchattacks
-        return cls([getattr(torchattacks, name)(model, **kwargs) for name, kwargs in members], verbose=verbose)
+        attacks = [getattr(torchattacks, name)(model, **kwargs) for name, kwargs in members]
+        for attack in attacks:
+            if getattr(attack, "wants_minmax", False):
+                raise ValueError(f"{attack.attack} needs each utterance's min and max (set_minmax), which MultiAttack's row "
+                                 "compaction does not route to its members: it cannot be a member")
+        return cls(attacks, verbose=verbose)
 
     def set_training_mode(self, model_training=False, batchnorm_training=False, dropout_training=False):
         """Also forwarded to the members: they switch the model themselves at every call (Attack.__call__), and the evaluation

@@ -317,6 +317,8 @@ class AdversarialGDTrainer(Trainer):
         """to_minmax -> attack -> revert_minmax (src/trainer.py:424-426, 470-472, ...) through the attack's op table."""
         ops = attack.ops
         x01, mn, mx = ops.to_minmax(batch_x.contiguous())
+        if getattr(attack, "wants_minmax", False):          # a budget stated in the waveform's domain (torchattacks.PGDSNR)
+            attack.set_minmax(mn, mx)
         return ops.revert_minmax(attack(x01, batch_y).contiguous(), mn, mx)
 
     def init_adv_attacks(self, attack_model, adversarial_attacks):
