@@ -47,6 +47,11 @@ SIGNATURES = {
     "advstep_mfm_pool2_backward_f32": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "advstep_conv5_mfm_pool2_forward_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "advstep_conv5_mfm_pool2_backward_f32": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    "advstep_conv5_conv1x1_mfm_supported": (ctypes.c_int, [_i64, _i64, _i64, _i64]),
+    "advstep_conv5_conv1x1_mfm_forward_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64,
+                                                             _i64, _p]),
+    "advstep_conv5_conv1x1_mfm_backward_supported": (ctypes.c_int, [_i64, _i64, _i64, _i64]),
+    "advstep_conv5_conv1x1_mfm_backward_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "advstep_conv1x1_mfm_supported": (ctypes.c_int, [_i64]),
     "advstep_conv1x1_mfm_sel_bytes": (_sz, [_i64, _i64, _i64]),
     "advstep_conv1x1_mfm_forward_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),

@@ -8,6 +8,7 @@ bit-identical to the ATen ops they replace, ties and NaN included (tests/test_gp
 HIP tensors only: these functions raise on CPU tensors (the model keeps its plain torch path for CPU runs)."""
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -213,6 +214,111 @@ def conv1x1_mfm_supported(in_channels: int) -> bool:
 def conv1x1_mfm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None) -> torch.Tensor:
     """[BN_eval](MFM(conv2d(x, weight (2C, Cin, 1, 1), bias))) in one kernel (Cin in 32/48/64); bn = (mean, invstd)."""
     return _Conv1x1Mfm.apply(x.contiguous(), weight.contiguous(), bias, bn)
+
+
+# ---- first block + the 1x1 block behind it (csrc/lcnn_conv0.hip) ------------------------------------------------------------
+
+def _block0_pair_bwd_enabled() -> bool:
+    """ADVSTEP_LCNN_BLOCK0_PAIR_BWD=0 keeps the pair's backward as the two blocks' own launches (A/B measurements); read at
+    every call, default on."""
+    return os.environ.get("ADVSTEP_LCNN_BLOCK0_PAIR_BWD", "1") != "0"
+
+
+class _Conv5Conv1x1Mfm(torch.autograd.Function):
+    """conv5_mfm_pool2 followed by conv1x1_mfm as ONE kernel each way: neither the pooled tensor between them nor its gradient
+    is written.  Saves the first block's selection bytes and the 1x1 block's masks - what the two blocks' own backward entry
+    points read, which serve shapes the fused backward does not take - and nothing else; differentiable w.r.t. the input
+    only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, weight1, bias1, bn):
+        for t, name in ((x, "x"), (weight, "weight"), (weight1, "weight1")):
+            _require(t, name)
+        for t, name in ((bias, "bias"), (bias1, "bias1")):
+            if t is not None:
+                _require(t, name)
+        bn_mean, bn_invstd = _bn_ptrs(bn)
+        if x.dim() != 4 or x.shape[1] != 1 or weight.dim() != 4 or tuple(weight.shape[1:]) != (1, 5, 5) \
+                or weight1.dim() != 4 or tuple(weight1.shape[1:]) != (weight.shape[0] // 2, 1, 1) \
+                or (bias is not None and bias.numel() != weight.shape[0]) \
+                or (bias1 is not None and bias1.numel() != weight1.shape[0]):
+            raise ValueError(f"expected x (N, 1, H, W), weight (2C, 1, 5, 5), weight1 (2 C1, C, 1, 1); got {tuple(x.shape)}, "
+                             f"{tuple(weight.shape)}, {tuple(weight1.shape)}")
+        N, _, H, W = x.shape
+        C, C1 = weight.shape[0] // 2, weight1.shape[0] // 2
+        lib = _lib.load()
+        if weight.shape[0] % 2 or weight1.shape[0] % 2 or not lib.advstep_conv5_conv1x1_mfm_supported(C, C1, H, W):
+            raise ValueError(f"conv5_conv1x1_mfm supports C = C1 = 32 and even H, W; got C = {C}, C1 = {C1}, H = {H}, W = {W}")
+        P = (H // 2) * (W // 2)
+        y = torch.empty((N, C1, H // 2, W // 2), dtype=x.dtype, device=x.device)
+        idx = torch.empty(max(N * C * P, 1), dtype=torch.uint8, device=x.device)
+        sel = torch.empty(max(lib.advstep_conv1x1_mfm_sel_bytes(N, C1, P), 4), dtype=torch.uint8, device=x.device)
+        # priced as both convolutions (the benchmark's family table keeps one first-block row)
+        with _Launch("conv5_mfm_pool2_forward", x.device, work=100.0 * N * C * H * W + 4.0 * N * C * C1 * P,
+                     tensors=(x, y, idx, sel)):
+            st = lib.advstep_conv5_conv1x1_mfm_forward_f32(
+                x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, weight1.data_ptr(),
+                bias1.data_ptr() if bias1 is not None else None, bn_mean, bn_invstd, y.data_ptr(), idx.data_ptr(),
+                sel.data_ptr(), N, C, C1, H, W, _stream(x.device))
+        _lib.check(st, "advstep_conv5_conv1x1_mfm_forward_f32")
+        ctx.save_for_backward(idx, sel, weight, weight1, *([bn[1]] if bn is not None else []))
+        ctx.shape = (N, C, C1, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if any(ctx.needs_input_grad[1:5]):
+            raise RuntimeError("conv5_conv1x1_mfm provides the input gradient only; call it with frozen weights "
+                               "(the model takes the separate blocks otherwise)")
+        idx, sel, weight, weight1, *scale = ctx.saved_tensors
+        N, C, C1, H, W = ctx.shape
+        Ho, Wo = H // 2, W // 2
+        gy = gy.contiguous()
+        lib = _lib.load()
+        gx = torch.empty((N, 1, H, W), dtype=gy.dtype, device=gy.device)
+        if _block0_pair_bwd_enabled() and lib.advstep_conv5_conv1x1_mfm_backward_supported(C, C1, H, W):
+            # one kernel, priced as both gradients
+            with _Launch("conv5_mfm_pool2_backward", gy.device, work=12.5 * N * C * H * W + 4.0 * N * C * C1 * Ho * Wo,
+                         tensors=(gy, sel, idx, gx)):
+                st = lib.advstep_conv5_conv1x1_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), weight1.data_ptr(),
+                                                                scale[0].data_ptr() if scale else None, idx.data_ptr(),
+                                                                weight.data_ptr(), gx.data_ptr(), N, C, C1, H, W,
+                                                                _stream(gy.device))
+            _lib.check(st, "advstep_conv5_conv1x1_mfm_backward_f32")
+            return gx, None, None, None, None, None
+        # the two blocks' own backward kernels, through a temporary gradient of the pooled tensor
+        gp = torch.empty((N, C, Ho, Wo), dtype=gy.dtype, device=gy.device)
+        with _Launch("conv1x1_mfm_backward", gy.device, work=4.0 * N * C * C1 * Ho * Wo, tensors=(gy, sel, gp)):
+            st = lib.advstep_conv1x1_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), weight1.data_ptr(),
+                                                      scale[0].data_ptr() if scale else None, gp.data_ptr(), N, C, C1,
+                                                      Ho * Wo, _stream(gy.device))
+        _lib.check(st, "advstep_conv1x1_mfm_backward_f32")
+        with _Launch("conv5_mfm_pool2_backward", gy.device, work=12.5 * N * C * H * W, tensors=(gp, idx, gx)):
+            st = lib.advstep_conv5_mfm_pool2_backward_f32(gp.data_ptr(), idx.data_ptr(), weight.data_ptr(), gx.data_ptr(), N,
+                                                          C, H, W, _stream(gy.device))
+        _lib.check(st, "advstep_conv5_mfm_pool2_backward_f32")
+        return gx, None, None, None, None, None
+
+
+def conv5_conv1x1_mfm_supported(C: int, C1: int, H: int, W: int) -> bool:
+    return bool(_lib.load().advstep_conv5_conv1x1_mfm_supported(C, C1, H, W))
+
+
+_PER_BLOCK_ENTRY_POINTS = (conv5_mfm_pool2, conv1x1_mfm)
+
+
+def per_block_entry_points_untouched() -> bool:
+    """False while somebody has replaced `conv5_mfm_pool2` or `conv1x1_mfm` in this module - an instrument that reads every
+    block's input and winners as the model calls them (tests/parity_attribution.py's WinnerTap).  The pair goes past both and
+    never forms the tensor between them, so the model keeps the two calls then: same kernels as ADVSTEP_LCNN_BLOCK0_PAIR=0,
+    same bits."""
+    return (conv5_mfm_pool2, conv1x1_mfm) == _PER_BLOCK_ENTRY_POINTS
+
+
+def conv5_conv1x1_mfm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], weight1: torch.Tensor,
+                      bias1: Optional[torch.Tensor] = None, bn=None) -> torch.Tensor:
+    """conv1x1_mfm(conv5_mfm_pool2(x, weight, bias), weight1, bias1, bn), bit for bit, with one forward kernel."""
+    return _Conv5Conv1x1Mfm.apply(x.contiguous(), weight.contiguous(), bias, weight1.contiguous(), bias1, bn)
 
 
 # ---- 3x3 blocks on the matrix cores (csrc/lcnn_wino.hip) -------------------------------------------------------------------

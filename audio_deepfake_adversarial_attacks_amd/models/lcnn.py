@@ -119,6 +119,11 @@ def _fused_conv0_enabled() -> bool:
     return os.environ.get("ADVSTEP_LCNN_CONV0", "1") != "0"
 
 
+def _block0_pair_enabled() -> bool:
+    """ADVSTEP_LCNN_BLOCK0_PAIR=0 keeps the first block and its 1x1 block as two launches (A/B measurements); default on."""
+    return os.environ.get("ADVSTEP_LCNN_BLOCK0_PAIR", "1") != "0"
+
+
 def _fused_bn_enabled() -> bool:
     """ADVSTEP_LCNN_BN=0 keeps ATen's batch-norm kernels after the fused blocks (A/B measurements); default on."""
     return os.environ.get("ADVSTEP_LCNN_BN", "1") != "0"
@@ -204,6 +209,13 @@ class BaseLCNN(nn.Module):
                                                                   (m.bias is not None and m.bias.requires_grad)))
                 if (params_frozen and _is_first_block_conv(m) and isinstance(after, nn.MaxPool2d) and _is_pool2(after)
                         and _fused_conv0_enabled()):
+                    pair = self._block0_pair(mods, i, x)
+                    if pair is not None:
+                        # ... and the 1x1 block behind it in the same kernel: the pooled tensor between them never exists
+                        conv1, bn, consumed = pair
+                        x = lcnn_ops.conv5_conv1x1_mfm(x, m.weight, m.bias, conv1.weight, conv1.bias, bn)
+                        i += consumed
+                        continue
                     # one-channel 5x5 conv + MFM + pool in ONE kernel: the (B, 64, 404, 80) conv output never exists
                     x = lcnn_ops.conv5_mfm_pool2(x, m.weight, m.bias)
                     i += 3
@@ -237,6 +249,32 @@ class BaseLCNN(nn.Module):
                 x = m(x)
                 i += 1
         return x
+
+    @staticmethod
+    def _block0_pair(mods, i, x):
+        """(1x1 conv, folded BatchNorm stats or None, modules consumed) when mods[i:] starts with the first block followed by a 1x1
+        block that lcnn_ops.conv5_conv1x1_mfm takes under today's conditions for both fused kernels; None otherwise."""
+        from .. import lcnn_ops
+        if not (_block0_pair_enabled() and _fused_conv1x1_enabled() and i + 4 < len(mods)):
+            return None
+        if not lcnn_ops.per_block_entry_points_untouched():     # someone listens on the two calls the pair would go past
+            return None
+        conv1, mfm1 = mods[i + 3], mods[i + 4]
+        after = mods[i + 5] if i + 5 < len(mods) else None
+        if not (isinstance(conv1, nn.Conv2d) and conv1.padding_mode == "zeros" and _is_pointwise_conv(conv1)
+                and isinstance(mfm1, MaxFeatureMap2D) and mfm1.max_dim == 1 and not isinstance(after, nn.MaxPool2d)):
+            return None
+        if torch.is_grad_enabled() and (conv1.weight.requires_grad or (conv1.bias is not None and conv1.bias.requires_grad)):
+            return None
+        C = mods[i].out_channels // 2
+        if conv1.in_channels != C or x.dtype != torch.float32 or not lcnn_ops.conv5_conv1x1_mfm_supported(
+                C, conv1.out_channels // 2, x.shape[2], x.shape[3]):
+            return None
+        consumed, bn = 5, None
+        if _foldable_bn(after) and _fused_bn_enabled():
+            bn = lcnn_ops.bn_eval_stats(after)
+            consumed += 1
+        return conv1, bn, consumed
 
     def _fused_tail(self, hidden4):
         """The two BLSTM layers, the skip connection, the mean over frames and the read-out as ONE autograd node

@@ -74,6 +74,33 @@ int advstep_conv5_mfm_pool2_forward_f32(const float *x, const float *weight, con
 int advstep_conv5_mfm_pool2_backward_f32(const float *gy, const uint8_t *idx, const float *weight, float *gx, int64_t N,
                                          int64_t C, int64_t H, int64_t W, advstep_stream_t stream);
 
+/* ---- first block and the 1x1 block behind it in one kernel (src/models/lcnn.py:121-127):
+ *     Conv2d(1, 2C, (5,5), padding 2) -> MFM -> MaxPool2d(2, 2) -> Conv2d(C, 2 C1, (1,1)) -> MFM [-> BatchNorm2d(eval)]
+ * for the one shape family advstep_conv5_conv1x1_mfm_supported() accepts: C = C1 = 32 (LCNN's), even H and W.  The pooled
+ * (N, C, H/2, W/2) tensor between the blocks is never written: a wave hands the pooled values of its 64 positions to the
+ * matrix cores as the 1x1 kernel's operands.  y (N, C1, H/2, W/2), idx (the first block's selection bytes, as
+ * advstep_conv5_mfm_pool2_forward_f32 writes them) and sel (the 1x1 block's masks, as advstep_conv1x1_mfm_forward_f32
+ * writes them; advstep_conv1x1_mfm_sel_bytes(N, C1, H/2 * W/2) bytes, 4-byte aligned) are bit for bit what the two calls
+ * give - same fma chains in the same order - so either block's backward entry point takes them.  weight (2C, 1, 5, 5),
+ * bias (2C) or NULL, weight1 (2 C1, C), bias1 (2 C1) or NULL, bn_mean / bn_invstd (C1) or both NULL. */
+int advstep_conv5_conv1x1_mfm_supported(int64_t C, int64_t C1, int64_t H, int64_t W);
+int advstep_conv5_conv1x1_mfm_forward_f32(const float *x, const float *weight, const float *bias, const float *weight1,
+                                          const float *bias1, const float *bn_mean, const float *bn_invstd, float *y,
+                                          uint8_t *idx, void *sel, int64_t N, int64_t C, int64_t C1, int64_t H, int64_t W,
+                                          advstep_stream_t stream);
+
+/* Input gradient of the pair above (src/models/lcnn.py:121-127) in one kernel: gx (N, 1, H, W) from gy (N, C1, H/2, W/2), the
+ * 1x1 block's masks `sel`, its weights and the following BatchNorm's invstd `gscale` (C1, or NULL), the first block's
+ * selection bytes `idx` and weights.  The gradient of the pooled tensor between the blocks is never written: every pooled
+ * cell forms its C values on the matrix cores by advstep_conv1x1_mfm_backward_f32's chain (same instructions, same order)
+ * and feeds them to the cell-centric kernel of advstep_conv5_mfm_pool2_backward_f32 - gx is bit for bit what those two
+ * calls give.  Shapes: what advstep_conv5_conv1x1_mfm_backward_supported() accepts (the forward's, W <= 128); gx 8-byte
+ * aligned. */
+int advstep_conv5_conv1x1_mfm_backward_supported(int64_t C, int64_t C1, int64_t H, int64_t W);
+int advstep_conv5_conv1x1_mfm_backward_f32(const float *gy, const void *sel, const float *weight1, const float *gscale,
+                                           const uint8_t *idx, const float *weight, float *gx, int64_t N, int64_t C, int64_t C1,
+                                           int64_t H, int64_t W, advstep_stream_t stream);
+
 /* ---- 1x1 blocks fused: Conv2d(Cin, 2C, (1,1)) -> MaxFeatureMap2D  (src/models/lcnn.py:125-126,132-133,139-140,146-147)
  * A skinny GEMM (K = Cin) run on the matrix cores (fp32-in / fp32-accumulate MFMA: exact f32).
  * x (N, Cin, P) with P = H*W, weight (2C, Cin), bias (2C) or NULL -> y (N, C, P); sel gets ONE bit per output, set
