@@ -106,4 +106,17 @@ class AttackEnum(Enum):
     PGDSEGSNR_30dB = (torchattacks.PGDSNR, {"snr_db": 30.0, "segmental": True, "steps": 10})
     PGDSEGSNR_20dB = (torchattacks.PGDSNR, {"snr_db": 20.0, "segmental": True, "steps": 10})
 
+    # --- additive members: one perturbation for every utterance (torchattacks.UniversalPGD), fitted on the first batches of the
+    # run and applied to all of them (evaluation.generate_attacks: universal_fit / universal_load / universal_save).  The radii
+    # are those of the PGD / PGDL2 members above; label 0 is spoof (base_dataset.py), so *_SPOOF is the noise an attacker adds
+    # to any fake; UAP_WAVE_SPOOF's eps is 0.001 of full scale in the WAVEFORM's units, the same signal for every utterance.
+    # All of these scales are choices, not measured equivalences ---
+    UAP = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.0005})
+    UAP_eps00075 = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.00075})
+    UAP_eps001 = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001})
+    UAP_L2 = (torchattacks.UniversalPGD, {"norm": "L2", "eps": 0.1})
+    UAP_SPOOF = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.0005, "source_label": 0})
+    UAP_SPOOF_eps001 = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001, "source_label": 0})
+    UAP_WAVE_SPOOF = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001, "source_label": 0, "domain": "waveform"})
+
     NO_ATTACK = (None, {})

@@ -15,7 +15,8 @@ log line.  What is different is how the work is placed on the machine:
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
     (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
     all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD — one
-    all-gather of the per-utterance radii).
+    all-gather of the per-utterance radii).  A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE
+    process before the loop, or loaded from a file by every rank: no communication either way.
 """
 from __future__ import annotations
 
@@ -149,6 +150,12 @@ def format_min_radius(report: Dict[str, float]) -> str:
     return ", ".join(f"{k}: {v:.4g}" for k, v in report.items() if k.startswith("min_radius/"))
 
 
+def format_universal(report: Dict[str, float]) -> str:
+    """The log line of a run whose attack is universal (torchattacks.UniversalPGD): the summary of metrics.universal_summary."""
+    return ", ".join(f"{k}: {v}" if k.endswith("_utterances") else f"{k}: {v:.4g}" for k, v in report.items()
+                     if k.startswith("universal/"))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # the loop
 # ---------------------------------------------------------------------------------------------------------
@@ -279,6 +286,45 @@ class _Lanes:
             self.held = []
 
 
+def prepare_universal(atk, loader, device, n_batches: int, fit: Optional[int] = None, load=None, save=None) -> int:
+    """Give a universal attack (`is_universal`) its perturbation before the loop, on the caller's stream: from the file `load`,
+    or by `atk.fit` on the first `fit` batches of `loader` (None: max(1, n_batches // 4)), normalised as the loop normalises
+    them and KEPT ON THE DEVICE with their labels, mn and mx for the attack's epochs — fit x B x T x 4 bytes (66 MB for two
+    batches of 128 utterances of 64 600 samples).  `save`: rank 0 writes the perturbation the run uses.  Returns the number of
+    this rank's utterances it was fitted on (0 for a loaded one).  Fitting is single-process: every rank of a larger job loads
+    the same file, so no step of the fit communicates."""
+    rank, world = rank_and_world()
+    fitted_rows = 0
+    if load is not None:
+        atk.load_delta(load)
+    else:
+        if world > 1:
+            raise ValueError("a universal perturbation is fitted by one process: with more than one rank, fit it in a "
+                             "single-process run with universal_save and pass that file as universal_load")
+        n_fit = max(1, n_batches // 4) if fit is None else int(fit)
+        if not 1 <= n_fit <= n_batches:
+            raise ValueError(f"universal_fit must name between 1 and the run's {n_batches} batches, got {n_fit}")
+        dev = torch.device(device)
+        kept = []
+        batches = _device_batches(loader, device)
+        for batch_x, _, batch_y, _, ready in batches:
+            if ready is not None:                          # uploaded on a side stream: this stream waits and takes the tensors over
+                torch.cuda.current_stream(dev).wait_event(ready)
+                batch_x.record_stream(torch.cuda.current_stream(dev))
+                batch_y.record_stream(torch.cuda.current_stream(dev))
+            x01, mn, mx = aa_utils.to_minmax(batch_x)
+            kept.append((x01, batch_y, mn, mx))
+            fitted_rows += batch_x.size(0)
+            if len(kept) == n_fit:
+                break
+        batches.close()
+        atk.reset()
+        atk.fit(kept)
+    if save is not None and rank == 0:
+        atk.save_delta(save)
+    return fitted_rows
+
+
 def default_in_flight(atk, device, has_callback: bool) -> int:
     """Two batches in flight when the attack's inner loop replays from a hipGraph (PGD, PGDL2: the host queues a batch in a
     few milliseconds); host-driven attacks (CW: a host read every steps // 10 iterations; FAB) and callback runs (the
@@ -323,6 +369,9 @@ def generate_attacks(
     on_batch_queued: Optional[Callable[[int], None]] = None,
     in_flight: Optional[int] = None,
     perturbation_stats: bool = False,
+    universal_fit: Optional[int] = None,
+    universal_load: Optional[Union[str, os.PathLike]] = None,
+    universal_save: Optional[Union[str, os.PathLike]] = None,
 ) -> Dict[str, float]:
     """Reference signature (:146-157) plus additive keywords: `dataset` (a ready Dataset yielding the reference's
     4-tuple; without it the `DetectionDataset` over `datasets_paths` is built as in the reference's `get_dataset`,
@@ -343,6 +392,13 @@ def generate_attacks(
     An attack that carries `last_radius` (torchattacks.MinRadiusPGD: each utterance's minimal radius, on the device) adds the
     `min_radius/*` keys of `metrics.radius_summary` at the attack's `report_at`, one more log line and, with `return_scores`,
     the per-utterance radii under `scores["min_radius"]` (utterance order, like `y_pred`); any other attack: nothing.
+    A universal attack (`is_universal`: torchattacks.UniversalPGD) gets its perturbation BEFORE the loop (`prepare_universal`):
+    loaded from `universal_load`, or fitted on the first `universal_fit` batches of this run's batch order (None: a quarter of
+    them, at least 1), which are kept on the device meanwhile (universal_fit x B x T x 4 bytes); `universal_save` writes it.  The
+    loop then runs over ALL batches with the frozen perturbation, one launch per batch.  More than one rank needs
+    `universal_load`.  Adds the `universal/*` keys of `metrics.universal_summary` (fitted against held-out utterances), one
+    more log line and, with `return_scores`, `scores["universal_delta"]`; any other attack: nothing, and the three keywords
+    must be left at None.
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -390,6 +446,14 @@ def generate_attacks(
     multi = atk if isinstance(atk, MultiAttack) else None
     if multi is not None:
         multi._start_multi_atk_records()
+
+    universal = atk if getattr(atk, "is_universal", False) else None
+    if universal is not None:
+        # on the caller's stream, BEFORE the lanes exist: their constructor orders every lane behind this stream
+        fitted_rows = prepare_universal(universal, test_loader, device, len(sampler), universal_fit, universal_load,
+                                        universal_save)
+    elif universal_fit is not None or universal_load is not None or universal_save is not None:
+        raise ValueError("universal_fit / universal_load / universal_save need a universal attack (AttackEnum UAP*)")
 
     lanes = _Lanes(device, in_flight if in_flight is not None
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
@@ -477,6 +541,13 @@ def generate_attacks(
         report.update(metrics.radius_summary(all_radii, getattr(atk, "report_at", ())))
         if return_scores:
             report["scores"]["min_radius"] = all_radii
+    if universal is not None:
+        delta = universal.delta.detach().cpu().numpy()
+        # rank order = utterance order for the one process that fits; a loaded perturbation was fitted on none of them
+        report.update(metrics.universal_summary(all_y, all_label, np.arange(len(all_y)) < fitted_rows, delta,
+                                                universal.source_label))
+        if return_scores:
+            report["scores"]["universal_delta"] = delta
     if multi is not None:
         report["multi_attack/remaining"] = remaining
     if rank == 0:
@@ -487,4 +558,6 @@ def generate_attacks(
             LOGGER.info(format_perturbation(report))
         if has_radius:
             LOGGER.info(format_min_radius(report))
+        if universal is not None:
+            LOGGER.info(format_universal(report))
     return report

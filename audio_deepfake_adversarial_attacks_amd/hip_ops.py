@@ -19,6 +19,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   row_pgd_*_step / radius_*          no counterpart: the per-row radius steps and the bisection of torchattacks.MinRadiusPGD
   l1_box_project / apgdl1_*          no counterpart: l1-APGD (Croce & Hein, ICML 2021), torchattacks.APGDL1
   seg_pgd_step / snr_row_radius      no counterpart: PGD under an SNR or segmental-SNR budget, torchattacks.PGDSNR
+  universal_colsum / universal_apply no counterpart: one perturbation for every utterance, torchattacks.UniversalPGD
 """
 from __future__ import annotations
 
@@ -1032,4 +1033,62 @@ def snr_row_radius(x, offset_rows, rho: float, out=None):
         ws, ws_bytes = _workspace(x.device, B, T)
         st = _lib.load().advstep_snr_row_radius_f32(x.data_ptr(), c, rho, out.data_ptr(), B, T, ws, ws_bytes, _stream(x.device))
     _lib.check(st, "advstep_snr_row_radius_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# universal perturbation (include/advstep_universal.h): the column sum over a batch and the broadcast of one delta
+# ---------------------------------------------------------------------------------------------------------
+
+UNIVERSAL_GROUP_ROWS = 16                       # ADVSTEP_UNIVERSAL_GROUP_ROWS: rows per group of universal_colsum's first launch
+
+
+def _row_weight(row_weight, B: int, device):
+    """The rows' w_b, (B,) or (B, 1), or None (w_b = 1) -> the pointer the library takes."""
+    if row_weight is None:
+        return None
+    _per_row(row_weight, "row_weight", B)
+    if row_weight.device != device:
+        raise ValueError(f"row_weight lives on {row_weight.device}, the rows on {device}")
+    return row_weight.data_ptr()
+
+
+def universal_colsum(grad, row_weight=None, out=None):
+    """(1, T) float32: out[t] = sum_b w_b * grad[b, t], w_b = row_weight[b] (None: 1) — the gradient of the batch's loss with
+    respect to one perturbation shared by its rows.  Every product rounds once and the order of the additions depends on (B, T)
+    alone (include/advstep_universal.h): reruns, on any stream, are bit-identical.  One launch for B <= 16, two above; no host
+    read."""
+    _require(grad, "grad")
+    B, T = _rows(grad, "grad")
+    w = _row_weight(row_weight, B, grad.device)
+    if out is None:
+        out = torch.empty((1, T), dtype=torch.float32, device=grad.device)
+    _require(out, "out")
+    if out.numel() != T or out.device != grad.device:
+        raise ValueError(f"out must hold one value per column ({T}) on {grad.device}, got {tuple(out.shape)}@{out.device}")
+    lib = _lib.load()
+    with _Launch("universal_colsum", grad.device, tensors=(grad, out)):
+        # partial planes only, rewritten by every call: keyed by stream like the row workspace
+        key = (grad.device.index if grad.device.index is not None else torch.cuda.current_device(), _stream(grad.device), int(B),
+               int(T), "universal")
+        ws, ws_bytes = _scratch(key, lambda: torch.empty(max(lib.advstep_universal_workspace_bytes(B, T), 256), dtype=torch.uint8,
+                                                         device=grad.device))
+        st = lib.advstep_universal_colsum_f32(grad.data_ptr(), w, out.data_ptr(), B, T, ws, ws_bytes, _stream(grad.device))
+    _lib.check(st, "advstep_universal_colsum_f32")
+    return out
+
+
+def universal_apply(x, delta, row_weight=None, lo: float = 0.0, hi: float = 1.0, out=None):
+    """out[b, t] = clamp(x[b, t] + w_b * delta[t], lo, hi), w_b = row_weight[b] (None: 1): one perturbation of T samples added
+    to every row.  One launch, 8 B per sample, no host read.  `out` may be `x`."""
+    _require(x, "x"), _require(delta, "delta")
+    B, T = _rows(x, "x")
+    if delta.numel() != T or delta.device != x.device:
+        raise ValueError(f"delta must hold one value per sample of a row ({T}) on {x.device}, got {tuple(delta.shape)}@{delta.device}")
+    w = _row_weight(row_weight, B, x.device)
+    out = _out_like(x, out)
+    with _Launch("universal_apply", x.device, tensors=(x, out)):
+        st = _lib.load().advstep_universal_apply_f32(x.data_ptr(), delta.data_ptr(), w, out.data_ptr(), B, T, lo, hi,
+                                                     _stream(x.device))
+    _lib.check(st, "advstep_universal_apply_f32")
     return out

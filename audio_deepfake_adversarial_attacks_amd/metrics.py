@@ -3,8 +3,9 @@ evaluate_models_on_adversarial_attacks.py:267-293), restated in numpy so the GPU
 scipy.  Each function documents the library routine it reproduces; tests pin them against values the
 reference's own calls produced (tests/golden/metrics.npz).  `perturbation_summary` is this package's own: the run-level
 digest of the per-utterance perturbation report (include/advstep_perturb.h); so is `radius_summary`, the digest of the
-per-utterance minimal radii of torchattacks.MinRadiusPGD."""
-from typing import Dict, Sequence, Tuple
+per-utterance minimal radii of torchattacks.MinRadiusPGD, and `universal_summary`, the fitted / held-out split of a run with one
+universal perturbation (torchattacks.UniversalPGD)."""
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -208,4 +209,41 @@ def radius_summary(radii, report_at: Sequence[float] = ()) -> Dict[str, float]:
         # in the radii's own precision: the search's grid points are float32 (float32(0.001) > 0.001 as a float64), and a row
         # that flipped AT eps is not robust at eps
         out[f"min_radius/robust_acc@{eps:g}"] = 100.0 * float(np.mean(r32 > np.float32(eps))) if n else float("nan")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# universal-perturbation report
+# ---------------------------------------------------------------------------------------------------------
+
+def universal_summary(y, y_pred_label, fitted, delta, source_label: Optional[int] = None) -> Dict[str, float]:
+    """Run-level digest of a run that applied ONE perturbation (torchattacks.UniversalPGD) to every utterance.  `y`,
+    `y_pred_label`: (N,) labels and post-attack hard labels; `fitted`: (N,) bool, the utterances the perturbation was fitted on
+    (all False for a loaded one); `delta`: the perturbation, in its own domain.
+
+    universal/fit_utterances, heldout_utterances     the sizes of the two groups
+    universal/accuracy_fit, accuracy_heldout         100 x the share of correct labels in each group (what generalises is the
+                                                     held-out figure; the fitted one is the optimiser's own training score)
+    universal/source_flipped_fit, _heldout           with a source label: 100 x the share of the group's SOURCE-class utterances
+                                                     whose post-attack label is the other class
+    universal/delta_linf, delta_l2                   max |delta| and ||delta||_2, accumulated in float64
+    A group without utterances (of the source class) has NaN."""
+    y, lab = np.asarray(y).ravel(), np.asarray(y_pred_label).ravel()
+    fitted = np.asarray(fitted).ravel().astype(bool)
+    if not (y.shape == lab.shape == fitted.shape):
+        raise ValueError(f"y, y_pred_label and fitted must hold one value per utterance, got {y.shape}, {lab.shape}, {fitted.shape}")
+    d = np.asarray(delta, dtype=np.float64).ravel()
+
+    def share(rows, hit):
+        return 100.0 * float(np.mean(hit[rows])) if rows.any() else float("nan")
+
+    out: Dict[str, float] = {"universal/fit_utterances": int(fitted.sum()), "universal/heldout_utterances": int((~fitted).sum()),
+                             "universal/accuracy_fit": share(fitted, lab == y),
+                             "universal/accuracy_heldout": share(~fitted, lab == y)}
+    if source_label is not None:
+        src = y == source_label
+        out["universal/source_flipped_fit"] = share(fitted & src, lab != y)
+        out["universal/source_flipped_heldout"] = share(~fitted & src, lab != y)
+    out["universal/delta_linf"] = float(np.max(np.abs(d))) if d.size else float("nan")
+    out["universal/delta_l2"] = float(np.sqrt(np.sum(d * d)))
     return out

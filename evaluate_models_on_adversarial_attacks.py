@@ -77,6 +77,14 @@ def parse_arguments(argv=None):
                         help="report how large the perturbation is per utterance (L-inf, L2, SNR and segmental SNR in dB of the "
                              "waveform the detector is given): perturbation/* keys and a second log line; with --qual also "
                              "perturbation_metrics.csv beside the WAV pairs")
+    parser.add_argument("--universal_fit", type=int, default=None, metavar="N",
+                        help="universal attacks (UAP*): fit the perturbation on the first N batches of the run (default: a "
+                             "quarter of them, at least 1); every batch is then evaluated with the frozen perturbation")
+    parser.add_argument("--universal_load", type=str, default=None, metavar="PATH",
+                        help="universal attacks: apply the perturbation of this .npz instead of fitting one (required with "
+                             "more than one process)")
+    parser.add_argument("--universal_save", type=str, default=None, metavar="PATH",
+                        help="universal attacks: write the perturbation the run used to this .npz")
     return parser.parse_args(argv)
 
 
@@ -134,6 +142,9 @@ def main(args):
         num_workers=args.num_workers,
         in_flight=args.in_flight,
         perturbation_stats=args.perturbation_stats,
+        universal_fit=args.universal_fit,
+        universal_load=args.universal_load,
+        universal_save=args.universal_save,
     )
     if world > 1:
         dist.destroy_process_group()
