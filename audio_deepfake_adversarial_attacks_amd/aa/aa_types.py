@@ -119,4 +119,13 @@ class AttackEnum(Enum):
     UAP_SPOOF_eps001 = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001, "source_label": 0})
     UAP_WAVE_SPOOF = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001, "source_label": 0, "domain": "waveform"})
 
+    # --- additive members: the score-based black-box attack (torchattacks.SPSA: the attacker reads the detector's score and
+    # takes no gradient), at the radii of the PGD triplet above.  20 steps of 8 direction pairs are 20 * 17 = 340 queries per
+    # utterance, SPSA100_eps003 (PGD40_eps003's radius) 100 * 33 = 3300.  These budgets are choices of scale: nobody has
+    # measured what they achieve against these detectors ---
+    SPSA = (torchattacks.SPSA, {"eps": 0.0005, "steps": 20, "nb_sample": 8})
+    SPSA_eps00075 = (torchattacks.SPSA, {"eps": 0.00075, "steps": 20, "nb_sample": 8})
+    SPSA_eps001 = (torchattacks.SPSA, {"eps": 0.001, "steps": 20, "nb_sample": 8})
+    SPSA100_eps003 = (torchattacks.SPSA, {"eps": 0.003, "steps": 100, "nb_sample": 16})
+
     NO_ATTACK = (None, {})

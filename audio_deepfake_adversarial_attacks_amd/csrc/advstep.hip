@@ -31,13 +31,6 @@ __device__ __forceinline__ float fgsm_elem(float x, float g, float eps, float lo
     return clampf(x + eps * sgn(g), lo, hi);
 }
 
-__device__ __forceinline__ float pgd_linf_elem(float a, float g, float x, float alpha, float eps, float lo,
-                                               float hi) {
-    a = a + alpha * sgn(g);
-    float d = clampf(a - x, -eps, eps);
-    return clampf(x + d, lo, hi);
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // flat elementwise kernels: n = B*T samples, tile-strided, float4 when all pointers are 16-byte aligned
 // ---------------------------------------------------------------------------------------------------------

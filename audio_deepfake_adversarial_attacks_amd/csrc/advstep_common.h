@@ -4,9 +4,10 @@
 // these are rules that separate kernels must agree on bit for bit: the max-feature-map / 2x2 pool selection written by
 // the forward kernels (lcnn_conv0.hip, lcnn_wino.hip, lcnn_mfm.hip) and read back by the backward ones (lcnn_mfm.hip),
 // and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The attack files (advstep.hip, apgd.hip,
-// momentum.hip, radius.hip, perturb.hip, multiattack.hip, fab.hip, apgdl1.hip, snr.hip) share the scalar semantics, the reduction operators
-// with the wave butterfly, and the host's rows_vec / ROW_KERNEL_PAIR / overlaps; what depends on the 256-thread (tile, row)
-// geometry is in row_tiles.h; fab.hip and apgdl1.hip give a row to one 1024-thread workgroup instead: row_workgroup.h.
+// momentum.hip, radius.hip, perturb.hip, multiattack.hip, fab.hip, apgdl1.hip, snr.hip, universal.hip, spsa.hip) share the scalar
+// semantics, the reduction operators with the wave butterfly, and the host's rows_vec / ROW_KERNEL_PAIR / overlaps; what depends
+// on the 256-thread (tile, row) geometry is in row_tiles.h; fab.hip and apgdl1.hip give a row to one 1024-thread workgroup
+// instead: row_workgroup.h.
 
 #ifndef ADVSTEP_COMMON_H
 #define ADVSTEP_COMMON_H
@@ -130,6 +131,14 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) {
     return (v > hi) ? hi : v;
 }
 
+// The PGD L-inf move and projection of one sample (pgd.py:74-76): advstep.hip's advstep_pgd_linf_step_f32 and spsa.hip's step,
+// which promises that entry point's bits for its estimated gradient.
+__device__ __forceinline__ float pgd_linf_elem(float a, float g, float x, float alpha, float eps, float lo, float hi) {
+    a = a + alpha * sgn(g);
+    float d = clampf(a - x, -eps, eps);
+    return clampf(x + d, lo, hi);
+}
+
 // log(1 + exp(t)), stable: the 2-logit cross-entropy in closed form.
 __device__ __forceinline__ float softplusf(float t) { return (t > 0.0f ? t : 0.0f) + log1pf(expf(-fabsf(t))); }
 
@@ -165,7 +174,8 @@ __device__ __forceinline__ float wg_sum(float v, float *lds) { return wg_reduce(
 __device__ __forceinline__ float wg_max_nan(float v, float *lds) { return wg_reduce(v, MaxNanOp(), lds); }
 __device__ __forceinline__ float wg_min_nan(float v, float *lds) { return wg_reduce(v, MinNanOp(), lds); }
 
-// ---- Philox4x32-10 (Salmon et al., SC'11), counter-based: the random starts of advstep.hip and apgd.hip draw from it ----
+// ---- Philox4x32-10 (Salmon et al., SC'11), counter-based: the random starts of advstep.hip and apgd.hip draw from it, and
+// spsa.hip takes its direction bits from it ----
 
 struct Quad {
     uint32_t v[4];

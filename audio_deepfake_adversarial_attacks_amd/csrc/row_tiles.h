@@ -1,7 +1,8 @@
 // row_tiles.h — the (tile, row) geometry of the 256-thread row kernels (advstep.hip, apgd.hip, momentum.hip, radius.hip, perturb.hip,
-// multiattack.hip, snr.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2 arithmetic that several kernels must
-// agree on bit for bit, and the launch on the (tile, row) grid (internal, like advstep_common.h, which has the rules that do not
-// depend on this tile: scalar semantics, reductions, rows_vec, ROW_KERNEL_PAIR, overlaps).
+// multiattack.hip, snr.hip, universal.hip, spsa.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2
+// arithmetic that several kernels must agree on bit for bit, and the launch on the (tile, row) grid (internal, like
+// advstep_common.h, which has the rules that do not depend on this tile: scalar semantics, reductions, rows_vec, ROW_KERNEL_PAIR,
+// overlaps).
 //
 // grid = (C tiles of 4096 samples, B rows), 256 threads, 4 float4 per thread and stream; float4 q of a row is loaded whole when
 // the rows are float4-addressable (VEC) and sample by sample otherwise (T % 4 != 0 leaves rows 2 .. B unaligned).  Tile c of

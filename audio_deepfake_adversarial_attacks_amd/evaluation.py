@@ -15,8 +15,9 @@ log line.  What is different is how the work is placed on the machine:
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
     (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
     all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD — one
-    all-gather of the per-utterance radii).  A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE
-    process before the loop, or loaded from a file by every rank: no communication either way.
+    all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA — one of the per-utterance queries).
+    A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE process before the loop, or loaded from a
+    file by every rank: no communication either way.
 """
 from __future__ import annotations
 
@@ -154,6 +155,12 @@ def format_universal(report: Dict[str, float]) -> str:
     """The log line of a run whose attack is universal (torchattacks.UniversalPGD): the summary of metrics.universal_summary."""
     return ", ".join(f"{k}: {v}" if k.endswith("_utterances") else f"{k}: {v:.4g}" for k, v in report.items()
                      if k.startswith("universal/"))
+
+
+def format_blackbox(report: Dict[str, float]) -> str:
+    """The log line of a run whose attack carries `last_queries` (torchattacks.SPSA): the summary of metrics.query_summary."""
+    return ", ".join(f"{k}: {v}" if k.endswith("budget") else f"{k}: {v:.4g}" for k, v in report.items()
+                     if k.startswith("blackbox/"))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -392,6 +399,9 @@ def generate_attacks(
     An attack that carries `last_radius` (torchattacks.MinRadiusPGD: each utterance's minimal radius, on the device) adds the
     `min_radius/*` keys of `metrics.radius_summary` at the attack's `report_at`, one more log line and, with `return_scores`,
     the per-utterance radii under `scores["min_radius"]` (utterance order, like `y_pred`); any other attack: nothing.
+    An attack that carries `last_queries` (torchattacks.SPSA: the model queries each utterance spent, on the device) adds the
+    `blackbox/*` keys of `metrics.query_summary` against the attack's `budget`, one more log line and, with `return_scores`,
+    the per-utterance counts under `scores["queries"]`; any other attack: nothing.
     A universal attack (`is_universal`: torchattacks.UniversalPGD) gets its perturbation BEFORE the loop (`prepare_universal`):
     loaded from `universal_load`, or fitted on the first `universal_fit` batches of this run's batch order (None: a quarter of
     them, at least 1), which are kept on the device meanwhile (universal_fit x B x T x 4 bytes); `universal_save` writes it.  The
@@ -459,8 +469,9 @@ def generate_attacks(
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
     seen_total = 0
-    y_pred, y_pred_label, y, perturbation, radii = [], [], [], [], []
+    y_pred, y_pred_label, y, perturbation, radii, queries = [], [], [], [], [], []
     has_radius = atk is not None and hasattr(atk, "last_radius")
+    has_queries = atk is not None and hasattr(atk, "last_queries")
     if perturbation_stats:
         from . import hip_ops
 
@@ -474,6 +485,9 @@ def generate_attacks(
             if has_radius:
                 radii.append(atk.last_radius)                      # (B,), on this lane's stream; read after join()
                 lanes.keep(radii[-1])
+            if has_queries:
+                queries.append(atk.last_queries)                   # (B,) int32, on this lane's stream; read after join()
+                lanes.keep(queries[-1])
         else:
             batch_x_attacked = torch.clone(batch_x)
         batch_x_noproc, batch_x_attacked_noproc = batch_x, batch_x_attacked  # :223-224 (nothing below writes in place)
@@ -528,6 +542,9 @@ def generate_attacks(
     if has_radius:
         all_radii = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(radii).reshape(-1, 1))[:, 0], dtype=np.float32)
 
+    if has_queries:
+        all_queries = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(queries).reshape(-1, 1))[:, 0], dtype=np.int32)
+
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
@@ -541,6 +558,10 @@ def generate_attacks(
         report.update(metrics.radius_summary(all_radii, getattr(atk, "report_at", ())))
         if return_scores:
             report["scores"]["min_radius"] = all_radii
+    if has_queries:
+        report.update(metrics.query_summary(all_queries, atk.budget))
+        if return_scores:
+            report["scores"]["queries"] = all_queries
     if universal is not None:
         delta = universal.delta.detach().cpu().numpy()
         # rank order = utterance order for the one process that fits; a loaded perturbation was fitted on none of them
@@ -558,6 +579,8 @@ def generate_attacks(
             LOGGER.info(format_perturbation(report))
         if has_radius:
             LOGGER.info(format_min_radius(report))
+        if has_queries:
+            LOGGER.info(format_blackbox(report))
         if universal is not None:
             LOGGER.info(format_universal(report))
     return report

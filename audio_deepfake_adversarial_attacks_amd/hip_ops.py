@@ -20,6 +20,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   l1_box_project / apgdl1_*          no counterpart: l1-APGD (Croce & Hein, ICML 2021), torchattacks.APGDL1
   seg_pgd_step / snr_row_radius      no counterpart: PGD under an SNR or segmental-SNR budget, torchattacks.PGDSNR
   universal_colsum / universal_apply no counterpart: one perturbation for every utterance, torchattacks.UniversalPGD
+  spsa_probe / spsa_step             no counterpart: the score-based black-box attack, torchattacks.SPSA
 """
 from __future__ import annotations
 
@@ -1091,4 +1092,61 @@ def universal_apply(x, delta, row_weight=None, lo: float = 0.0, hi: float = 1.0,
         st = _lib.load().advstep_universal_apply_f32(x.data_ptr(), delta.data_ptr(), w, out.data_ptr(), B, T, lo, hi,
                                                      _stream(x.device))
     _lib.check(st, "advstep_universal_apply_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# score-based black-box attack (include/advstep_spsa.h): the probe slots of an iteration and the sign step along the estimate
+# ---------------------------------------------------------------------------------------------------------
+
+SPSA_MAX_DIRECTIONS = 1024                      # ADVSTEP_SPSA_MAX_DIRECTIONS: direction pairs of one iteration
+
+
+def spsa_probe(adv, delta: float, seed: int, offset: int = 0, s0: int = 0, ns: int = 1, lo: float = 0.0, hi: float = 1.0,
+               out=None):
+    """(ns, *adv.shape) float32: slots s0 .. s0 + ns - 1 of an SPSA iteration on `adv` (B, T) — slot 0 is adv itself, slot 1 + 2j is
+    clamp(adv + delta v_j, lo, hi), slot 2 + 2j is clamp(adv - delta v_j, lo, hi), v_j the Rademacher direction j that the
+    kernel regenerates from Philox (seed, offset; include/advstep_spsa.h has the bit mapping).  A fill in chunks gives the bytes
+    of a whole one.  One launch, 4 B read and 4 * ns B written per sample, no host read."""
+    _require(adv, "adv")
+    B, T = _rows(adv, "adv")
+    s0, ns = int(s0), int(ns)
+    if s0 < 0 or ns < 0 or s0 + ns > 1 + 2 * SPSA_MAX_DIRECTIONS:
+        raise ValueError(f"slots {s0} .. {s0 + ns - 1} are outside 0 .. {2 * SPSA_MAX_DIRECTIONS}")
+    if out is None:
+        out = torch.empty((ns,) + tuple(adv.shape), dtype=torch.float32, device=adv.device)
+    _require(out, "out")
+    if out.numel() != ns * B * T or out.device != adv.device:
+        raise ValueError(f"out must hold ({ns}, {B}, {T}) values on {adv.device}, got {tuple(out.shape)}@{out.device}")
+    with _Launch("spsa_probe", adv.device, tensors=(adv, out)):
+        st = _lib.load().advstep_spsa_probe_f32(adv.data_ptr(), out.data_ptr(), B, T, s0, ns, delta, lo, hi, seed, offset,
+                                                _stream(adv.device))
+    _lib.check(st, "advstep_spsa_probe_f32")
+    return out
+
+
+def spsa_step(adv, orig, z, labels, queries, alpha: float, eps: float, seed: int, offset: int = 0, lo: float = 0.0,
+              hi: float = 1.0, out=None):
+    """One SPSA sign step from the logits `z` (S, B) of the S = 1 + 2n slots `spsa_probe` filled with the same (seed, offset).
+    A row that slot 0 already shows fooled — (z[0, b] > 0) != (labels[b] == 1) — is copied and its `queries` (B, int32) entry
+    stays; every other row moves along sign(sum_j v_j d_j), d_j = -+(z[1 + 2j, b] - z[2 + 2j, b]), is projected exactly as by
+    `pgd_linf_step`, and counts S queries.  The estimate is never stored: one launch, 12 B per sample, no host read.  `out` may
+    be `adv`."""
+    _require(adv, "adv"), _require(orig, "orig"), _require(z, "z")
+    _same_shape(("adv", adv), ("orig", orig))
+    B, T = _rows(adv, "adv")
+    if z.dim() != 2 or z.shape[1] != B or z.shape[0] < 1 or z.shape[0] % 2 != 1 or z.device != adv.device:
+        raise ValueError(f"z must be (1 + 2n, {B}) on {adv.device}, got {tuple(z.shape)}@{z.device}")
+    n = (z.shape[0] - 1) // 2
+    if n > SPSA_MAX_DIRECTIONS:
+        raise ValueError(f"at most {SPSA_MAX_DIRECTIONS} direction pairs per iteration, got {n}")
+    _per_row(labels, "labels", B, torch.int64), _per_row(queries, "queries", B, torch.int32)
+    if labels.device != adv.device or queries.device != adv.device:
+        raise ValueError(f"labels and queries must live on {adv.device}, got {labels.device} and {queries.device}")
+    out = _out_like(adv, out)
+    with _Launch("spsa_step", adv.device, tensors=(adv, orig, out, z)):
+        st = _lib.load().advstep_spsa_step_f32(adv.data_ptr(), orig.data_ptr(), z.data_ptr(), labels.data_ptr(),
+                                               queries.data_ptr(), out.data_ptr(), B, T, n, alpha, eps, lo, hi, seed, offset,
+                                               _stream(adv.device))
+    _lib.check(st, "advstep_spsa_step_f32")
     return out

@@ -3,8 +3,9 @@ evaluate_models_on_adversarial_attacks.py:267-293), restated in numpy so the GPU
 scipy.  Each function documents the library routine it reproduces; tests pin them against values the
 reference's own calls produced (tests/golden/metrics.npz).  `perturbation_summary` is this package's own: the run-level
 digest of the per-utterance perturbation report (include/advstep_perturb.h); so is `radius_summary`, the digest of the
-per-utterance minimal radii of torchattacks.MinRadiusPGD, and `universal_summary`, the fitted / held-out split of a run with one
-universal perturbation (torchattacks.UniversalPGD)."""
+per-utterance minimal radii of torchattacks.MinRadiusPGD, `universal_summary`, the fitted / held-out split of a run with one
+universal perturbation (torchattacks.UniversalPGD), and `query_summary`, the digest of the per-utterance model queries of a
+score-based attack (torchattacks.SPSA)."""
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -247,3 +248,25 @@ def universal_summary(y, y_pred_label, fitted, delta, source_label: Optional[int
     out["universal/delta_linf"] = float(np.max(np.abs(d))) if d.size else float("nan")
     out["universal/delta_l2"] = float(np.sqrt(np.sum(d * d)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# black-box query report
+# ---------------------------------------------------------------------------------------------------------
+
+def query_summary(queries, budget: int) -> Dict[str, float]:
+    """Run-level digest of the model queries a score-based attack spent per utterance (torchattacks.SPSA's `last_queries`;
+    `budget` = steps * slots, what an utterance that is never fooled costs).
+
+    blackbox/queries_mean, queries_median   over all utterances
+    blackbox/stopped_early                  the share of utterances below the full budget, in [0, 1]: those the attack stopped
+                                            on because the detector's own answer showed them fooled (0 queries: the clean
+                                            input already was)
+    blackbox/budget                         `budget` itself
+    An empty vector gives NaN for the three statistics."""
+    q = np.asarray(queries, dtype=np.float64).ravel()
+    n = q.size
+    return {"blackbox/queries_mean": float(np.mean(q)) if n else float("nan"),
+            "blackbox/queries_median": float(np.median(q)) if n else float("nan"),
+            "blackbox/stopped_early": float(np.mean(q < budget)) if n else float("nan"),
+            "blackbox/budget": int(budget)}

@@ -4,7 +4,8 @@ The attacks the north-star path names — FGSM, PGD, PGDL2, CW — FAB (SURVEY.m
 reference's AttackEnum), APGD (the step-size-free gradient attack of AutoAttack), APGDL1 (its L1 member) and the momentum attacks made for
 transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), MultiAttack (the worst case over a list
 of them), MinRadiusPGD (each utterance's minimal radius, by bisection on the device), PGDSNR (PGD under a budget in dB of
-SNR or segmental SNR) and UniversalPGD (one perturbation fitted once and added to every utterance), with the reference's constructor
+SNR or segmental SNR), UniversalPGD (one perturbation fitted once and added to every utterance) and SPSA (the score-based
+black-box counterpart of PGD: queries instead of gradients), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -19,10 +20,11 @@ from .attacks.nifgsm import NIFGSM
 from .attacks.pgd import PGD
 from .attacks.pgdl2 import PGDL2
 from .attacks.pgdsnr import PGDSNR
+from .attacks.spsa import SPSA
 from .attacks.universal import UniversalPGD
 from .attacks.vmifgsm import VMIFGSM
 from .attacks.vnifgsm import VNIFGSM
 
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
-           "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD"]
+           "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA"]
