@@ -128,4 +128,15 @@ class AttackEnum(Enum):
     SPSA_eps001 = (torchattacks.SPSA, {"eps": 0.001, "steps": 20, "nb_sample": 8})
     SPSA100_eps003 = (torchattacks.SPSA, {"eps": 0.003, "steps": 100, "nb_sample": 16})
 
+    # --- additive members: PGD on the gradient averaged over draws of a simulated audio channel (torchattacks.EOTPGD with
+    # torchattacks.CHANNELS["mild"]), at the radii and 10 steps of the PGD triplet above, alpha = 2.5 * eps / steps, 4 draws per
+    # step: 40 model passes per utterance, EOTPGD40_eps003 (PGD40_eps003's radius) 160.  These budgets and the channel are
+    # choices of scale: nobody has measured what they achieve against these detectors or against a real device ---
+    EOTPGD = (torchattacks.EOTPGD, {"eps": 0.0005, "alpha": 2.5 * 0.0005 / 10, "steps": 10, "eot_iter": 4, "channel": "mild"})
+    EOTPGD_eps00075 = (torchattacks.EOTPGD, {"eps": 0.00075, "alpha": 2.5 * 0.00075 / 10, "steps": 10, "eot_iter": 4,
+                                             "channel": "mild"})
+    EOTPGD_eps001 = (torchattacks.EOTPGD, {"eps": 0.001, "alpha": 2.5 * 0.001 / 10, "steps": 10, "eot_iter": 4, "channel": "mild"})
+    EOTPGD40_eps003 = (torchattacks.EOTPGD, {"eps": 0.003, "alpha": 2.5 * 0.003 / 40, "steps": 40, "eot_iter": 4,
+                                             "channel": "mild"})    # budget unmeasured, as above
+
     NO_ATTACK = (None, {})

@@ -15,7 +15,8 @@ log line.  What is different is how the work is placed on the machine:
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
     (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
     all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD — one
-    all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA — one of the per-utterance queries).
+    all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA — one of the per-utterance queries;
+    `channel=` one all-reduce of its five counters).
     A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE process before the loop, or loaded from a
     file by every rank: no communication either way.
 """
@@ -161,6 +162,62 @@ def format_blackbox(report: Dict[str, float]) -> str:
     """The log line of a run whose attack carries `last_queries` (torchattacks.SPSA): the summary of metrics.query_summary."""
     return ", ".join(f"{k}: {v}" if k.endswith("budget") else f"{k}: {v:.4g}" for k, v in report.items()
                      if k.startswith("blackbox/"))
+
+
+def format_channel(report: Dict[str, float]) -> str:
+    """The log line of a `channel=` run: what is left of the attack after the simulated channel."""
+    return ", ".join(f"{k}: {v}" if k.endswith(("draws", "flipped")) else f"{k}: {v:.4f}" for k, v in report.items()
+                     if k.startswith("channel/"))
+
+
+class _ChannelScorer:
+    """What survives a simulated channel (torchattacks.Channel), counted on the device.  Per batch: N draws of the channel, the
+    SAME draws and noise for the attacked and the clean waveform (a paired comparison), in the waveform's domain (centre 0); the
+    detector scores each draw's B rows under no_grad, like every other forward of the loop.  Five counters: (utterance, draw)
+    pairs, attacked pairs judged right, clean pairs judged right, pairs of utterances the attack flipped without the channel
+    (clean judged right, attacked judged wrong, both unchannelled), and those of them still judged wrong through it.
+    The draws and the noise seeds come from generators of the scorer's own (seeded with `seed`), so the attack sees the random
+    numbers it would see in a run without `channel=`."""
+
+    def __init__(self, channel, draws: int, device, seed: int = 0):
+        from . import hip_ops
+        from .torchattacks.channel import resolve
+        self.ops, self.channel, self.draws = hip_ops, resolve(channel), int(draws)
+        if not 1 <= self.draws <= hip_ops.CHANNEL_MAX_DRAWS:
+            raise ValueError(f"channel_draws must lie between 1 and {hip_ops.CHANNEL_MAX_DRAWS}, got {draws}")
+        self.device = device
+        self.host_gen = torch.Generator().manual_seed(seed)
+        self.device_gen = torch.Generator(device=device).manual_seed(seed)
+        self.pairs = 0                                  # counted on the host: B per draw
+        self.counters: Dict[int, torch.Tensor] = {}     # lane -> the other four, int64 on the device
+
+    def batch(self, lane: int, model, clean, attacked, labels, attacked_label, post=None) -> None:
+        """`post`: the loop's preprocessing between the waveform and the detector (raw_sample_from_dataset), or None."""
+        ops, N = self.ops, self.draws
+        c = self.counters.setdefault(lane, torch.zeros(4, dtype=torch.int64, device=self.device))
+        y = labels.int()
+        zero = torch.zeros(clean.shape[0], dtype=torch.float32, device=clean.device)
+        params = self.channel.draw(N, clean, zero, generator=self.device_gen)
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=self.host_gen).item())   # on the host: no device sync
+        through_adv = ops.channel_apply(attacked.contiguous(), zero, *params, seed=seed)
+        through_clean = ops.channel_apply(clean.contiguous(), zero, *params, seed=seed)
+        score = (lambda x: score_batch(model, post(x))[1]) if post is not None else (lambda x: score_batch(model, x)[1])
+        flipped = (score(clean) == y) & (attacked_label != y)
+        for j in range(N):
+            adv_right, clean_right = score(through_adv[j]) == y, score(through_clean[j]) == y
+            c += torch.stack([adv_right.sum(), clean_right.sum(), flipped.sum(), (flipped & ~adv_right).sum()])
+        self.pairs += N * y.numel()
+
+    def report(self) -> Dict[str, float]:
+        """After the lanes have joined.  Accuracies in per cent, like adv_eval/accuracy; survival is a share."""
+        total = torch.stack(list(self.counters.values())).sum(dim=0)
+        total = torch.cat([torch.tensor([self.pairs], dtype=torch.int64, device=total.device), total])
+        if rank_and_world()[1] > 1:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM)
+        pairs, adv_right, clean_right, flipped, still = (int(v) for v in total.cpu().tolist())
+        return {"channel/accuracy": (adv_right / pairs) * 100, "channel/clean_accuracy": (clean_right / pairs) * 100,
+                "channel/survival": still / flipped if flipped else 0.0, "channel/flipped": flipped // self.draws,
+                "channel/draws": self.draws}
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -379,6 +436,8 @@ def generate_attacks(
     universal_fit: Optional[int] = None,
     universal_load: Optional[Union[str, os.PathLike]] = None,
     universal_save: Optional[Union[str, os.PathLike]] = None,
+    channel: Optional[Any] = None,
+    channel_draws: int = 1,
 ) -> Dict[str, float]:
     """Reference signature (:146-157) plus additive keywords: `dataset` (a ready Dataset yielding the reference's
     4-tuple; without it the `DetectionDataset` over `datasets_paths` is built as in the reference's `get_dataset`,
@@ -409,6 +468,13 @@ def generate_attacks(
     `universal_load`.  Adds the `universal/*` keys of `metrics.universal_summary` (fitted against held-out utterances), one
     more log line and, with `return_scores`, `scores["universal_delta"]`; any other attack: nothing, and the three keywords
     must be left at None.
+    `channel` (a torchattacks.Channel or the name of a preset in torchattacks.CHANNELS) measures what is left of the attack —
+    any attack, or none — after a simulated audio channel: after the attack, the attacked and the clean waveform each go through
+    `channel_draws` draws of it (`_ChannelScorer`: the same draws for both, centre 0) and the detector scores them.  Adds
+    `channel/accuracy` (per cent, over all (utterance, draw) pairs), `channel/clean_accuracy`, `channel/survival` (the share of
+    pairs still misclassified among the utterances the attack flipped without the channel; 0 when it flipped none:
+    `channel/flipped` says how many), one log line and, over several ranks, one all-reduce of five counters.  `adv_eval/*` and
+    every other key are computed exactly as without it, from the unchannelled waveform.
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -474,6 +540,7 @@ def generate_attacks(
     has_queries = atk is not None and hasattr(atk, "last_queries")
     if perturbation_stats:
         from . import hip_ops
+    through = _ChannelScorer(channel, channel_draws, device, seed + rank) if channel is not None else None
 
     for i, (batch_x, batch_sr, batch_y, batch_metadata, ready) in enumerate(_device_batches(test_loader, device)):
       with lanes.batch(i, tuple(batch_x.shape), ready, (batch_x, batch_y)) as lane:
@@ -499,6 +566,10 @@ def generate_attacks(
             batch_x_attacked, _ = SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(
                 batch_x_attacked, batch_sr, wave_fake_trim=wave_fake_trim)
         batch_preds, batch_preds_label = score_batch(model, batch_x_attacked)
+        if through is not None:
+            post = ((lambda x: SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(x, batch_sr, wave_fake_trim=wave_fake_trim)[0])
+                    if raw_sample_from_dataset else None)
+            through.batch(lane, model, batch_x_noproc, batch_x_attacked_noproc, batch_y, batch_preds_label, post)
 
         if on_attack_end_callback is not None:  # :240-259
             if raw_sample_from_dataset:
@@ -571,6 +642,8 @@ def generate_attacks(
             report["scores"]["universal_delta"] = delta
     if multi is not None:
         report["multi_attack/remaining"] = remaining
+    if through is not None:
+        report.update(through.report())
     if rank == 0:
         if multi is not None:
             LOGGER.info(multi._return_sr_record(remaining))
@@ -583,4 +656,6 @@ def generate_attacks(
             LOGGER.info(format_blackbox(report))
         if universal is not None:
             LOGGER.info(format_universal(report))
+        if through is not None:
+            LOGGER.info(format_channel(report))
     return report

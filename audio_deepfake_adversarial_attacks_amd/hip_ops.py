@@ -21,6 +21,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   seg_pgd_step / snr_row_radius      no counterpart: PGD under an SNR or segmental-SNR budget, torchattacks.PGDSNR
   universal_colsum / universal_apply no counterpart: one perturbation for every utterance, torchattacks.UniversalPGD
   spsa_probe / spsa_step             no counterpart: the score-based black-box attack, torchattacks.SPSA
+  channel_apply / _adjoint / _eot_step  no counterpart: the simulated audio channel of torchattacks.Channel / EOTPGD
 """
 from __future__ import annotations
 
@@ -1149,4 +1150,102 @@ def spsa_step(adv, orig, z, labels, queries, alpha: float, eps: float, seed: int
                                                queries.data_ptr(), out.data_ptr(), B, T, n, alpha, eps, lo, hi, seed, offset,
                                                _stream(adv.device))
     _lib.check(st, "advstep_spsa_step_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# simulated audio channel (include/advstep_channel.h): K draws of a FIR + delay + gain + noise, and the adjoint summed over the draws
+# ---------------------------------------------------------------------------------------------------------
+
+CHANNEL_MAX_TAPS = 256                          # ADVSTEP_CHANNEL_MAX_TAPS
+CHANNEL_MAX_DRAWS = 64                          # ADVSTEP_CHANNEL_MAX_DRAWS
+
+
+def _channel_params(taps, shift, gain, B: int, device, noise=None) -> Tuple[int, int]:
+    """(K, L) of a draw's parameter tensors: taps (K, B, L) float32, shift (K, B) int32, gain (K, B) and noise (K, B) float32."""
+    _require(taps, "taps"), _require(shift, "shift", torch.int32), _require(gain, "gain")
+    if taps.dim() != 3 or taps.shape[1] != B:
+        raise ValueError(f"taps must be (K, {B}, L), got {tuple(taps.shape)}")
+    K, L = int(taps.shape[0]), int(taps.shape[2])
+    if not 1 <= L <= CHANNEL_MAX_TAPS:
+        raise ValueError(f"a channel has between 1 and {CHANNEL_MAX_TAPS} taps, got {L}")
+    if K > CHANNEL_MAX_DRAWS:
+        raise ValueError(f"at most {CHANNEL_MAX_DRAWS} draws per call, got {K}")
+    named = [("shift", shift), ("gain", gain)] + ([("noise", _require(noise, "noise"))] if noise is not None else [])
+    for name, t in named:
+        if tuple(t.shape) != (K, B):
+            raise ValueError(f"{name} must be ({K}, {B}), got {tuple(t.shape)}")
+    for name, t in [("taps", taps)] + named:
+        if t.device != device:
+            raise ValueError(f"{name} must live on {device}, got {t.device}")
+    return K, L
+
+
+def channel_apply(x, center, taps, shift, gain, noise, seed: int, offset: int = 0, out=None):
+    """(K, *x.shape) float32: K draws of the channel on x (B, T) — out[j] = (c + gain[j] * FIR(taps[j], x - c delayed by shift[j]))
+    + noise[j] * n, with silence (c = `center`, one value per row) outside the utterance and n in [-1, 1) regenerated from Philox
+    (seed, offset + j); include/advstep_channel.h fixes the arithmetic.  Not clamped.  One launch, 4 B read and 4 K B written per
+    sample, no host read."""
+    _require(x, "x")
+    B, T = _rows(x, "x")
+    _per_row(center, "center", B)
+    if center.device != x.device:
+        raise ValueError(f"center must live on {x.device}, got {center.device}")
+    K, L = _channel_params(taps, shift, gain, B, x.device, noise)
+    if out is None:
+        out = torch.empty((K,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    _require(out, "out")
+    if out.numel() != K * B * T or out.device != x.device:
+        raise ValueError(f"out must hold ({K}, {B}, {T}) values on {x.device}, got {tuple(out.shape)}@{out.device}")
+    with _Launch("channel_apply", x.device, work=2.0 * K * L * B * T, tensors=(x, out)):
+        st = _lib.load().advstep_channel_apply_f32(x.data_ptr(), center.data_ptr(), taps.data_ptr(), shift.data_ptr(),
+                                                   gain.data_ptr(), noise.data_ptr(), out.data_ptr(), B, T, K, L, seed, offset,
+                                                   _stream(x.device))
+    _lib.check(st, "advstep_channel_apply_f32")
+    return out
+
+
+def _channel_grads(grads, like, name: str = "grads") -> int:
+    _require(grads, name)
+    if grads.dim() < 2 or tuple(grads.shape[1:]) != tuple(like.shape) or grads.device != like.device:
+        raise ValueError(f"{name} must be (K, {', '.join(map(str, like.shape))}) on {like.device}, got "
+                         f"{tuple(grads.shape)}@{grads.device}")
+    return int(grads.shape[0])
+
+
+def channel_adjoint(grads, taps, shift, gain, out=None):
+    """(B, T) float32: the channel's adjoint applied to the K gradients `grads` (K, B, T) and summed over the draws in draw
+    order — the gradient at the channel's input of sum_j loss_j(channel_j(x)).  One launch, 4 K B read and 4 B written per sample."""
+    _require(grads, "grads")
+    if grads.dim() < 3:
+        raise ValueError(f"grads: expected (K, B, ...), got {tuple(grads.shape)}")
+    like = grads[0]
+    B, T = _rows(like, "grads[0]")
+    K, L = _channel_params(taps, shift, gain, B, grads.device)
+    if K != grads.shape[0]:
+        raise ValueError(f"grads holds {grads.shape[0]} draws, the parameters {K}")
+    out = _out_like(like, out)
+    with _Launch("channel_adjoint", grads.device, work=2.0 * K * L * B * T, tensors=(grads, out)):
+        st = _lib.load().advstep_channel_adjoint_f32(grads.data_ptr(), taps.data_ptr(), shift.data_ptr(), gain.data_ptr(),
+                                                     out.data_ptr(), B, T, K, L, _stream(grads.device))
+    _lib.check(st, "advstep_channel_adjoint_f32")
+    return out
+
+
+def channel_eot_step(adv, orig, grads, taps, shift, gain, alpha: float, eps: float, lo: float = 0.0, hi: float = 1.0, out=None):
+    """`pgd_linf_step(adv, channel_adjoint(grads, taps, shift, gain), orig, alpha, eps)` byte for byte, in one launch: the summed
+    gradient stays in registers.  4 K + 12 B per sample.  `out` may be `adv`."""
+    _require(adv, "adv"), _require(orig, "orig")
+    _same_shape(("adv", adv), ("orig", orig))
+    B, T = _rows(adv, "adv")
+    Kg = _channel_grads(grads, adv)
+    K, L = _channel_params(taps, shift, gain, B, adv.device)
+    if K != Kg:
+        raise ValueError(f"grads holds {Kg} draws, the parameters {K}")
+    out = _out_like(adv, out)
+    with _Launch("channel_eot_step", adv.device, work=2.0 * K * L * B * T, tensors=(adv, orig, grads, out)):
+        st = _lib.load().advstep_channel_eot_step_f32(adv.data_ptr(), orig.data_ptr(), grads.data_ptr(), taps.data_ptr(),
+                                                      shift.data_ptr(), gain.data_ptr(), out.data_ptr(), B, T, K, L, alpha, eps,
+                                                      lo, hi, _stream(adv.device))
+    _lib.check(st, "advstep_channel_eot_step_f32")
     return out

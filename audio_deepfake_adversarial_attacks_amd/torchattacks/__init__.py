@@ -5,12 +5,14 @@ reference's AttackEnum), APGD (the step-size-free gradient attack of AutoAttack)
 transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), MultiAttack (the worst case over a list
 of them), MinRadiusPGD (each utterance's minimal radius, by bisection on the device), PGDSNR (PGD under a budget in dB of
 SNR or segmental SNR), UniversalPGD (one perturbation fitted once and added to every utterance) and SPSA (the score-based
-black-box counterpart of PGD: queries instead of gradients), with the reference's constructor
+black-box counterpart of PGD: queries instead of gradients) and EOTPGD (PGD on a gradient summed over passes, here over draws of a
+simulated audio channel: `Channel`, `CHANNELS`), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
 from .attacks.apgdl1 import APGDL1
 from .attacks.cw import CW
+from .attacks.eotpgd import EOTPGD
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
 from .attacks.mifgsm import MIFGSM
@@ -24,7 +26,8 @@ from .attacks.spsa import SPSA
 from .attacks.universal import UniversalPGD
 from .attacks.vmifgsm import VMIFGSM
 from .attacks.vnifgsm import VNIFGSM
+from .channel import CHANNELS, Channel
 
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
-           "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA"]
+           "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS"]

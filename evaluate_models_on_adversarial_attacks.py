@@ -85,6 +85,12 @@ def parse_arguments(argv=None):
                              "more than one process)")
     parser.add_argument("--universal_save", type=str, default=None, metavar="PATH",
                         help="universal attacks: write the perturbation the run used to this .npz")
+    parser.add_argument("--channel", type=str, default=None, metavar="NAME",
+                        help="also score the attacked and the clean waveforms through a simulated audio channel (a preset of "
+                             "torchattacks.CHANNELS: identity, mild, handset): channel/* keys and one more log line; works "
+                             "with every attack and with NO_ATTACK")
+    parser.add_argument("--channel_draws", type=int, default=1, metavar="N",
+                        help="draws of the channel per utterance (default 1)")
     return parser.parse_args(argv)
 
 
@@ -145,6 +151,8 @@ def main(args):
         universal_fit=args.universal_fit,
         universal_load=args.universal_load,
         universal_save=args.universal_save,
+        channel=args.channel,
+        channel_draws=args.channel_draws,
     )
     if world > 1:
         dist.destroy_process_group()
