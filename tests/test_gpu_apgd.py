@@ -194,6 +194,17 @@ def test_l2_step_kernel(cuda, B, T, a):
     assert (d[ok].norm(dim=1) <= eps * (1 + 1e-6)).all()
 
 
+def l2_step_f64(cur, prev, grad, x, step, eps, a):
+    """The L2 step's chain (apgd.py:140-157) in float64 from the float32 inputs, on the CPU."""
+    X, Cu, P, G = (t.cpu().double() for t in (x, cur, prev, grad))
+    x1 = Cu + step.cpu().double()[:, None] * G / (G.norm(dim=1, keepdim=True) + 1e-12)
+    n1 = (x1 - X).norm(dim=1, keepdim=True)
+    x1 = (X + (x1 - X) / (n1 + 1e-12) * torch.clamp(n1, max=eps)).clamp(0, 1)
+    x2 = Cu + (x1 - Cu) * a + (Cu - P) * (1 - a)
+    n2 = (x2 - X).norm(dim=1, keepdim=True)
+    return (X + (x2 - X) / (n2 + 1e-12) * torch.clamp(n2 + 1e-12, max=eps)).clamp(0, 1)
+
+
 def test_l2_step_error_against_float64(cuda):
     """The bound L2_ATOL: the device's and the CPU table's distance from a float64 evaluation of the same chain."""
     ops = hip()
@@ -203,13 +214,7 @@ def test_l2_step_error_against_float64(cuda):
     eps, a = 0.1, 0.75
     step = torch.full((B,), 2 * eps, device=cuda)
     got = ops.apgd_l2_step(cur, prev, grad, x, step, eps, a).cpu().double()
-    X, Cu, P, G = (t.cpu().double() for t in (x, cur, prev, grad))
-    x1 = Cu + step.cpu().double()[:, None] * G / (G.norm(dim=1, keepdim=True) + 1e-12)
-    n1 = (x1 - X).norm(dim=1, keepdim=True)
-    x1 = (X + (x1 - X) / (n1 + 1e-12) * torch.clamp(n1, max=eps)).clamp(0, 1)
-    x2 = Cu + (x1 - Cu) * a + (Cu - P) * (1 - a)
-    n2 = (x2 - X).norm(dim=1, keepdim=True)
-    ref = (X + (x2 - X) / (n2 + 1e-12) * torch.clamp(n2 + 1e-12, max=eps)).clamp(0, 1)
+    ref = l2_step_f64(cur, prev, grad, x, step, eps, a)
     cpu = C.apgd_l2_step(cur, prev, grad, x, step, eps, a).cpu().double()
     ok = torch.isfinite(ref)
     err_dev, err_cpu = (got - ref)[ok].abs().max().item(), (cpu - ref)[ok].abs().max().item()
