@@ -282,8 +282,9 @@ __global__ __launch_bounds__(kBlock) void pool2_forward_kernel(const float *__re
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const bool in = e < 2 || two;
-            r0[e] = in ? ap[e] + (bp ? bp[e] : 0.0f) : 0.0f;
-            r1[e] = in ? ap[W + e] + (bp ? bp[W + e] : 0.0f) : 0.0f;
+            // without b the element itself, as on the float4 route: a + 0.0f would turn -0.0 into +0.0 (seen in xw)
+            r0[e] = in ? (bp ? ap[e] + bp[e] : ap[e]) : 0.0f;
+            r1[e] = in ? (bp ? ap[W + e] + bp[W + e] : ap[W + e]) : 0.0f;
         }
     }
     float raw[KIND == 1 ? 8 : 1];                                 // KIND 1: the un-gated inputs, for `xw`
@@ -363,7 +364,9 @@ __global__ __launch_bounds__(kBlock) void pool2_backward_kernel(const float *__r
         }
         if (g) {
             float *gp = g + (nc * H + h) * W + w0;
-            if (w0 + 3 < W && (W & 3) == 0) *reinterpret_cast<float4 *>(gp) = make_float4(out[0], out[1], out[2], out[3]);
+            // float4 only from a 16-byte aligned base (the ABI promises contiguous float32, not alignment): as the forward's loads
+            if (w0 + 3 < W && (W & 3) == 0 && (reinterpret_cast<uintptr_t>(g) & 15u) == 0)
+                *reinterpret_cast<float4 *>(gp) = make_float4(out[0], out[1], out[2], out[3]);
             else
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
