@@ -139,4 +139,14 @@ class AttackEnum(Enum):
     EOTPGD40_eps003 = (torchattacks.EOTPGD, {"eps": 0.003, "alpha": 2.5 * 0.003 / 40, "steps": 40, "eot_iter": 4,
                                              "channel": "mild"})    # budget unmeasured, as above
 
+    # --- additive members: the sparse (L0) threat model (torchattacks.PGDL0: PGD0 of Croce & Hein, ICCV 2019): at most k samples
+    # of an utterance change, each as far as [0, 1] allows - a handful of clicks.  k = 64 is about 0.1 % of a 64 600-sample
+    # utterance; *_cap005 also bounds every change by 0.05 (the paper's "sparse and bounded" variant).  20 steps of
+    # alpha = 0.15 per dimension, the paper's scale.  These budgets are choices of scale: nobody has measured what they achieve
+    # against these detectors ---
+    PGDL0 = (torchattacks.PGDL0, {"k": 64, "alpha": 0.15, "steps": 20})
+    PGDL0_k256 = (torchattacks.PGDL0, {"k": 256, "alpha": 0.15, "steps": 20})
+    PGDL0_k1024 = (torchattacks.PGDL0, {"k": 1024, "alpha": 0.15, "steps": 20})
+    PGDL0_k1024_cap005 = (torchattacks.PGDL0, {"k": 1024, "alpha": 0.15, "steps": 20, "eps_inf": 0.05})
+
     NO_ATTACK = (None, {})

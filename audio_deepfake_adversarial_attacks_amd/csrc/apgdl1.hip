@@ -37,48 +37,7 @@ __device__ __forceinline__ float l1_move(float ad, float cap, float lam) {
 }
 __device__ __forceinline__ float l1_cap(float d, float xi) { return d > 0.0f ? 1.0f - xi : xi; }
 
-// visit_rows for the search passes: f(s) with s[k] = the sample of row in[k], in visit_rows' order and sample -> thread map, but
-// with the next element's loads issued before this element's arithmetic (with one quad per thread in flight a pass waits out
-// a full L2 latency per quad).
-template <bool VEC, int N, class F>
-__device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], int64_t T, F f) {
-    using Elem = std::conditional_t<VEC, float4, float>;
-    const int64_t n = VEC ? T >> 2 : T;
-    int64_t e = threadIdx.x;
-    Elem next[N];
-    if (e < n) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e];
-    }
-    for (; e < n; e += kRow) {
-        Elem v[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = next[k];
-        if (e + kRow < n) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e + kRow];
-        }
-        float s[N];
-        if constexpr (VEC) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k] = v[k].x;
-            f(s);
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k] = v[k].y;
-            f(s);
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k] = v[k].z;
-            f(s);
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k] = v[k].w;
-            f(s);
-        } else {
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k] = v[k];
-            f(s);
-        }
-    }
-}
+// (the search passes traverse with row_workgroup.h's visit_rows_ahead: the next element's loads before this one's arithmetic)
 
 // out row = P(u row; x row, eps), phi0 = phi(0) as the caller's pass over (x, u) summed it.  ur may be outr.
 template <bool VEC>

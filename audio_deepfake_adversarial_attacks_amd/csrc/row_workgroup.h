@@ -1,4 +1,4 @@
-// row_workgroup.h — the one-workgroup-per-row geometry of fab.hip and apgdl1.hip (internal: not part of the C ABI in include/).
+// row_workgroup.h — the one-workgroup-per-row geometry of fab.hip, apgdl1.hip and l0.hip (internal: not part of the C ABI in include/).
 //
 // One workgroup of kRow = 1024 threads (16 wave64) owns one row of T samples and makes several passes over it; at the repo's
 // T = 64 600 a row is 258 KB: it does not fit LDS, but stays L2 / Infinity-Cache resident between the passes, so only the first
@@ -92,6 +92,53 @@ __device__ __forceinline__ void visit_rows(const float *const (&in)[N], int64_t 
 template <bool VEC, size_t N, class F>
 __device__ __forceinline__ void map_rows(const float *const (&in)[N], float *out, int64_t T, F f) {
     traverse<VEC, true>(in, out, T, f, std::make_index_sequence<N>());
+}
+
+// visit_rows for the search passes of apgdl1.hip and l0.hip: f(s) with s[k] = the sample of row in[k], or f(i, s) where f takes
+// the sample index, in visit_rows' order and sample -> thread map, but with the next element's loads issued before this
+// element's arithmetic (with one quad per thread in flight a pass waits out a full L2 latency per quad).
+template <bool VEC, int N, class F>
+__device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], int64_t T, F f) {
+    using Elem = std::conditional_t<VEC, float4, float>;
+    auto at = [&](int64_t i, const float(&s)[N]) {
+        if constexpr (std::is_invocable_v<F, int64_t, const float(&)[N]>) f(i, s);
+        else f(s);
+    };
+    const int64_t n = VEC ? T >> 2 : T;
+    int64_t e = threadIdx.x;
+    Elem next[N];
+    if (e < n) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e];
+    }
+    for (; e < n; e += kRow) {
+        Elem v[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = next[k];
+        if (e + kRow < n) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e + kRow];
+        }
+        float s[N];
+        if constexpr (VEC) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].x;
+            at(4 * e, s);
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].y;
+            at(4 * e + 1, s);
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].z;
+            at(4 * e + 2, s);
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k].w;
+            at(4 * e + 3, s);
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = v[k];
+            at(e, s);
+        }
+    }
 }
 
 inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }

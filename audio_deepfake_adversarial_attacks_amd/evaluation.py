@@ -16,6 +16,7 @@ log line.  What is different is how the work is placed on the machine:
     (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
     all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD — one
     all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA — one of the per-utterance queries;
+    an attack that carries `last_changed` — PGDL0 — one of the per-utterance changed-sample counts;
     `channel=` one all-reduce of its five counters).
     A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE process before the loop, or loaded from a
     file by every rank: no communication either way.
@@ -162,6 +163,12 @@ def format_blackbox(report: Dict[str, float]) -> str:
     """The log line of a run whose attack carries `last_queries` (torchattacks.SPSA): the summary of metrics.query_summary."""
     return ", ".join(f"{k}: {v}" if k.endswith("budget") else f"{k}: {v:.4g}" for k, v in report.items()
                      if k.startswith("blackbox/"))
+
+
+def format_sparse(report: Dict[str, float]) -> str:
+    """The log line of a run whose attack carries `last_changed` (torchattacks.PGDL0): the summary of metrics.sparsity_summary."""
+    return ", ".join(f"{k}: {v}" if k.endswith(("_max", "/k")) else f"{k}: {v:.4g}" for k, v in report.items()
+                     if k.startswith("sparse/"))
 
 
 def format_channel(report: Dict[str, float]) -> str:
@@ -461,6 +468,9 @@ def generate_attacks(
     An attack that carries `last_queries` (torchattacks.SPSA: the model queries each utterance spent, on the device) adds the
     `blackbox/*` keys of `metrics.query_summary` against the attack's `budget`, one more log line and, with `return_scores`,
     the per-utterance counts under `scores["queries"]`; any other attack: nothing.
+    An attack that carries `last_changed` (torchattacks.PGDL0: the samples of each utterance it changed, on the device) adds the
+    `sparse/*` keys of `metrics.sparsity_summary` against the attack's `k`, one more log line and, with `return_scores`, the
+    per-utterance counts under `scores["changed"]`; any other attack: nothing.
     A universal attack (`is_universal`: torchattacks.UniversalPGD) gets its perturbation BEFORE the loop (`prepare_universal`):
     loaded from `universal_load`, or fitted on the first `universal_fit` batches of this run's batch order (None: a quarter of
     them, at least 1), which are kept on the device meanwhile (universal_fit x B x T x 4 bytes); `universal_save` writes it.  The
@@ -535,9 +545,10 @@ def generate_attacks(
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
     seen_total = 0
-    y_pred, y_pred_label, y, perturbation, radii, queries = [], [], [], [], [], []
+    y_pred, y_pred_label, y, perturbation, radii, queries, changed = [], [], [], [], [], [], []
     has_radius = atk is not None and hasattr(atk, "last_radius")
     has_queries = atk is not None and hasattr(atk, "last_queries")
+    has_changed = atk is not None and hasattr(atk, "last_changed")
     if perturbation_stats:
         from . import hip_ops
     through = _ChannelScorer(channel, channel_draws, device, seed + rank) if channel is not None else None
@@ -555,6 +566,9 @@ def generate_attacks(
             if has_queries:
                 queries.append(atk.last_queries)                   # (B,) int32, on this lane's stream; read after join()
                 lanes.keep(queries[-1])
+            if has_changed:
+                changed.append(atk.last_changed)                   # (B,) int64, on this lane's stream; read after join()
+                lanes.keep(changed[-1])
         else:
             batch_x_attacked = torch.clone(batch_x)
         batch_x_noproc, batch_x_attacked_noproc = batch_x, batch_x_attacked  # :223-224 (nothing below writes in place)
@@ -616,6 +630,9 @@ def generate_attacks(
     if has_queries:
         all_queries = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(queries).reshape(-1, 1))[:, 0], dtype=np.int32)
 
+    if has_changed:
+        all_changed = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(changed).reshape(-1, 1))[:, 0], dtype=np.int64)
+
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
@@ -633,6 +650,10 @@ def generate_attacks(
         report.update(metrics.query_summary(all_queries, atk.budget))
         if return_scores:
             report["scores"]["queries"] = all_queries
+    if has_changed:
+        report.update(metrics.sparsity_summary(all_changed, atk.k))
+        if return_scores:
+            report["scores"]["changed"] = all_changed
     if universal is not None:
         delta = universal.delta.detach().cpu().numpy()
         # rank order = utterance order for the one process that fits; a loaded perturbation was fitted on none of them
@@ -654,6 +675,8 @@ def generate_attacks(
             LOGGER.info(format_min_radius(report))
         if has_queries:
             LOGGER.info(format_blackbox(report))
+        if has_changed:
+            LOGGER.info(format_sparse(report))
         if universal is not None:
             LOGGER.info(format_universal(report))
         if through is not None:

@@ -18,6 +18,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   perturbation_stats                 src/aa/qualitative/attacks_postanalysis.py (the distortion figures beside the WAV pairs)
   row_pgd_*_step / radius_*          no counterpart: the per-row radius steps and the bisection of torchattacks.MinRadiusPGD
   l1_box_project / apgdl1_*          no counterpart: l1-APGD (Croce & Hein, ICML 2021), torchattacks.APGDL1
+  l0_box_project / pgdl0_step        no counterpart: PGD0 (Croce & Hein, ICCV 2019), torchattacks.PGDL0
   seg_pgd_step / snr_row_radius      no counterpart: PGD under an SNR or segmental-SNR budget, torchattacks.PGDSNR
   universal_colsum / universal_apply no counterpart: one perturbation for every utterance, torchattacks.UniversalPGD
   spsa_probe / spsa_step             no counterpart: the score-based black-box attack, torchattacks.SPSA
@@ -728,6 +729,54 @@ def apgdl1_checkpoint(cur, x_best, x, state, eps: float) -> None:
                                                        state.topk.data_ptr(), state.step_size.data_ptr(), B, T,
                                                        _positive_eps(eps), _stream(cur.device))
     _lib.check(st, "advstep_apgdl1_checkpoint_f32")
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the L0 threat model (include/advstep_l0.h): the exact-k projection and the PGD0 step of torchattacks.PGDL0
+# ---------------------------------------------------------------------------------------------------------
+
+def _l0_budget(k, eps_inf) -> Tuple[int, float]:
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1 (the samples an utterance may change), got {k!r}")
+    if not eps_inf > 0:
+        raise ValueError(f"the per-sample cap eps_inf must be positive (inf: none), got {eps_inf!r}")
+    return int(k), float(eps_inf)
+
+
+def l0_box_project(x, u, k: int, eps_inf: float = float("inf"), out=None):
+    """Projection of each row of u onto {z : at most k samples differ from x, max(0, x - eps_inf) <= z <= min(1, x + eps_inf)}
+    (x in [0, 1]): the k samples whose keeping saves most squared distance, ties to the lower index; `out` may be `u`."""
+    _require(x, "x"), _require(u, "u")
+    _same_shape(("x", x), ("u", u))
+    B, T = _rows(x, "x")
+    k, eps_inf = _l0_budget(k, eps_inf)
+    out = _out_like(u, out)
+    with _Launch("l0_box_project", x.device, tensors=(x, u, out)):
+        st = _lib.load().advstep_l0_box_project_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), k, eps_inf, B, T,
+                                                    _stream(x.device))
+    _lib.check(st, "advstep_l0_box_project_f32")
+    return out
+
+
+def pgdl0_step(cur, grad, x, step: float, k: int, eps_inf: float = float("inf"), out=None, return_stats: bool = False):
+    """One PGD0 iteration: cur + step * grad / (||grad||_1 + 1e-10) per row, then `l0_box_project` about x; `out` may be `cur`.
+    return_stats: also (B, 4) = the row's ||grad||_1, score threshold, scores above it, index of the last kept tie."""
+    named = (("cur", cur), ("grad", grad), ("x", x))
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    B, T = _rows(cur, "cur")
+    k, eps_inf = _l0_budget(k, eps_inf)
+    if not step >= 0:
+        raise ValueError(f"step must be non-negative, got {step!r}")
+    out = _out_like(cur, out)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=cur.device) if return_stats else None
+    with _Launch("pgdl0_step", cur.device, tensors=(cur, grad, x, out)):
+        st = _lib.load().advstep_pgdl0_step_f32(cur.data_ptr(), grad.data_ptr(), x.data_ptr(), out.data_ptr(),
+                                                stats.data_ptr() if return_stats else None, step, k, eps_inf, B, T,
+                                                _stream(cur.device))
+    _lib.check(st, "advstep_pgdl0_step_f32")
+    return (out, stats) if return_stats else out
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -4,8 +4,9 @@ scipy.  Each function documents the library routine it reproduces; tests pin the
 reference's own calls produced (tests/golden/metrics.npz).  `perturbation_summary` is this package's own: the run-level
 digest of the per-utterance perturbation report (include/advstep_perturb.h); so is `radius_summary`, the digest of the
 per-utterance minimal radii of torchattacks.MinRadiusPGD, `universal_summary`, the fitted / held-out split of a run with one
-universal perturbation (torchattacks.UniversalPGD), and `query_summary`, the digest of the per-utterance model queries of a
-score-based attack (torchattacks.SPSA)."""
+universal perturbation (torchattacks.UniversalPGD), `query_summary`, the digest of the per-utterance model queries of a
+score-based attack (torchattacks.SPSA), and `sparsity_summary`, the digest of the per-utterance changed-sample counts of a
+sparse attack (torchattacks.PGDL0)."""
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -270,3 +271,23 @@ def query_summary(queries, budget: int) -> Dict[str, float]:
             "blackbox/queries_median": float(np.median(q)) if n else float("nan"),
             "blackbox/stopped_early": float(np.mean(q < budget)) if n else float("nan"),
             "blackbox/budget": int(budget)}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# sparse (L0) report
+# ---------------------------------------------------------------------------------------------------------
+
+def sparsity_summary(changed, k: int) -> Dict[str, float]:
+    """Run-level digest of the samples a sparse attack changed per utterance (torchattacks.PGDL0's `last_changed`, #{adv != x};
+    `k` = the attack's budget, which no count may exceed).
+
+    sparse/changed_mean, changed_median     over all utterances
+    sparse/changed_max                      the largest count (an int; 0 for an empty vector)
+    sparse/k                                `k` itself
+    An empty vector gives NaN for the mean and the median."""
+    c = np.asarray(changed, dtype=np.float64).ravel()
+    n = c.size
+    return {"sparse/changed_mean": float(np.mean(c)) if n else float("nan"),
+            "sparse/changed_median": float(np.median(c)) if n else float("nan"),
+            "sparse/changed_max": int(np.max(c)) if n else 0,
+            "sparse/k": int(k)}

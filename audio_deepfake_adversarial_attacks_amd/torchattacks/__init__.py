@@ -6,7 +6,7 @@ transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), Mu
 of them), MinRadiusPGD (each utterance's minimal radius, by bisection on the device), PGDSNR (PGD under a budget in dB of
 SNR or segmental SNR), UniversalPGD (one perturbation fitted once and added to every utterance) and SPSA (the score-based
 black-box counterpart of PGD: queries instead of gradients) and EOTPGD (PGD on a gradient summed over passes, here over draws of a
-simulated audio channel: `Channel`, `CHANNELS`), with the reference's constructor
+simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat model: at most k samples of an utterance change), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -20,6 +20,7 @@ from .attacks.minradius import MinRadiusPGD
 from .attacks.multiattack import MultiAttack
 from .attacks.nifgsm import NIFGSM
 from .attacks.pgd import PGD
+from .attacks.pgdl0 import PGDL0
 from .attacks.pgdl2 import PGDL2
 from .attacks.pgdsnr import PGDSNR
 from .attacks.spsa import SPSA
@@ -30,4 +31,5 @@ from .channel import CHANNELS, Channel
 
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
-           "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS"]
+           "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
+           "PGDL0"]
