@@ -19,7 +19,7 @@ SOURCES = [PKG / "csrc" / "advstep.hip", PKG / "csrc" / "lcnn_mfm.hip", PKG / "c
 HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants (tools/gen_stft_tables.py), #included by lfcc_stft.hip
            PKG / "csrc" / "advstep_common.h",      # internal helpers #included by every source
            PKG / "csrc" / "row_tiles.h",           # (tile, row) addressing, partial re-reductions, shared L2 arithmetic and launch of every row kernel
-           PKG / "csrc" / "row_workgroup.h",       # one 1024-thread workgroup per row: fab.hip's, apgdl1.hip's and l0.hip's reduction, traversal, launch
+           PKG / "csrc" / "row_workgroup.h",       # one 1024-thread workgroup per row: fab.hip's, apgdl1.hip's and l0.hip's reduction, traversal, digit-walk search, launch
            PKG / "csrc" / "lcnn_wino_plan.h",      # lcnn_wino.hip's enumerators, predicates and launch plan (host side)
            ROOT / "include" / "advstep.h", ROOT / "include" / "advstep_lcnn.h", ROOT / "include" / "advstep_frontend.h",
            ROOT / "include" / "advstep_fab.h", ROOT / "include" / "advstep_dataset.h", ROOT / "include" / "advstep_detector.h",

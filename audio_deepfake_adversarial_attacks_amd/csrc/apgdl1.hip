@@ -4,10 +4,10 @@
 // checkpoint.  The per-row loss / flags and the best-point tracking are apgd.hip's (advstep_apgd_eval / _track).
 //
 // Layout as fab.hip (row_workgroup.h): one workgroup of 1024 threads per row, the row re-read from L2 by every pass, float4
-// loads where the rows allow, fixed-order reductions.  No sort: both per-row searches walk the 31 bits of a non-negative
-// float's pattern kDigit bits at a time, one streaming pass per digit with 2^kDigit - 1 candidates, always all 11 passes.
-// A thread only ever re-reads samples it wrote itself (the traversal gives every pass the same sample -> thread map), so
-// the passes over the output row need no barrier beyond the reductions'.
+// loads where the rows allow, fixed-order reductions.  No sort: both per-row searches (the projection's lambda, the step's
+// top-k rank) are row_workgroup.h's digit_search over the 31 bits of a non-negative float's pattern, 11 streaming passes
+// each.  A thread only ever re-reads samples it wrote itself (the traversal gives every pass the same sample -> thread
+// map), so the passes over the output row need no barrier beyond the reductions'.
 //
 // Algorithmic bytes per row sample: step 4 x 12 (grad) + 12 + 4 (cur, grad, x -> u) + 8 x 12 (x, u) + 4 = 164 B, of which
 // 20 B are first touches and the rest L2 / Infinity-Cache re-reads; projection alone 8 x 13 + 4; checkpoint 8 B.
@@ -25,7 +25,6 @@
 
 namespace {
 
-constexpr int kDigit = 3, kCand = (1 << kDigit) - 1;   // candidates per streaming pass
 constexpr uint8_t kImproved = 2, kReset = 4;           // the flag bits of include/advstep_apgd.h
 
 // ---- the projection --------------------------------------------------------------------------------------------------
@@ -46,29 +45,20 @@ __device__ __forceinline__ void l1_box_project_row(const float *xr, const float 
     float lam = 0.0f;
     if (phi0 > eps) {                                          // workgroup-uniform: every thread holds the same phi0
         // rho = the largest bit pattern with phi > eps (phi(0) > eps: it exists); lam* is the next float
-        uint32_t rho = 0;
-        for (int top = 31; top > 0; top -= kDigit) {           // bits [shift, top) of the pattern: 11 passes
-            const int shift = top >= kDigit ? top - kDigit : 0;
-            const uint32_t limit = (1u << (top - shift)) - 1u; // candidates j = 1 .. limit
-            float cand[kCand], h[kCand];
+        float h[kCand];
+        const uint32_t rho = digit_search(
+            31, h, lds,
+            [&](uint32_t lo, int shift, float(&hh)[kCand]) {   // bin k = phi at candidate k + 1 itself: nothing to accumulate
+                float cand[kCand];
 #pragma unroll
-            for (int k = 0; k < kCand; ++k) {
-                cand[k] = __uint_as_float(rho | ((uint32_t)(k + 1) << shift));
-                h[k] = 0.0f;
-            }
-            visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float (&xu)[2]) {
-                const float d = xu[1] - xu[0], ad = fabsf(d), cap = l1_cap(d, xu[0]);
+                for (int k = 0; k < kCand; ++k) cand[k] = __uint_as_float(lo | ((uint32_t)(k + 1) << shift));
+                visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float (&xu)[2]) {
+                    const float d = xu[1] - xu[0], ad = fabsf(d), cap = l1_cap(d, xu[0]);
 #pragma unroll
-                for (int k = 0; k < kCand; ++k) h[k] += l1_move(ad, cap, cand[k]);
-            });
-            row_reduce<kCand>(h, SumOp(), lds);
-            uint32_t pick = 0;
-            for (uint32_t j = 1; j <= limit; ++j) {            // phi is non-increasing: the first j that fits ends the scan
-                if (h[j - 1] > eps) pick = j;
-                else break;
-            }
-            rho |= pick << shift;
-        }
+                    for (int k = 0; k < kCand; ++k) hh[k] += l1_move(ad, cap, cand[k]);
+                });
+            },
+            [&](float phi) { return phi > eps; });             // phi is non-increasing: the first candidate that fits ends the scan
         lam = __uint_as_float(rho + 1u);
     }
     map_rows<VEC>({xr, ur}, outr, T, [&](float xi, float ui) {
@@ -112,36 +102,20 @@ __global__ __launch_bounds__(kRow) void apgdl1_step_kernel(const float *cur, con
         float n = truncf(clampf((1.0f - topk[row]) * (float)T, 0.0f, (float)(T - 1)));
         if (!(n >= 0.0f)) n = 0.0f;                            // a NaN topk
         // rho = the largest key with #{key_i < rho} <= n, which is the key of rank n; `below` is that count
-        uint32_t rho = 0;
-        float below = 0.0f;
-        for (int top = 31; top > 0; top -= kDigit) {
-            const int shift = top >= kDigit ? top - kDigit : 0;
-            const uint32_t limit = (1u << (top - shift)) - 1u;
-            float h[kCand];
-#pragma unroll
-            for (int k = 0; k < kCand; ++k) h[k] = 0.0f;
-            visit_rows_ahead<VEC, 1>({gr}, T, [&](const float (&gi)[1]) {
-                const uint32_t key = __float_as_uint(gi[0]) & 0x7FFFFFFFu;   // |g|'s pattern: NaN sorts above +inf
-                if (key >= rho) {
-                    const uint32_t q = (key - rho) >> shift;   // lies below every candidate j > q
-#pragma unroll
-                    for (int k = 0; k < kCand; ++k) h[k] += (q == (uint32_t)k) ? 1.0f : 0.0f;
-                }
+        float h[kCand], below = 0.0f;
+        const uint32_t rho = digit_search(
+            31, h, lds,
+            [&](uint32_t lo, int shift, float(&hh)[kCand]) {
+                visit_rows_ahead<VEC, 1>({gr}, T, [&](const float (&gi)[1]) {
+                    bucket_add(hh, __float_as_uint(gi[0]) & 0x7FFFFFFFu, lo, shift, 1.0f);   // |g|'s pattern: NaN sorts above +inf
+                });
+            },
+            [&](float hj) {                                    // #{key < candidate j} = below + h[0..j)
+                const float at = below + hj;
+                if (!(at <= n)) return false;
+                below = at;
+                return true;
             });
-            row_reduce<kCand>(h, SumOp(), lds);
-            float run = below;
-            uint32_t pick = 0;
-            for (uint32_t j = 1; j <= limit; ++j) {            // #{key < candidate j} = below + h[0..j)
-                run += h[j - 1];
-                if (run <= n) {
-                    pick = j;
-                    below = run;
-                } else {
-                    break;
-                }
-            }
-            rho |= pick << shift;
-        }
         const float thr = __uint_as_float(rho);
         float cnt[1] = {0.0f};
         visit_rows<VEC>({gr}, T, [&](float gi) { cnt[0] += (fabsf(gi) >= thr && gi != 0.0f) ? 1.0f : 0.0f; });
@@ -235,8 +209,6 @@ __global__ __launch_bounds__(kRow) void apgdl1_checkpoint_kernel(const float *__
         }
     }
 }
-
-constexpr int64_t kMaxRowLength = int64_t(1) << 24;            // per-row counts are carried as exact floats
 
 template <bool PHILOX>
 int apgdl1_init(const float *x, const float *draw, float *out, int64_t B, int64_t T, float eps, uint64_t seed,

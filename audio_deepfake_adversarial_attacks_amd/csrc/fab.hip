@@ -10,8 +10,8 @@
 // keeps the data-dependent iteration counts workgroup-uniform.
 //
 // From advstep_common.h: the NaN-propagating maximum, the reduction operators, the wave butterfly, rows_vec, kMaxGridY.
-// From row_workgroup.h (shared with apgdl1.hip, the other file with 1024-thread rows): kRow, row_reduce, the row traversal
-// (visit_rows / map_rows) and launch_rows.
+// From row_workgroup.h (shared with apgdl1.hip and l0.hip, the other files with 1024-thread rows): kRow, row_reduce, the
+// row traversal (visit_rows / map_rows), the digit-walk search of the L1 projection (digit_search) and launch_rows.
 //
 // No sort: see include/advstep_fab.h.  Algorithmic bytes per row sample: hyperplane 8 B, projection 12 B (t, w in, d
 // out; the re-reads of the fixed-point iteration hit L2), combine 20 B, backward step 8-20 B.
@@ -241,19 +241,17 @@ __device__ __forceinline__ float l1_face(float ti, float wi) {
 
 // Greedy L1: coordinates in order of increasing key r = |1/w| (= decreasing |w|, index order within equal keys) move to
 // their face while the residual stays positive.  Keys are non-negative floats, so their bit patterns order like
-// integers: the last key whose residual-before is positive is found kDigit bits at a time (a histogram of the gains
-// over the 2^kDigit - 1 candidate prefixes per streaming pass, 11 passes for the 31 key bits), then the tie group is
-// walked in index order with a workgroup prefix scan.  The output row doubles as scratch for the keys (one division
-// per coordinate in total), so d must not alias t or w.
-constexpr int kDigit = 3, kBuckets = (1 << kDigit) - 1;
-
+// integers: the last key whose residual-before is positive is found by row_workgroup.h's digit_search over the 31 key
+// bits (the bins hold the gains between consecutive candidates), then the tie group is walked in index order with a
+// workgroup prefix scan.  The output row doubles as scratch for the keys (one division per coordinate in total), so d
+// must not alias t or w.
 template <bool VEC>
 __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__restrict__ t, const float *__restrict__ w,
                                                                  const float *__restrict__ wscale,
                                                                  const float *__restrict__ b, float *d,
                                                                  float *__restrict__ dnorm, int64_t R, int64_t w_rows,
                                                                  int64_t T) {
-    __shared__ float lds[kBuckets * kRowWaves];
+    __shared__ float lds[kCand * kRowWaves];
     __shared__ float wave_tot[kRowWaves];
     for (int64_t row = blockIdx.x; row < R; row += gridDim.x) {
         const float *tr = t + row * T, *wr = w + (row % w_rows) * T;
@@ -288,36 +286,20 @@ __global__ __launch_bounds__(kRow) void fab_projection_l1_kernel(const float *__
             uint32_t rho = 0;
             float before = c;
             if (c > 0.0f) {
-                for (int top = 31; top > 0; top -= kDigit) {          // bits [shift, top) of the key
-                    const int shift = top >= kDigit ? top - kDigit : 0;
-                    const uint32_t limit = (1u << (top - shift)) - 1u; // candidates j = 1 .. limit
-                    float h[kBuckets];
-#pragma unroll
-                    for (int q = 0; q < kBuckets; ++q) h[q] = 0.0f;
-                    visit_rows<VEC>({tr, wr, dr}, T, [&](float ti, float wraw, float ri) {
-                        const uint32_t key = __float_as_uint(ri);
-                        if (key >= rho) {
-                            const uint32_t q = (key - rho) >> shift;   // contributes to every candidate j > q
-                            const float gn = l1_gain(ti, sg * (sc * wraw));
-#pragma unroll
-                            for (int k = 0; k < kBuckets; ++k) h[k] += (q == (uint32_t)k) ? gn : 0.0f;
-                        }
+                float h[kCand];
+                rho = digit_search(
+                    31, h, lds,
+                    [&](uint32_t lo, int shift, float(&hh)[kCand]) {
+                        visit_rows<VEC>({tr, wr, dr}, T, [&](float ti, float wraw, float ri) {
+                            bucket_add(hh, __float_as_uint(ri), lo, shift, l1_gain(ti, sg * (sc * wraw)));
+                        });
+                    },
+                    [&](float hj) {                                    // residual before candidate j = before + h[0..j)
+                        const float at = before + hj;
+                        if (!(at > 0.0f)) return false;
+                        before = at;
+                        return true;
                     });
-                    row_reduce<kBuckets>(h, SumOp(), lds);
-                    float run = before;
-                    uint32_t pick = 0;
-                    for (uint32_t j = 1; j <= limit; ++j) {            // residual before candidate j = before + h[0..j)
-                        run += h[j - 1];
-                        if (run > 0.0f) {
-                            pick = j;
-                            before = run;
-                        } else {
-                            break;
-                        }
-                    }
-                    rho |= pick << shift;
-                    if (shift == 0) break;
-                }
             }
             // every key below rho moves to its face, every key above stays; the tie group at rho holds the coordinate
             // that crosses the hyperplane.  One coalesced pass writes everything but the tie group and counts it.
@@ -463,7 +445,7 @@ int advstep_fab_projection_f32(const float *t, const float *w, const float *wsca
                                advstep_stream_t stream) {
     ADVSTEP_REQUIRE(R >= 0 && T >= 0 && w_rows >= 0 && norm_kind >= 0 && norm_kind <= 2);
     if (R == 0) return ADVSTEP_OK;
-    ADVSTEP_REQUIRE(t && w && b && d && d != t && d != w && w_rows >= 1 && T >= 1 && T < (int64_t(1) << 24));
+    ADVSTEP_REQUIRE(t && w && b && d && d != t && d != w && w_rows >= 1 && T >= 1 && T < kMaxRowLength);
     static_assert(ADVSTEP_FAB_LINF == 0 && ADVSTEP_FAB_L2 == 1 && ADVSTEP_FAB_L1 == 2, "the table's row order");
     static constexpr decltype(&fab_projection_linf_kernel<true>) kernels[3][2] = {   // [norm_kind][vec]
         ROW_KERNEL_PAIR(fab_projection_linf_kernel), ROW_KERNEL_PAIR(fab_projection_l2_kernel),

@@ -3,12 +3,11 @@
 // the box (and an optional per-sample cap), and the L1-normalised gradient step fused with it.
 //
 // Layout as apgdl1.hip (row_workgroup.h): one workgroup of 1024 threads per row, the row re-read from L2 by every pass, float4
-// loads where the rows allow, fixed-order reductions.  No sort and no atomics: the k-th largest score is found by walking the 31
-// bits of a non-negative float's pattern kDigit bits at a time, one streaming pass per digit that counts the scores at or above
-// each of 2^kDigit - 1 candidates, always all 11 passes; where scores tie at the threshold a second search of the same shape
-// walks the bits of the sample index for the cut that keeps exactly k.  A thread only ever re-reads samples it wrote itself (the
-// traversals give every pass the same sample -> thread map), so the passes over the output row need no barrier beyond the
-// reductions'.
+// loads where the rows allow, fixed-order reductions.  No sort and no atomics: the k-th largest score is found by
+// row_workgroup.h's digit_search over the 31 bits of a non-negative float's pattern (11 streaming passes that count the scores
+// between consecutive candidates); where scores tie at the threshold a second digit_search walks the bits of the sample index
+// for the cut that keeps exactly k.  A thread only ever re-reads samples it wrote itself (the traversals give every pass the
+// same sample -> thread map), so the passes over the output row need no barrier beyond the reductions'.
 //
 // Algorithmic bytes per row sample: step 4 (grad) + 12 (cur, grad -> u) + 8 x 11 (x, u) [+ 8 x ceil(bits(T - 1) / 3) for the
 // cut] + 12 (x, u -> out), of which 16 B are first touches and the rest L2 / Infinity-Cache re-reads; projection alone
@@ -23,8 +22,6 @@
 #include "row_workgroup.h"
 
 namespace {
-
-constexpr int kDigit = 3, kCand = (1 << kDigit) - 1;   // candidates per streaming pass
 
 // c_i of include/advstep_l0.h: d clipped to what the box and the cap leave of it
 __device__ __forceinline__ float l0_clip(float d, float xi, float cap) {
@@ -42,74 +39,41 @@ template <bool VEC>
 __device__ __forceinline__ void l0_project_row(const float *xr, const float *ur, float *outr, int64_t T, float kk, float cap,
                                                float *stats, float *lds) {
     // rho = the largest pattern with #{key >= rho} >= kk, which is the kk-th largest key; `above` is that count
-    uint32_t rho = 0;
-    float above = (float)T, eq = 0.0f;
-    for (int top = 31; top > 0; top -= kDigit) {               // bits [shift, top) of the pattern: 11 passes
-        const int shift = top >= kDigit ? top - kDigit : 0;
-        const uint32_t limit = (1u << (top - shift)) - 1u;     // candidates j = 1 .. limit
-        float h[kCand];
-#pragma unroll
-        for (int k = 0; k < kCand; ++k) h[k] = 0.0f;
-        visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float(&xu)[2]) {
-            const uint32_t key = l0_key(xu[0], xu[1], cap);
-            if (key >= rho) {
-                const uint32_t q = (key - rho) >> shift;       // lies at or above every candidate j <= q
-#pragma unroll
-                for (int k = 0; k < kCand; ++k) h[k] += (q == (uint32_t)k) ? 1.0f : 0.0f;
-            }
+    float h[kCand], above = (float)T;
+    const uint32_t rho = digit_search(
+        31, h, lds,
+        [&](uint32_t lo, int shift, float(&hh)[kCand]) {
+            visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float(&xu)[2]) {
+                bucket_add(hh, l0_key(xu[0], xu[1], cap), lo, shift, 1.0f);
+            });
+        },
+        [&](float hj) {                                        // #{key >= candidate j} = above - h[0..j): non-increasing in j
+            const float at = above - hj;
+            if (!(at >= kk)) return false;
+            above = at;
+            return true;
         });
-        row_reduce<kCand>(h, SumOp(), lds);
-        float run = above;
-        uint32_t pick = 0;
-        for (uint32_t j = 1; j <= limit; ++j) {                // #{key >= candidate j} = above - h[0..j): non-increasing in j
-            const float at = run - h[j - 1];
-            if (at >= kk) {
-                pick = j;
-                run = at;
-            } else {
-                break;
-            }
-        }
-        above = run;
-        rho |= pick << shift;
-        if (shift == 0) eq = pick ? h[1] : h[0];               // the last pass has one bit: h[pick] = #{key == rho}
-    }
+    const float eq = (rho & 1u) ? h[1] : h[0];                 // the last pass has one bit: h[pick] = #{key == rho}
     const float gt = above - eq;                               // #{key > rho} < kk <= above
     // the cut: the smallest index with #{i <= cut : key_i == rho} = kk - gt, wanted only where ties exceed what is left of kk.
     // cut = the largest c with #{i < c : key_i == rho} < need, found like rho, over the bits of an index
     int64_t cut = T;
     if (above > kk) {                                          // workgroup-uniform: every thread holds the same counts
         const float need = kk - gt;
-        uint32_t c = 0;
         float below = 0.0f;
-        for (int top = 32 - __clz((int)(T - 1)); top > 0; top -= kDigit) {   // T - 1 >= 1 here (above > kk >= 1)
-            const int shift = top >= kDigit ? top - kDigit : 0;
-            const uint32_t limit = (1u << (top - shift)) - 1u;
-            float h[kCand];
-#pragma unroll
-            for (int k = 0; k < kCand; ++k) h[k] = 0.0f;
-            visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](int64_t i, const float(&xu)[2]) {
-                if (l0_key(xu[0], xu[1], cap) == rho && (uint32_t)i >= c) {
-                    const uint32_t q = ((uint32_t)i - c) >> shift;
-#pragma unroll
-                    for (int k = 0; k < kCand; ++k) h[k] += (q == (uint32_t)k) ? 1.0f : 0.0f;
-                }
+        cut = (int64_t)digit_search(
+            32 - __clz((int)(T - 1)), h, lds,                  // T - 1 >= 1 here (above > kk >= 1)
+            [&](uint32_t c, int shift, float(&hh)[kCand]) {
+                visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](int64_t i, const float(&xu)[2]) {
+                    if (l0_key(xu[0], xu[1], cap) == rho) bucket_add(hh, (uint32_t)i, c, shift, 1.0f);
+                });
+            },
+            [&](float hj) {                                    // #{i < candidate j : tie} = below + h[0..j)
+                const float at = below + hj;
+                if (!(at < need)) return false;
+                below = at;
+                return true;
             });
-            row_reduce<kCand>(h, SumOp(), lds);
-            float run = below;
-            uint32_t pick = 0;
-            for (uint32_t j = 1; j <= limit; ++j) {            // #{i < candidate j : tie} = below + h[0..j)
-                run += h[j - 1];
-                if (run < need) {
-                    pick = j;
-                    below = run;
-                } else {
-                    break;
-                }
-            }
-            c |= pick << shift;
-        }
-        cut = (int64_t)c;
     }
     float last[1] = {-1.0f};                                   // the last kept tie (a thread's indices ascend)
     map_rows<VEC>({xr, ur}, outr, T, [&](int64_t i, float xi, float ui) {
@@ -156,8 +120,6 @@ __global__ __launch_bounds__(kRow) void pgdl0_step_kernel(const float *cur, cons
         l0_project_row<VEC>(x + row * T, orow, orow, T, kk, cap, stats ? stats + 4 * row : nullptr, lds);
     }
 }
-
-constexpr int64_t kMaxRowLength = int64_t(1) << 24;            // per-row counts and indices are carried as exact floats
 
 inline float kept(int64_t k, int64_t T) { return (float)(k < T ? k : T); }
 

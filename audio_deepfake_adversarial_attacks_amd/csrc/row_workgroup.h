@@ -3,8 +3,10 @@
 // One workgroup of kRow = 1024 threads (16 wave64) owns one row of T samples and makes several passes over it; at the repo's
 // T = 64 600 a row is 258 KB: it does not fit LDS, but stays L2 / Infinity-Cache resident between the passes, so only the first
 // pass reads HBM.  This header holds what those kernels share: the 16-wave reduction, the row traversal (whose order is part of
-// every reduced result's bits) and the launch helper.  Include after advstep_common.h (wave_reduce, ROW_KERNEL_PAIR,
-// status_after_launch, kMaxGridY).  The 256-thread (tile, row) geometry of the other attack files is row_tiles.h.
+// every reduced result's bits), the digit-walk search behind every per-row threshold (digit_search, bucket_add: FAB's greedy L1
+// key, l1-APGD's lambda and top-k rank, L0's k-th score and index cut) and the launch helper.  Include after advstep_common.h
+// (wave_reduce, SumOp, ROW_KERNEL_PAIR, status_after_launch, kMaxGridY).  The 256-thread (tile, row) geometry of the other
+// attack files is row_tiles.h.
 
 #ifndef ADVSTEP_ROW_WORKGROUP_H
 #define ADVSTEP_ROW_WORKGROUP_H
@@ -139,6 +141,60 @@ __device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], in
             at(e, s);
         }
     }
+}
+
+// ---- the digit-walk search: a per-row threshold without a sort -----------------------------------------------------------
+//
+// rho = the largest `bits`-bit pattern that a predicate, monotone in the pattern (true up to some pattern, false above it),
+// still accepts; pattern 0 counts as accepted.  The bits are fixed from the top, kDigit at a time (the last digit takes what
+// is left): one streaming pass over the row per digit fills kCand bins, bin j - 1 for the digit's candidate
+// rho | j << shift, row_reduce sums them over the workgroup, and a scan takes the candidates in ascending order up to the
+// first one refused.  31 bits (a non-negative float's pattern) are 11 passes, always all of them.
+//
+//   fill(rho, shift, h)  the caller's streaming pass: per-thread partial sums into the zeroed h.  Where bin j - 1 is to hold
+//                        what the samples with pattern in [candidate j - 1, candidate j) contribute, that is
+//                        bucket_add(h, key, rho, shift, v) per sample, and the scan accumulates.
+//   accept(h[j - 1])     for j = 1 .. 2^(digit's bits) - 1, in order, until the first false; a running sum or count lives in
+//                        the caller's capture and moves on only where the candidate is accepted.
+//
+// Contract.  The predicate is monotone in the candidate.  `bits`, and everything accept reads besides the reduced bins, are
+// workgroup-uniform: every thread then picks the same digits, which also keeps the two barriers that row_reduce issues per
+// pass convergent (lds: kCand * kRowWaves floats, free again on return).  Every pass's fill must give each sample to the same
+// thread in the same order (visit_rows, visit_rows_ahead): a thread may then read back row samples it wrote itself with no
+// further barrier, and the bins' bits do not depend on the pass.  h is left holding the last pass's reduced bins.
+//
+// The scan is one loop that indexes h by its counter on purpose.  Written so that the compiler peels its first iteration
+// (`for j = 1 .. limit` with a separate pick), the sums of bins 1 .. 6 sink out of row_reduce into the scan's later blocks,
+// 96 LDS words stay live across the barrier and every kernel with a search drops from 8 to 4 waves per SIMD
+// (profiles/row_search_refactor_resource_usage.txt).
+
+constexpr int kDigit = 3, kCand = (1 << kDigit) - 1;          // bits and candidates per streaming pass
+constexpr int64_t kMaxRowLength = int64_t(1) << 24;            // per-row counts and indices are carried as exact floats
+
+// v into the bin of the digit that `key` has at `shift` above rho; keys below rho belong to no candidate of this pass
+__device__ __forceinline__ void bucket_add(float (&h)[kCand], uint32_t key, uint32_t rho, int shift, float v) {
+    if (key >= rho) {
+        const uint32_t q = (key - rho) >> shift;              // q > kCand - 1: above every candidate, no bin
+#pragma unroll
+        for (int k = 0; k < kCand; ++k) h[k] += (q == (uint32_t)k) ? v : 0.0f;
+    }
+}
+
+template <class Fill, class Accept>
+__device__ __forceinline__ uint32_t digit_search(int bits, float (&h)[kCand], float *lds, Fill fill, Accept accept) {
+    uint32_t rho = 0;
+    for (int top = bits; top > 0; top -= kDigit) {            // bits [shift, top) of the pattern
+        const int shift = top >= kDigit ? top - kDigit : 0;
+        const uint32_t limit = (1u << (top - shift)) - 1u;    // candidates j = 1 .. limit
+#pragma unroll
+        for (int k = 0; k < kCand; ++k) h[k] = 0.0f;
+        fill(rho, shift, h);
+        row_reduce<kCand>(h, SumOp(), lds);
+        uint32_t pick = 0;
+        while (pick < limit && accept(h[pick])) ++pick;
+        rho |= pick << shift;
+    }
+    return rho;
 }
 
 inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }

@@ -123,6 +123,47 @@ def test_projection_kernel(cuda, B, T):
             assert (got[2].cpu() != x[2]).sum() == k
 
 
+def short_tie_rows(T, layout):
+    """(x, u, ties) for B = 2, x = 0.5.  "all": u = x +- 0.25, every sample ties.  "odd": u = x + 0.25 (row 1: - 0.25) on odd i
+    and x + 0.125 on even i, so only the odd indices tie at the threshold of every k <= T // 2 and the kept ties are not a prefix
+    of the row.  ties: how many samples share the largest score."""
+    x = torch.full((2, T), 0.5)
+    if layout == "all":
+        sign = torch.sign(torch.randn(2, T, generator=torch.Generator().manual_seed(70 + T)))
+        return x, x + 0.25 * sign, T
+    u = x + 0.125
+    u[0, 1::2] = 0.75
+    u[1, 1::2] = 0.25
+    return x, u, T // 2
+
+
+@pytest.mark.parametrize("layout", ["all", "odd"])
+@pytest.mark.parametrize("T", [2, 3, 8, 9, 64, 65])
+def test_projection_short_rows_index_cut(cuda, T, layout):
+    """Rows whose index has 1, 2, 3, 3 + 1, 6 and 6 + 1 bits: the cut search with fewer bits than one digit, exactly one digit,
+    whole digits and a one-bit last digit.  Bit for bit against the table, whose kept set is written out here as well: the
+    lowest-index min(k, ties) samples of the top score, then (k = T) everything."""
+    ops = hip()
+    x, u, ties = short_tie_rows(T, layout)
+    top = torch.arange(T) if layout == "all" else torch.arange(1, T, 2)
+    xd, ud = x.to(cuda), u.to(cuda)
+    for k in sorted({1, ties - 1, T} - {0}):
+        for eps_inf in (INF, 0.05):
+            want = C.l0_box_project(x, u, k, eps_inf)
+            kept = torch.zeros(T, dtype=torch.bool)
+            kept[top[:k]] = True
+            if k == T:
+                kept[:] = True
+            assert ((want != x) == kept).all(), (k, eps_inf)                    # the table keeps the set described above
+            out, canary = with_canary(torch.full((2, T), NAN), cuda)
+            got = ops.l0_box_project(xd, ud, k, eps_inf, out=out)
+            assert (canary == 7.0).all()
+            assert same(got, want), (k, eps_inf, got.cpu(), want)               # bit for bit
+            alias = ud.clone()
+            ops.l0_box_project(xd, alias, k, eps_inf, out=alias)                # out aliasing u
+            assert same(alias, got)
+
+
 @pytest.mark.parametrize("B,T", SHAPES)
 def test_step_kernel(cuda, B, T):
     ops = hip()

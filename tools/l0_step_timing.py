@@ -1,7 +1,8 @@
 """The measurement behind profiles/l0_step_timing.txt (needs a HIP device; run from the repository root): hip_ops.pgdl0_step next
 to the sort-based eager formulation of the same arithmetic, which must agree with it bit for bit.  HIP events, B = 128,
 T = 64 600, k in {64, 1024}, one hot buffer set, alternating rounds, no profiler; then the projection alone and apgdl1_step in
-the same process for the per-pass reading."""
+the same process for the per-pass reading; then l1_box_project and apgdl1_init, and the five search kernels at B = 1024
+(profiles/row_search_refactor_timing.txt)."""
 import math, statistics, sys
 sys.path.insert(0, ".")
 import torch
@@ -82,3 +83,30 @@ for _ in range(5):
 torch.cuda.synchronize()
 rs = [timed(fn, 50) for _ in range(5)]
 print(f"apgdl1_step (same process, for comparison): min {min(rs):.1f} median {statistics.median(rs):.1f} max {max(rs):.1f} us")
+# the other two kernels with row_workgroup.h's digit_search that the lines above do not reach, then every search kernel at
+# B = 1024: four rows per CU, where the kernels' occupancy (one or two resident rows per CU) can show
+for label, fn in (("l1_box_project, u = x + N(0, 1), eps = 20", lambda: ops.l1_box_project(xd, u, 20.0, out=out)),
+                  ("apgdl1_init (Philox), eps = 20", lambda: ops.apgdl1_init(xd, 20.0, seed=1, out=out))):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    rs = [timed(fn, 50) for _ in range(5)]
+    print(f"{label}: min {min(rs):.1f} median {statistics.median(rs):.1f} max {max(rs):.1f} us")
+del u, ut, out, c1
+B8 = 8 * B
+x8, g8 = xd.repeat(8, 1), gd.repeat(8, 1)
+u8 = x8 + torch.randn(B8, T, device=dev)
+out8 = torch.empty_like(x8)
+step8, topk8 = torch.full((B8,), 20.0, device=dev), torch.full((B8,), 0.2, device=dev)
+c8 = ops.apgdl1_init(x8, 20.0, seed=1)
+p8 = ops.l0_box_project(x8, u8, 64)
+for label, fn in ((f"B = {B8}: pgdl0_step, random gradient, k = 64", lambda: ops.pgdl0_step(p8, g8, x8, STEP, 64, out=out8)),
+                  (f"B = {B8}: l0_box_project, u = x + N(0, 1), k = 64", lambda: ops.l0_box_project(x8, u8, 64, out=out8)),
+                  (f"B = {B8}: apgdl1_step", lambda: ops.apgdl1_step(c8, g8, x8, step8, topk8, 20.0, out=out8)),
+                  (f"B = {B8}: l1_box_project, u = x + N(0, 1), eps = 20", lambda: ops.l1_box_project(x8, u8, 20.0, out=out8)),
+                  (f"B = {B8}: apgdl1_init (Philox), eps = 20", lambda: ops.apgdl1_init(x8, 20.0, seed=1, out=out8))):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    rs = [timed(fn, 10) for _ in range(5)]
+    print(f"{label}: min {min(rs):.1f} median {statistics.median(rs):.1f} max {max(rs):.1f} us")
