@@ -17,7 +17,7 @@ ABI_VERSION = 3
 _p, _i64, _f32, _f64, _u64, _sz = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_double,
                                    ctypes.c_uint64, ctypes.c_size_t)
 
-# name -> (restype, argtypes); one entry per symbol declared in include/advstep.h, advstep_lcnn.h, advstep_frontend.h, advstep_fab.h, advstep_dataset.h, advstep_detector.h, advstep_apgd.h, advstep_momentum.h, advstep_multi.h, advstep_perturb.h, advstep_radius.h, advstep_apgdl1.h, advstep_snr.h, advstep_universal.h, advstep_spsa.h, advstep_channel.h and advstep_l0.h
+# name -> (restype, argtypes); one entry per symbol declared in include/advstep.h, advstep_lcnn.h, advstep_frontend.h, advstep_fab.h, advstep_dataset.h, advstep_detector.h, advstep_apgd.h, advstep_momentum.h, advstep_multi.h, advstep_perturb.h, advstep_radius.h, advstep_apgdl1.h, advstep_snr.h, advstep_universal.h, advstep_spsa.h, advstep_channel.h, advstep_l0.h and advstep_hsj.h
 SIGNATURES = {
     "advstep_abi_version": (ctypes.c_int, []),
     "advstep_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -199,6 +199,13 @@ SIGNATURES = {
     # include/advstep_l0.h
     "advstep_l0_box_project_f32": (ctypes.c_int, [_p, _p, _p, _i64, _f32, _i64, _i64, _p]),
     "advstep_pgdl0_step_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _f32, _i64, _f32, _i64, _i64, _p]),
+    # include/advstep_hsj.h
+    "advstep_hsj_search_open_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _f32, _p]),
+    "advstep_hsj_search_next_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _f32, _p]),
+    "advstep_hsj_search_close_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _f32, _f32, _p]),
+    "advstep_hsj_probe_f32": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _u64, _p]),
+    "advstep_hsj_candidates_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _u64, _u64, _p]),
+    "advstep_hsj_take_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
 }
 
 

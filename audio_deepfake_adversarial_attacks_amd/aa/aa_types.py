@@ -149,4 +149,14 @@ class AttackEnum(Enum):
     PGDL0_k1024 = (torchattacks.PGDL0, {"k": 1024, "alpha": 0.15, "steps": 20})
     PGDL0_k1024_cap005 = (torchattacks.PGDL0, {"k": 1024, "alpha": 0.15, "steps": 20, "eps_inf": 0.05})
 
+    # --- additive members: the label-only black-box attack (torchattacks.HopSkipJump: the attacker reads the detector's decision,
+    # neither score nor gradient), at the radii of the PGD triplet above; report_at = those radii, whose robust accuracies the run
+    # reports from the per-utterance radii.  10 iterations of 32 .. 101 probes, 4 candidate steps and 11 boundary searches of 12
+    # rounds are at most 889 queries per utterance, HSJ50_eps003 (PGD40_eps003's radius) 16 089.  These budgets, delta_rel,
+    # delta_min and search_steps are choices of scale: nobody has measured what they achieve against these detectors ---
+    HSJ = (torchattacks.HopSkipJump, {"eps": 0.0005, "report_at": (0.0005, 0.00075, 0.001)})
+    HSJ_eps00075 = (torchattacks.HopSkipJump, {"eps": 0.00075, "report_at": (0.0005, 0.00075, 0.001)})
+    HSJ_eps001 = (torchattacks.HopSkipJump, {"eps": 0.001, "report_at": (0.0005, 0.00075, 0.001)})
+    HSJ50_eps003 = (torchattacks.HopSkipJump, {"eps": 0.003, "steps": 50, "init_evals": 64, "max_evals": 1024})
+
     NO_ATTACK = (None, {})

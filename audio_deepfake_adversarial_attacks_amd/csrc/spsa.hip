@@ -15,28 +15,14 @@
 
 #include "advstep_spsa.h"
 #include "advstep_common.h"
+#include "direction_bits.h"
 #include "row_tiles.h"
 
 namespace {
 
 constexpr int64_t kMaxDirections = ADVSTEP_SPSA_MAX_DIRECTIONS;
 
-// The 128 sign bits of quad q of row b for directions 32 * call .. 32 * call + 31.
-__device__ __forceinline__ Quad direction_bits(int64_t q, int64_t b, uint64_t seed, uint64_t offset, int call) {
-    const uint64_t o = offset + (uint64_t)call;
-    return philox4x32_10((uint32_t)q, (uint32_t)b, (uint32_t)o, (uint32_t)(o >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// Direction j's 4 sign bits of the quad (bit k: sample k).  j is uniform over the workgroup, so the word is chosen by scalar
-// selects, not by an indexed read of the register array.
-__device__ __forceinline__ uint32_t direction_nibble(const Quad &r, int j) {
-    const int w = (j & 31) >> 3;
-    const uint32_t word = w == 0 ? r.v[0] : w == 1 ? r.v[1] : w == 2 ? r.v[2] : r.v[3];
-    return (word >> (4 * (j & 7))) & 15u;
-}
-
-// +-m by sign bit `bit` of `nib`: a set bit is v = -1.
-__device__ __forceinline__ float signed_by(float m, uint32_t nib, int bit) { return ((nib >> bit) & 1u) ? -m : m; }
+// direction_bits / direction_nibble / signed_by: direction_bits.h (hsj.hip draws the same directions)
 
 // ---- a. the probe slots ---------------------------------------------------------------------------------------------------------
 

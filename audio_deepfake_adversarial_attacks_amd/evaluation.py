@@ -14,8 +14,9 @@ log line.  What is different is how the work is placed on the machine:
   * the final aggregate is the only communication: an all-reduce(SUM) of the two counters and one all-gather of
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
     (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
-    all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD — one
-    all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA — one of the per-utterance queries;
+    all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD, HopSkipJump —
+    one all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA, HopSkipJump — one of the
+    per-utterance queries;
     an attack that carries `last_changed` — PGDL0 — one of the per-utterance changed-sample counts;
     `channel=` one all-reduce of its five counters).
     A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE process before the loop, or loaded from a
@@ -462,7 +463,8 @@ def generate_attacks(
     the attack did not move is part of the figure; adds the `perturbation/*` keys of `metrics.perturbation_summary`, a
     second log line and, with `return_scores`, the per-utterance planes under `scores["perturbation"]`; off: the report, the
     launches of a batch and the log are exactly those of a run without the keyword).
-    An attack that carries `last_radius` (torchattacks.MinRadiusPGD: each utterance's minimal radius, on the device) adds the
+    An attack that carries `last_radius` (torchattacks.MinRadiusPGD: each utterance's minimal radius, on the device;
+    torchattacks.HopSkipJump: the radius a label-only attacker reached, which also carries `last_queries`) adds the
     `min_radius/*` keys of `metrics.radius_summary` at the attack's `report_at`, one more log line and, with `return_scores`,
     the per-utterance radii under `scores["min_radius"]` (utterance order, like `y_pred`); any other attack: nothing.
     An attack that carries `last_queries` (torchattacks.SPSA: the model queries each utterance spent, on the device) adds the

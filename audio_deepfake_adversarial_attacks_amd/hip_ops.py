@@ -22,6 +22,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   seg_pgd_step / snr_row_radius      no counterpart: PGD under an SNR or segmental-SNR budget, torchattacks.PGDSNR
   universal_colsum / universal_apply no counterpart: one perturbation for every utterance, torchattacks.UniversalPGD
   spsa_probe / spsa_step             no counterpart: the score-based black-box attack, torchattacks.SPSA
+  hsj_search_* / hsj_probe / hsj_candidates / hsj_take  no counterpart: the label-only black-box attack, torchattacks.HopSkipJump
   channel_apply / _adjoint / _eot_step  no counterpart: the simulated audio channel of torchattacks.Channel / EOTPGD
 """
 from __future__ import annotations
@@ -1199,6 +1200,168 @@ def spsa_step(adv, orig, z, labels, queries, alpha: float, eps: float, seed: int
                                                queries.data_ptr(), out.data_ptr(), B, T, n, alpha, eps, lo, hi, seed, offset,
                                                _stream(adv.device))
     _lib.check(st, "advstep_spsa_step_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# label-only black-box attack (include/advstep_hsj.h): the bisection towards the boundary, the probes of a normal estimate, the
+# candidate steps along its sign and the choice among them
+# ---------------------------------------------------------------------------------------------------------
+
+HSJ_PLANES = ("lo", "hi", "mid", "dist0")       # the rows of a boundary-search state, in the order of include/advstep_hsj.h
+HSJ_MAX_DIRECTIONS = 1024                       # ADVSTEP_HSJ_MAX_DIRECTIONS: probes of one normal estimate
+HSJ_MAX_TRIALS = 8                              # ADVSTEP_HSJ_MAX_TRIALS: candidate slots of one step
+
+
+def _hsj_state(t: torch.Tensor, name: str, B: int, device) -> torch.Tensor:
+    _require(t, name)
+    if t.shape != (len(HSJ_PLANES), B) or t.device != device:
+        raise ValueError(f"{name} must be ({len(HSJ_PLANES)}, {B}) on {device}, got {tuple(t.shape)}@{t.device}")
+    return t
+
+
+def _hsj_rows(cur, orig, B, **per_row):
+    """The per-row operands of the HopSkipJump entry points: name=(tensor, dtype), each (B,) on cur's device."""
+    if orig is not None:
+        _require(orig, "orig")
+        _same_shape(("cur", cur), ("orig", orig))
+    for name, (t, dtype) in per_row.items():
+        _per_row(t, name, B, dtype)
+        if t.device != cur.device:
+            raise ValueError(f"{name} must live on {cur.device}, got {t.device}")
+
+
+def _hsj_logits(z, name: str, B: int, cap: int, device) -> int:
+    _require(z, name)
+    if z.dim() != 2 or z.shape[1] != B or z.device != device:
+        raise ValueError(f"{name} must be (n, {B}) on {device}, got {tuple(z.shape)}@{z.device}")
+    if z.shape[0] > cap:
+        raise ValueError(f"{name}: at most {cap} rows of logits, got {z.shape[0]}")
+    return int(z.shape[0])
+
+
+def hsj_search_open(cur, orig, dist, active, out, state=None, lo: float = 0.0, hi: float = 1.0):
+    """Open a boundary search: per active row lo = 0, hi = dist0 = dist, mid = (lo + hi) / 2, and `out` = point(mid) =
+    clamp(orig + clamp(cur - orig, -mid, mid), lo, hi), the first probe to be judged.  An inactive row (active[b] == 0) is copied
+    and every plane of its state is dist.  Returns the (4, B) state (HSJ_PLANES).  One launch, no host read."""
+    _require(cur, "cur"), _require(out, "out")
+    _same_shape(("cur", cur), ("out", out))
+    B, T = _rows(cur, "cur")
+    _hsj_rows(cur, orig, B, dist=(dist, torch.float32), active=(active, torch.int32))
+    if state is None:
+        state = torch.empty((len(HSJ_PLANES), B), dtype=torch.float32, device=cur.device)
+    _hsj_state(state, "state", B, cur.device)
+    with _Launch("hsj_search_open", cur.device, tensors=(cur, orig, out)):
+        st = _lib.load().advstep_hsj_search_open_f32(cur.data_ptr(), orig.data_ptr(), dist.data_ptr(), active.data_ptr(),
+                                                     state.data_ptr(), out.data_ptr(), B, T, lo, hi, _stream(cur.device))
+    _lib.check(st, "advstep_hsj_search_open_f32")
+    return state
+
+
+def hsj_search_next(cur, orig, z, labels, active, state, out, state_out=None, lo: float = 0.0, hi: float = 1.0):
+    """One round of the bisection after the probe at state[2] was judged (z = its logits): adversarial -> hi = mid, else lo = mid;
+    then mid = (lo + hi) / 2 and `out` = point(mid).  Returns the NEW state, written to `state_out` (another buffer than `state`:
+    the launch only reads `state`).  One launch, no host read."""
+    _require(cur, "cur"), _require(out, "out")
+    _same_shape(("cur", cur), ("out", out))
+    B, T = _rows(cur, "cur")
+    _hsj_rows(cur, orig, B, z=(z, torch.float32), labels=(labels, torch.int64), active=(active, torch.int32))
+    _hsj_state(state, "state", B, cur.device)
+    if state_out is None:
+        state_out = torch.empty_like(state)
+    _hsj_state(state_out, "state_out", B, cur.device)
+    with _Launch("hsj_search_next", cur.device, tensors=(cur, orig, out)):
+        st = _lib.load().advstep_hsj_search_next_f32(cur.data_ptr(), orig.data_ptr(), z.data_ptr(), labels.data_ptr(),
+                                                     active.data_ptr(), state.data_ptr(), state_out.data_ptr(), out.data_ptr(),
+                                                     B, T, lo, hi, _stream(cur.device))
+    _lib.check(st, "advstep_hsj_search_next_f32")
+    return state_out
+
+
+def hsj_search_close(cur, orig, z, labels, active, state, queries, rounds: int, out=None, lo: float = 0.0, hi: float = 1.0):
+    """Close a boundary search after its last probe was judged: the same decision as a round, then a row with hi < dist0 becomes
+    point(hi) — the bytes of the probe that was judged adversarial — and any other row keeps cur's bytes.  `queries` (B, int32)
+    gains `rounds` for every active row.  `out` may be `cur`.  One launch, no host read."""
+    _require(cur, "cur")
+    B, T = _rows(cur, "cur")
+    _hsj_rows(cur, orig, B, z=(z, torch.float32), labels=(labels, torch.int64), active=(active, torch.int32),
+              queries=(queries, torch.int32))
+    _hsj_state(state, "state", B, cur.device)
+    if int(rounds) < 0:
+        raise ValueError(f"rounds must be >= 0, got {rounds}")
+    out = _out_like(cur, out)
+    with _Launch("hsj_search_close", cur.device, tensors=(cur, orig, out)):
+        st = _lib.load().advstep_hsj_search_close_f32(cur.data_ptr(), orig.data_ptr(), z.data_ptr(), labels.data_ptr(),
+                                                      active.data_ptr(), state.data_ptr(), queries.data_ptr(), int(rounds),
+                                                      out.data_ptr(), B, T, lo, hi, _stream(cur.device))
+    _lib.check(st, "advstep_hsj_search_close_f32")
+    return out
+
+
+def hsj_probe(cur, mag, active, seed: int, offset: int = 0, s0: int = 0, ns: int = 1, lo: float = 0.0, hi: float = 1.0, out=None):
+    """(ns, *cur.shape) float32: probes s0 .. s0 + ns - 1 of a normal estimate at `cur` (B, T) — slot j is
+    clamp(cur + mag[b] v_j, lo, hi), v_j the Rademacher direction j of `spsa_probe` (the same Philox mapping); there is no copy of
+    cur among the slots.  An inactive row is cur's bytes in every slot.  One launch, 4 B read and 4 * ns B written per sample."""
+    _require(cur, "cur")
+    B, T = _rows(cur, "cur")
+    _hsj_rows(cur, None, B, mag=(mag, torch.float32), active=(active, torch.int32))
+    s0, ns = int(s0), int(ns)
+    if s0 < 0 or ns < 0 or s0 + ns > HSJ_MAX_DIRECTIONS:
+        raise ValueError(f"slots {s0} .. {s0 + ns - 1} are outside 0 .. {HSJ_MAX_DIRECTIONS - 1}")
+    if out is None:
+        out = torch.empty((ns,) + tuple(cur.shape), dtype=torch.float32, device=cur.device)
+    _require(out, "out")
+    if out.numel() != ns * B * T or out.device != cur.device:
+        raise ValueError(f"out must hold ({ns}, {B}, {T}) values on {cur.device}, got {tuple(out.shape)}@{out.device}")
+    with _Launch("hsj_probe", cur.device, tensors=(cur, out)):
+        st = _lib.load().advstep_hsj_probe_f32(cur.data_ptr(), mag.data_ptr(), active.data_ptr(), out.data_ptr(), B, T, s0, ns,
+                                               lo, hi, seed, offset, _stream(cur.device))
+    _lib.check(st, "advstep_hsj_probe_f32")
+    return out
+
+
+def hsj_candidates(cur, z, labels, dist, active, xi_rel: float, trials: int, seed: int, offset: int = 0, lo: float = 0.0,
+                   hi: float = 1.0, out=None):
+    """(trials, *cur.shape) float32: the candidate steps from the logits `z` (n, B) of the n probes `hsj_probe` filled with the
+    same (seed, offset).  s = the sign of the integer form of HopSkipJump's estimate (include/advstep_hsj.h), xi = dist * xi_rel,
+    slot k = clamp(cur + (xi * 2^-k) s, lo, hi).  The estimate is never stored: one launch, no host read."""
+    _require(cur, "cur")
+    B, T = _rows(cur, "cur")
+    _hsj_rows(cur, None, B, labels=(labels, torch.int64), dist=(dist, torch.float32), active=(active, torch.int32))
+    n = _hsj_logits(z, "z", B, HSJ_MAX_DIRECTIONS, cur.device)
+    trials = int(trials)
+    if not 0 <= trials <= HSJ_MAX_TRIALS:
+        raise ValueError(f"trials must be in 0 .. {HSJ_MAX_TRIALS}, got {trials}")
+    if out is None:
+        out = torch.empty((trials,) + tuple(cur.shape), dtype=torch.float32, device=cur.device)
+    _require(out, "out")
+    if out.numel() != trials * B * T or out.device != cur.device:
+        raise ValueError(f"out must hold ({trials}, {B}, {T}) values on {cur.device}, got {tuple(out.shape)}@{out.device}")
+    with _Launch("hsj_candidates", cur.device, tensors=(cur, out, z)):
+        st = _lib.load().advstep_hsj_candidates_f32(cur.data_ptr(), z.data_ptr(), labels.data_ptr(), dist.data_ptr(),
+                                                    active.data_ptr(), out.data_ptr(), B, T, n, trials, xi_rel, lo, hi, seed,
+                                                    offset, _stream(cur.device))
+    _lib.check(st, "advstep_hsj_candidates_f32")
+    return out
+
+
+def hsj_take(cur, cand, zc, labels, active, queries, n: int, out=None):
+    """The step: per active row the first slot of `cand` (trials, B, T) whose logit in `zc` (trials, B) is adversarial becomes the
+    row, and `queries` gains n + k + 1 (what an attacker who tries the slots in turn spends); if none is, the row stays and
+    `queries` gains n + trials.  `out` may be `cur`: only the rows that move are then written.  One launch, no host read."""
+    _require(cur, "cur"), _require(cand, "cand")
+    B, T = _rows(cur, "cur")
+    _hsj_rows(cur, None, B, labels=(labels, torch.int64), active=(active, torch.int32), queries=(queries, torch.int32))
+    trials = _hsj_logits(zc, "zc", B, HSJ_MAX_TRIALS, cur.device)
+    if cand.numel() != trials * B * T or cand.device != cur.device:
+        raise ValueError(f"cand must hold ({trials}, {B}, {T}) values on {cur.device}, got {tuple(cand.shape)}@{cand.device}")
+    if not 0 <= int(n) <= HSJ_MAX_DIRECTIONS:
+        raise ValueError(f"n must be in 0 .. {HSJ_MAX_DIRECTIONS}, got {n}")
+    out = _out_like(cur, out)
+    with _Launch("hsj_take", cur.device, tensors=(cur, out)):
+        st = _lib.load().advstep_hsj_take_f32(cur.data_ptr(), cand.data_ptr(), zc.data_ptr(), labels.data_ptr(), active.data_ptr(),
+                                              queries.data_ptr(), out.data_ptr(), B, T, int(n), trials, _stream(cur.device))
+    _lib.check(st, "advstep_hsj_take_f32")
     return out
 
 

@@ -6,7 +6,8 @@ transfer between detectors (MI-FGSM, NI-FGSM and their variance-tuned forms), Mu
 of them), MinRadiusPGD (each utterance's minimal radius, by bisection on the device), PGDSNR (PGD under a budget in dB of
 SNR or segmental SNR), UniversalPGD (one perturbation fitted once and added to every utterance) and SPSA (the score-based
 black-box counterpart of PGD: queries instead of gradients) and EOTPGD (PGD on a gradient summed over passes, here over draws of a
-simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat model: at most k samples of an utterance change), with the reference's constructor
+simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat model: at most k samples of an utterance change) and HopSkipJump (the label-only
+black-box attack: decisions instead of scores), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -15,6 +16,7 @@ from .attacks.cw import CW
 from .attacks.eotpgd import EOTPGD
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
+from .attacks.hopskipjump import HopSkipJump
 from .attacks.mifgsm import MIFGSM
 from .attacks.minradius import MinRadiusPGD
 from .attacks.multiattack import MultiAttack
@@ -32,4 +34,4 @@ from .channel import CHANNELS, Channel
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
-           "PGDL0"]
+           "PGDL0", "HopSkipJump"]
