@@ -159,4 +159,13 @@ class AttackEnum(Enum):
     HSJ_eps001 = (torchattacks.HopSkipJump, {"eps": 0.001, "report_at": (0.0005, 0.00075, 0.001)})
     HSJ50_eps003 = (torchattacks.HopSkipJump, {"eps": 0.003, "steps": 50, "init_evals": 64, "max_evals": 1024})
 
+    # --- additive members: PGD pulled under the psychoacoustic masking threshold of the clean utterance (torchattacks.PsyPGD: `steps`
+    # of PGD inside the L-inf ball, then `mask_steps` that trade the classifier's gradient against the masking hinge's), at the
+    # radii of PGD_eps001 and PGD40_eps003; alpha = eps / 10 (eps / 16 at 40 steps).  The budgets, alpha and mask_weight = 1 are
+    # choices of scale: nobody has measured what they achieve against these detectors, or against listeners ---
+    PSYPGD = (torchattacks.PsyPGD, {"eps": 0.001, "alpha": 0.001 / 10, "steps": 10, "mask_steps": 20, "mask_weight": 1.0})
+    PSYPGD_eps003 = (torchattacks.PsyPGD, {"eps": 0.003, "alpha": 0.003 / 10, "steps": 10, "mask_steps": 20, "mask_weight": 1.0})
+    PSYPGD40_eps003 = (torchattacks.PsyPGD, {"eps": 0.003, "alpha": 2.5 * 0.003 / 40, "steps": 40, "mask_steps": 40,
+                                             "mask_weight": 1.0})    # budget unmeasured, as above
+
     NO_ATTACK = (None, {})

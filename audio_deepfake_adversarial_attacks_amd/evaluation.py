@@ -18,6 +18,7 @@ log line.  What is different is how the work is placed on the machine:
     one all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA, HopSkipJump — one of the
     per-utterance queries;
     an attack that carries `last_changed` — PGDL0 — one of the per-utterance changed-sample counts;
+    an attack that carries `last_masking` — PsyPGD — or `masking_stats=True` one of the per-utterance (3,) masking statistics;
     `channel=` one all-reduce of its five counters).
     A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE process before the loop, or loaded from a
     file by every rank: no communication either way.
@@ -170,6 +171,26 @@ def format_sparse(report: Dict[str, float]) -> str:
     """The log line of a run whose attack carries `last_changed` (torchattacks.PGDL0): the summary of metrics.sparsity_summary."""
     return ", ".join(f"{k}: {v}" if k.endswith(("_max", "/k")) else f"{k}: {v:.4g}" for k, v in report.items()
                      if k.startswith("sparse/"))
+
+
+def format_masking(report: Dict[str, float]) -> str:
+    """The log line of a run with masking statistics (torchattacks.PsyPGD's `last_masking`, or `masking_stats=True`): the
+    summary of metrics.masking_summary."""
+    return ", ".join(f"{k}: {v:.4g}" for k, v in report.items() if k.startswith("masking/"))
+
+
+def masking_pass(masking, batch_x: torch.Tensor, batch_x_attacked: torch.Tensor) -> torch.Tensor:
+    """(B, 3) masking statistics of what the attack did to a batch, any attack's or none's: both waveforms are mapped to the
+    attack's domain with the CLEAN utterance's minimum and maximum (the same arithmetic for both, so untouched samples give an
+    exact 0), then `masking.threshold` of the clean one and one `hip_ops.masking_hinge_grad` launch.  No host read."""
+    from . import hip_ops
+    B = batch_x.shape[0]
+    x, adv = batch_x.reshape(B, -1), batch_x_attacked.reshape(B, -1)
+    mn, mx = x.amin(dim=1, keepdim=True), x.amax(dim=1, keepdim=True)
+    span = (mx - mn).clamp_min(torch.finfo(torch.float32).tiny)
+    x01, adv01 = ((x - mn) / span).contiguous(), ((adv - mn) / span).contiguous()
+    theta, scale = masking.threshold(x01, hip_ops)
+    return hip_ops.masking_hinge_grad(adv01, x01, masking.window(x.device), theta, scale, masking.hop)[1]
 
 
 def format_channel(report: Dict[str, float]) -> str:
@@ -446,6 +467,7 @@ def generate_attacks(
     universal_save: Optional[Union[str, os.PathLike]] = None,
     channel: Optional[Any] = None,
     channel_draws: int = 1,
+    masking_stats: bool = False,
 ) -> Dict[str, float]:
     """Reference signature (:146-157) plus additive keywords: `dataset` (a ready Dataset yielding the reference's
     4-tuple; without it the `DetectionDataset` over `datasets_paths` is built as in the reference's `get_dataset`,
@@ -487,6 +509,12 @@ def generate_attacks(
     pairs still misclassified among the utterances the attack flipped without the channel; 0 when it flipped none:
     `channel/flipped` says how many), one log line and, over several ranks, one all-reduce of five counters.  `adv_eval/*` and
     every other key are computed exactly as without it, from the unchannelled waveform.
+    An attack that carries `last_masking` (torchattacks.PsyPGD: the (B, 3) masking statistics of the rows it returned, on the
+    device) adds the `masking/*` keys of `metrics.masking_summary`, one more log line and, with `return_scores`, the
+    per-utterance rows under `scores["masking"]`.  `masking_stats` does the same for ANY attack, or none: after the attack,
+    `masking_pass` rates the batch against the clean utterance's masking threshold (`torchattacks.MaskingModel`, hop 128 or
+    the attack's own) in the attack's domain, one threshold and one launch per batch; it replaces the attack's own figures
+    where both exist.
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -547,10 +575,15 @@ def generate_attacks(
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
     seen_total = 0
-    y_pred, y_pred_label, y, perturbation, radii, queries, changed = [], [], [], [], [], [], []
+    y_pred, y_pred_label, y, perturbation, radii, queries, changed, masked = [], [], [], [], [], [], [], []
     has_radius = atk is not None and hasattr(atk, "last_radius")
     has_queries = atk is not None and hasattr(atk, "last_queries")
     has_changed = atk is not None and hasattr(atk, "last_changed")
+    has_masking = masking_stats or (atk is not None and hasattr(atk, "last_masking"))
+    if has_masking:
+        from .torchattacks import MaskingModel
+        masking = getattr(atk, "masking", None) or MaskingModel()
+        masking_cells = None
     if perturbation_stats:
         from . import hip_ops
     through = _ChannelScorer(channel, channel_draws, device, seed + rank) if channel is not None else None
@@ -571,12 +604,20 @@ def generate_attacks(
             if has_changed:
                 changed.append(atk.last_changed)                   # (B,) int64, on this lane's stream; read after join()
                 lanes.keep(changed[-1])
+            if has_masking and not masking_stats:
+                masked.append(atk.last_masking)                    # (B, 3), on this lane's stream; read after join()
+                lanes.keep(masked[-1])
         else:
             batch_x_attacked = torch.clone(batch_x)
         batch_x_noproc, batch_x_attacked_noproc = batch_x, batch_x_attacked  # :223-224 (nothing below writes in place)
         if perturbation_stats:
             perturbation.append(hip_ops.perturbation_stats(batch_x, batch_x_attacked))       # (6, B), on this lane's stream
             lanes.keep(perturbation[-1])
+        if has_masking:
+            masking_cells = masking.frames(batch_x[0].numel()) * 257
+            if masking_stats:
+                masked.append(masking_pass(masking, batch_x, batch_x_attacked))                  # (B, 3), on this lane's stream
+                lanes.keep(masked[-1])
 
         if raw_sample_from_dataset:  # :229-234 — the dataset's default preprocessing, after the attack
             batch_x_attacked, _ = SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(
@@ -635,6 +676,9 @@ def generate_attacks(
     if has_changed:
         all_changed = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(changed).reshape(-1, 1))[:, 0], dtype=np.int64)
 
+    if has_masking:
+        all_masked = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(masked).reshape(-1, 3)), dtype=np.float32)
+
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
@@ -656,6 +700,10 @@ def generate_attacks(
         report.update(metrics.sparsity_summary(all_changed, atk.k))
         if return_scores:
             report["scores"]["changed"] = all_changed
+    if has_masking:
+        report.update(metrics.masking_summary(all_masked, masking_cells))
+        if return_scores:
+            report["scores"]["masking"] = all_masked
     if universal is not None:
         delta = universal.delta.detach().cpu().numpy()
         # rank order = utterance order for the one process that fits; a loaded perturbation was fitted on none of them
@@ -679,6 +727,8 @@ def generate_attacks(
             LOGGER.info(format_blackbox(report))
         if has_changed:
             LOGGER.info(format_sparse(report))
+        if has_masking:
+            LOGGER.info(format_masking(report))
         if universal is not None:
             LOGGER.info(format_universal(report))
         if through is not None:

@@ -24,6 +24,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   spsa_probe / spsa_step             no counterpart: the score-based black-box attack, torchattacks.SPSA
   hsj_search_* / hsj_probe / hsj_candidates / hsj_take  no counterpart: the label-only black-box attack, torchattacks.HopSkipJump
   channel_apply / _adjoint / _eot_step  no counterpart: the simulated audio channel of torchattacks.Channel / EOTPGD
+  stft_power / masking_hinge_grad / psy_step  no counterpart: the psychoacoustic masking hinge of torchattacks.PsyPGD
 """
 from __future__ import annotations
 
@@ -1460,4 +1461,95 @@ def channel_eot_step(adv, orig, grads, taps, shift, gain, alpha: float, eps: flo
                                                       shift.data_ptr(), gain.data_ptr(), out.data_ptr(), B, T, K, L, alpha, eps,
                                                       lo, hi, _stream(adv.device))
     _lib.check(st, "advstep_channel_eot_step_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# psychoacoustic masking (include/advstep_masking.h): the short-time power spectrum, the fused hinge with its gradient and the
+# mixed step of torchattacks.PsyPGD; the threshold itself is torchattacks/masking.py's
+# ---------------------------------------------------------------------------------------------------------
+
+MASKING_NFFT, MASKING_BINS = 512, 257
+
+
+def _masking_frames(t: torch.Tensor, window: torch.Tensor, hop: int) -> Tuple[int, int, int]:
+    B, T = _rows(t, "a")
+    _require(window, "window")
+    if window.numel() != MASKING_NFFT or window.device != t.device:
+        raise ValueError(f"window must hold {MASKING_NFFT} floats on {t.device}, got {tuple(window.shape)}@{window.device}")
+    hop = int(hop)
+    if not _lib.load().advstep_stft_bands_supported(MASKING_NFFT, hop, T):
+        raise ValueError(f"unsupported framing: n_fft {MASKING_NFFT}, hop {hop}, T {T} (128 <= hop <= 512 and T > 257)")
+    return B, T, 1 + T // hop
+
+
+def stft_power(a, b, window, hop: int, out=None):
+    """(B, NF, 257) float32: |STFT|^2 of `a - b` (of `a` when `b` is None) in the frontend's framing — n_fft 512, `window` (512),
+    centre framing with reflect padding, NF = 1 + T // hop.  One launch; the difference is formed in registers."""
+    _require(a, "a")
+    if b is not None:
+        _require(b, "b")
+        _same_shape(("a", a), ("b", b))
+    B, T, NF = _masking_frames(a, window, hop)
+    if out is None:
+        out = torch.empty((B, NF, MASKING_BINS), dtype=torch.float32, device=a.device)
+    else:
+        _require(out, "out")
+        if tuple(out.shape) != (B, NF, MASKING_BINS) or out.device != a.device:
+            raise ValueError(f"out must be {(B, NF, MASKING_BINS)} on {a.device}, got {tuple(out.shape)}@{out.device}")
+    with _Launch("stft_power", a.device, tensors=(a, out) if b is None else (a, b, out)):
+        st = _lib.load().advstep_stft_power_f32(a.data_ptr(), None if b is None else b.data_ptr(), window.data_ptr(),
+                                                out.data_ptr(), B, T, NF, int(hop), MASKING_NFFT, _stream(a.device))
+    _lib.check(st, "advstep_stft_power_f32")
+    return out
+
+
+def masking_hinge_grad(adv, x, window, theta, row_scale, hop: int, out=None, stats=None):
+    """The masking hinge of `adv - x` against `theta` (B, NF, 257) with the row scales `row_scale` (B): returns (grad, stats) —
+    grad (B, T) = d loss_b / d adv, stats (B, 3) = (loss_b = s_b sum max(P - theta, 0), #{P > theta}, max P / theta).  A zero fill
+    and ONE launch: forward and backward share the spectrum in registers.  `out` / `stats`: buffers to write into."""
+    _require(adv, "adv"), _require(x, "x"), _require(theta, "theta")
+    _same_shape(("adv", adv), ("x", x))
+    B, T, NF = _masking_frames(adv, window, hop)
+    if tuple(theta.shape) != (B, NF, MASKING_BINS) or theta.device != adv.device:
+        raise ValueError(f"theta must be {(B, NF, MASKING_BINS)} on {adv.device}, got {tuple(theta.shape)}@{theta.device}")
+    row_scale = _per_row(row_scale, "row_scale", B)
+    if row_scale.device != adv.device:
+        raise ValueError(f"row_scale lives on {row_scale.device}, adv on {adv.device}")
+    out = _out_like(adv, out)
+    if stats is None:
+        stats = torch.empty((B, 3), dtype=torch.float32, device=adv.device)
+    else:
+        _require(stats, "stats")
+        if tuple(stats.shape) != (B, 3) or stats.device != adv.device:
+            raise ValueError(f"stats must be {(B, 3)} on {adv.device}, got {tuple(stats.shape)}@{stats.device}")
+    with _Launch("masking_hinge_grad", adv.device, tensors=(adv, x, theta, out, out)):
+        st = _lib.load().advstep_masking_hinge_grad_f32(adv.data_ptr(), x.data_ptr(), window.data_ptr(), theta.data_ptr(),
+                                                        row_scale.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, NF,
+                                                        int(hop), MASKING_NFFT, _stream(adv.device))
+    _lib.check(st, "advstep_masking_hinge_grad_f32")
+    return out, stats
+
+
+def psy_step(cur, g_ce, g_mask, x, lam: float, step: float, eps: float, out=None):
+    """out = clamp(x + clamp(cur + step * sign(u) - x, -eps, eps), 0, 1) with u = g_ce / mean|g_ce| - lam * g_mask / mean|g_mask|
+    per row (a term whose mean is 0 is dropped).  lam == 0: `pgd_linf_step(cur, g_ce, x, step, eps)` bit for bit, and `g_mask`
+    may be None.  One launch; `out` may be `cur`."""
+    named = [("cur", cur), ("g_ce", g_ce), ("x", x)]
+    if g_mask is not None:
+        named.append(("g_mask", g_mask))
+    elif lam != 0:
+        raise ValueError("g_mask may only be None when lam == 0")
+    for name, t in named:
+        _require(t, name)
+    _same_shape(*named)
+    if not (lam >= 0 and step >= 0 and eps >= 0):
+        raise ValueError(f"lam, step and eps must be non-negative, got {lam!r}, {step!r}, {eps!r}")
+    B, T = _rows(cur, "cur")
+    out = _out_like(cur, out)
+    with _Launch("psy_step", cur.device, tensors=tuple(t for _, t in named) + (out,)):
+        st = _lib.load().advstep_psy_step_f32(cur.data_ptr(), g_ce.data_ptr(), None if g_mask is None else g_mask.data_ptr(),
+                                              x.data_ptr(), float(lam), float(step), float(eps), out.data_ptr(), B, T,
+                                              _stream(cur.device))
+    _lib.check(st, "advstep_psy_step_f32")
     return out

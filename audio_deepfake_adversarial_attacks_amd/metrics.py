@@ -291,3 +291,30 @@ def sparsity_summary(changed, k: int) -> Dict[str, float]:
             "sparse/changed_median": float(np.median(c)) if n else float("nan"),
             "sparse/changed_max": int(np.max(c)) if n else 0,
             "sparse/k": int(k)}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# psychoacoustic masking report
+# ---------------------------------------------------------------------------------------------------------
+
+def masking_summary(stats, cells: int) -> Dict[str, float]:
+    """Run-level digest of the masking statistics per utterance (torchattacks.PsyPGD's `last_masking`, or the one pass of
+    `generate_attacks(..., masking_stats=True)`): `stats` (N, 3) = (hinge loss, time-frequency cells whose perturbation power
+    exceeds the clean utterance's masking threshold, the largest ratio of power to threshold); `cells` = NF * 257, the cells of
+    an utterance.
+
+    masking/over_share_mean, over_share_median   cells over the threshold / cells, over all utterances
+    masking/worst_db_median, worst_db_p90        10 log10 of the largest ratio (-inf where the perturbation is 0)
+    masking/loss_mean                            the mean hinge loss
+    An empty array gives NaN everywhere."""
+    s = np.asarray(stats, dtype=np.float64).reshape(-1, 3)
+    if not s.shape[0]:
+        nan = float("nan")
+        return {"masking/over_share_mean": nan, "masking/over_share_median": nan, "masking/worst_db_median": nan,
+                "masking/worst_db_p90": nan, "masking/loss_mean": nan}
+    share = s[:, 1] / float(cells)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        db = 10.0 * np.log10(s[:, 2])
+    return {"masking/over_share_mean": float(np.mean(share)), "masking/over_share_median": float(np.median(share)),
+            "masking/worst_db_median": float(np.median(db)), "masking/worst_db_p90": float(np.percentile(db, 90)),
+            "masking/loss_mean": float(np.mean(s[:, 0]))}

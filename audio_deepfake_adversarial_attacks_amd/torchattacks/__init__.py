@@ -7,7 +7,8 @@ of them), MinRadiusPGD (each utterance's minimal radius, by bisection on the dev
 SNR or segmental SNR), UniversalPGD (one perturbation fitted once and added to every utterance) and SPSA (the score-based
 black-box counterpart of PGD: queries instead of gradients) and EOTPGD (PGD on a gradient summed over passes, here over draws of a
 simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat model: at most k samples of an utterance change) and HopSkipJump (the label-only
-black-box attack: decisions instead of scores), with the reference's constructor
+black-box attack: decisions instead of scores) and PsyPGD (PGD pulled under the psychoacoustic masking threshold of the clean
+utterance: `MaskingModel`), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -25,13 +26,15 @@ from .attacks.pgd import PGD
 from .attacks.pgdl0 import PGDL0
 from .attacks.pgdl2 import PGDL2
 from .attacks.pgdsnr import PGDSNR
+from .attacks.psypgd import PsyPGD
 from .attacks.spsa import SPSA
 from .attacks.universal import UniversalPGD
 from .attacks.vmifgsm import VMIFGSM
 from .attacks.vnifgsm import VNIFGSM
 from .channel import CHANNELS, Channel
+from .masking import MaskingModel
 
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
-           "PGDL0", "HopSkipJump"]
+           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel"]

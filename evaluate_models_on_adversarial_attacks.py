@@ -91,6 +91,10 @@ def parse_arguments(argv=None):
                              "with every attack and with NO_ATTACK")
     parser.add_argument("--channel_draws", type=int, default=1, metavar="N",
                         help="draws of the channel per utterance (default 1)")
+    parser.add_argument("--masking_stats", default=False, action="store_true",
+                        help="rate the perturbation against the clean utterance's psychoacoustic masking threshold (the share of "
+                             "time-frequency cells over it, the worst excess in dB, the hinge loss): masking/* keys and one more "
+                             "log line; works with every attack and with NO_ATTACK")
     return parser.parse_args(argv)
 
 
@@ -153,6 +157,7 @@ def main(args):
         universal_save=args.universal_save,
         channel=args.channel,
         channel_draws=args.channel_draws,
+        masking_stats=args.masking_stats,
     )
     if world > 1:
         dist.destroy_process_group()
