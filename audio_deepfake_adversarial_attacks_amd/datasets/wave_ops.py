@@ -13,8 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .. import _lib
-from ..hip_ops import _Launch, _require, _stream
+from ..hip_ops import _call, _require
 
 WAVE_F32, WAVE_PCM16 = 0, 1
 _KINDS = {torch.float32: WAVE_F32, torch.int16: WAVE_PCM16}
@@ -35,15 +34,10 @@ def pad_tile(src: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, cu
         raise ValueError(f"src {tuple(src.shape)}, offsets {tuple(offsets.shape)}, lengths {tuple(lengths.shape)}, "
                          f"cut {cut} do not describe a ragged batch")
     dst = torch.empty(B, cut, device=src.device)
-    lib = _lib.load()
     for lo in range(0, B, _MAX_ROWS):
         n = min(_MAX_ROWS, B - lo)
-        with _Launch("wave_pad_tile", src.device):
-            st = lib.advstep_wave_pad_tile_f32(src.data_ptr(), _KINDS[src.dtype], offsets[lo:].data_ptr(),
-                                               lengths[lo:].data_ptr(),
-                                               None if channels is None else channels[lo:].data_ptr(),
-                                               dst[lo:].data_ptr(), n, cut, _stream(src.device))
-        _lib.check(st, "advstep_wave_pad_tile_f32")
+        _call("advstep_wave_pad_tile_f32", src.device, src, _KINDS[src.dtype], offsets[lo:], lengths[lo:],
+              None if channels is None else channels[lo:], dst[lo:], n, cut, bracket="wave_pad_tile")
     return dst
 
 
@@ -124,10 +118,7 @@ def qual_select(y: torch.Tensor, pred_noattack_label: torch.Tensor,
         raise ValueError("y, pred_noattack_label and pred_label must have one entry per utterance")
     rows = torch.empty(max(B, 1), dtype=torch.int32, device=y.device)
     counts = torch.empty(2, dtype=torch.int32, device=y.device)
-    with _Launch("qual_select", y.device):
-        st = _lib.load().advstep_qual_select(y.data_ptr(), pred_noattack_label.data_ptr(), pred_label.data_ptr(), B,
-                                             rows.data_ptr(), counts.data_ptr(), _stream(y.device))
-    _lib.check(st, "advstep_qual_select")
+    _call("advstep_qual_select", y.device, y, pred_noattack_label, pred_label, B, rows, counts, bracket="qual_select")
     return rows, counts
 
 
@@ -145,11 +136,7 @@ def gather_rows(src: torch.Tensor, rows: torch.Tensor, n: Optional[int] = None,
     dst = torch.empty(n, T, device=src.device) if out is None else _require(out, "out")
     if dst.shape != (n, T) or dst.device != src.device:
         raise ValueError(f"out {tuple(dst.shape)} does not match ({n}, {T})")
-    lib = _lib.load()
     for lo in range(0, n, _MAX_ROWS):
         m = min(_MAX_ROWS, n - lo)
-        with _Launch("wave_gather_rows", src.device):
-            st = lib.advstep_wave_gather_rows_f32(src.data_ptr(), rows[lo:].data_ptr(), dst[lo:].data_ptr(), m, T,
-                                                  _stream(src.device))
-        _lib.check(st, "advstep_wave_gather_rows_f32")
+        _call("advstep_wave_gather_rows_f32", src.device, src, rows[lo:], dst[lo:], m, T, bracket="wave_gather_rows")
     return dst

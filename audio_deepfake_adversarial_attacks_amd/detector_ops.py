@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .hip_ops import _Launch, _require, _stream
+from .hip_ops import _Launch, _call, _require
 
 MODE_AFFINE_LRELU, MODE_RELU_AFFINE, MODE_AFFINE_SELU = 0, 1, 2
 
@@ -45,11 +45,8 @@ class _AffineAct(torch.autograd.Function):
         if scale.numel() != C or shift.numel() != C or (pre is not None and pre.numel() != C):
             raise ValueError("per-channel constants must have one entry per channel")
         y = torch.empty_like(x)
-        with _Launch("affine_act_forward", x.device, tensors=(x, y)):
-            st = _lib.load().advstep_affine_act_forward_f32(x.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                            pre.data_ptr() if pre is not None else None, y.data_ptr(), N, C, P,
-                                                            mode, slope, _stream(x.device))
-        _lib.check(st, "advstep_affine_act_forward_f32")
+        _call("advstep_affine_act_forward_f32", x.device, x, scale, shift, pre, y, N, C, P, mode, slope,
+              bracket="affine_act_forward", tensors=(x, y))
         ctx.save_for_backward(x, scale, shift, *([pre] if pre is not None else []))
         ctx.meta = (N, C, P, mode, slope)
         return y
@@ -60,11 +57,8 @@ class _AffineAct(torch.autograd.Function):
         N, C, P, mode, slope = ctx.meta
         gy = gy.contiguous()
         gx = torch.empty_like(x)
-        with _Launch("affine_act_backward", x.device, tensors=(gy, x, gx)):
-            st = _lib.load().advstep_affine_act_backward_f32(gy.data_ptr(), x.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                             pre[0].data_ptr() if pre else None, gx.data_ptr(), N, C, P, mode,
-                                                             slope, _stream(x.device))
-        _lib.check(st, "advstep_affine_act_backward_f32")
+        _call("advstep_affine_act_backward_f32", x.device, gy, x, scale, shift, pre[0] if pre else None, gx, N, C, P, mode, slope,
+              bracket="affine_act_backward", tensors=(gy, x, gx))
         return gx, None, None, None, None, None
 
 
@@ -95,11 +89,8 @@ def _add_maxpool2_raw(a, b, bias):
     N, C, H, W = a.shape
     y = torch.empty((N, C, H // 2, W // 2), dtype=a.dtype, device=a.device)
     sel = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=a.device)
-    with _Launch("add_maxpool2_forward", a.device, tensors=(a, b, y, sel)):
-        st = _lib.load().advstep_add_maxpool2_forward_f32(a.data_ptr(), b.data_ptr() if b is not None else None,
-                                                          bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                                          sel.data_ptr(), N, C, H, W, _stream(a.device))
-    _lib.check(st, "advstep_add_maxpool2_forward_f32")
+    _call("advstep_add_maxpool2_forward_f32", a.device, a, b, bias, y, sel, N, C, H, W,
+          bracket="add_maxpool2_forward", tensors=(a, b, y, sel))
     return y, sel
 
 
@@ -119,10 +110,8 @@ class _AddMaxPool2(torch.autograd.Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         g = torch.empty((N, C, H, W), dtype=gy.dtype, device=gy.device)
-        with _Launch("maxpool2_backward", gy.device, tensors=(gy, sel, g)):
-            st = _lib.load().advstep_maxpool2_backward_f32(gy.data_ptr(), sel.data_ptr(), g.data_ptr(), N, C, H, W,
-                                                           _stream(gy.device))
-        _lib.check(st, "advstep_maxpool2_backward_f32")
+        _call("advstep_maxpool2_backward_f32", gy.device, gy, sel, g, N, C, H, W,
+              bracket="maxpool2_backward", tensors=(gy, sel, g))
         return g, (g if ctx.two else None), None
 
 
@@ -155,11 +144,7 @@ def res2net_link_forward(h: torch.Tensor, scale, shift, pre, y: torch.Tensor, ot
     o_bs = _plane_view(other, "other") if other is not None else 0
     if z is not None:
         _require(z, "z")
-    st = _lib.load().advstep_res2net_link_forward_f32(h.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                      None if pre is None else pre.data_ptr(), y.data_ptr(), y_bs,
-                                                      None if other is None else other.data_ptr(), o_bs,
-                                                      None if z is None else z.data_ptr(), N, C, P, _stream(h.device))
-    _lib.check(st, "advstep_res2net_link_forward_f32")
+    _call("advstep_res2net_link_forward_f32", h.device, h, scale, shift, pre, y, y_bs, other, o_bs, z, N, C, P)
 
 
 def res2net_link_backward(g1: torch.Tensor, g2: Optional[torch.Tensor], h: torch.Tensor, scale, shift, pre) -> torch.Tensor:
@@ -167,11 +152,8 @@ def res2net_link_backward(g1: torch.Tensor, g2: Optional[torch.Tensor], h: torch
     _require(h, "h")
     N, C, P = h.shape
     gx = torch.empty_like(h)
-    st = _lib.load().advstep_res2net_link_backward_f32(g1.data_ptr(), _plane_view(g1, "g1"), None if g2 is None else g2.data_ptr(),
-                                                       _plane_view(g2, "g2") if g2 is not None else 0, h.data_ptr(),
-                                                       scale.data_ptr(), shift.data_ptr(), None if pre is None else pre.data_ptr(),
-                                                       gx.data_ptr(), N, C, P, _stream(h.device))
-    _lib.check(st, "advstep_res2net_link_backward_f32")
+    _call("advstep_res2net_link_backward_f32", h.device, g1, _plane_view(g1, "g1"), g2, _plane_view(g2, "g2") if g2 is not None else 0,
+          h, scale, shift, pre, gx, N, C, P)
     return gx
 
 
@@ -188,10 +170,8 @@ class _AddMaxPool1d(torch.autograd.Function):
         N, C, L = a.shape
         y = torch.empty((N, C, L // k), dtype=a.dtype, device=a.device)
         sel = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=a.device)
-        with _Launch("add_maxpool1d_forward", a.device, tensors=(a, b, y, sel)):
-            st = _lib.load().advstep_add_maxpool1d_forward_f32(a.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(),
-                                                               sel.data_ptr(), N, C, L, k, _stream(a.device))
-        _lib.check(st, "advstep_add_maxpool1d_forward_f32")
+        _call("advstep_add_maxpool1d_forward_f32", a.device, a, b, y, sel, N, C, L, k,
+              bracket="add_maxpool1d_forward", tensors=(a, b, y, sel))
         ctx.save_for_backward(sel)
         ctx.meta = (N, C, L, k, b is not None)
         return y
@@ -202,10 +182,8 @@ class _AddMaxPool1d(torch.autograd.Function):
         N, C, L, k, two = ctx.meta
         gy = gy.contiguous()
         g = torch.empty((N, C, L), dtype=gy.dtype, device=gy.device)
-        with _Launch("maxpool1d_backward", gy.device, tensors=(gy, sel, g)):
-            st = _lib.load().advstep_maxpool1d_backward_f32(gy.data_ptr(), sel.data_ptr(), g.data_ptr(), N, C, L, k,
-                                                            _stream(gy.device))
-        _lib.check(st, "advstep_maxpool1d_backward_f32")
+        _call("advstep_maxpool1d_backward_f32", gy.device, gy, sel, g, N, C, L, k,
+              bracket="maxpool1d_backward", tensors=(gy, sel, g))
         return g, (g if two else None), None
 
 
@@ -215,11 +193,8 @@ def add_maxpool1d(a: torch.Tensor, b: Optional[torch.Tensor], k: int) -> torch.T
 
 
 def _afms_row(mode: int, a, b, alpha, r0, r1, out, rows: int, C: int, L: int) -> None:
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with _Launch("afms_row", a.device, tensors=(a, b, out) if out.numel() >= a.numel() else (a, b)):
-        st = _lib.load().advstep_afms_row_f32(mode, a.data_ptr(), ptr(b), ptr(alpha), ptr(r0), ptr(r1), out.data_ptr(), rows, C, L,
-                                              _stream(a.device))
-    _lib.check(st, "advstep_afms_row_f32")
+    _call("advstep_afms_row_f32", a.device, mode, a, b, alpha, r0, r1, out, rows, C, L,
+          bracket="afms_row", tensors=(a, b, out) if out.numel() >= a.numel() else (a, b))
 
 
 class _Afms(torch.autograd.Function):
@@ -264,10 +239,8 @@ class _WeightedStats(torch.autograd.Function):
         N, C, L = x.shape
         mu = torch.empty((N, C), dtype=x.dtype, device=x.device)
         m2 = torch.empty_like(mu)
-        with _Launch("weighted_stats_forward", x.device, tensors=(x, w)):
-            st = _lib.load().advstep_weighted_stats_forward_f32(x.data_ptr(), w.data_ptr(), mu.data_ptr(), m2.data_ptr(), N * C, L,
-                                                                _stream(x.device))
-        _lib.check(st, "advstep_weighted_stats_forward_f32")
+        _call("advstep_weighted_stats_forward_f32", x.device, x, w, mu, m2, N * C, L,
+              bracket="weighted_stats_forward", tensors=(x, w))
         ctx.save_for_backward(x, w)
         return mu, m2
 
@@ -276,11 +249,8 @@ class _WeightedStats(torch.autograd.Function):
         x, w = ctx.saved_tensors
         N, C, L = x.shape
         gx, gw = torch.empty_like(x), torch.empty_like(w)
-        with _Launch("weighted_stats_backward", x.device, tensors=(x, w, gx, gw)):
-            st = _lib.load().advstep_weighted_stats_backward_f32(x.data_ptr(), w.data_ptr(), gmu.contiguous().data_ptr(),
-                                                                 gm2.contiguous().data_ptr(), gx.data_ptr(), gw.data_ptr(), N * C, L,
-                                                                 _stream(x.device))
-        _lib.check(st, "advstep_weighted_stats_backward_f32")
+        _call("advstep_weighted_stats_backward_f32", x.device, x, w, gmu.contiguous(), gm2.contiguous(), gx, gw, N * C, L,
+              bracket="weighted_stats_backward", tensors=(x, w, gx, gw))
         return gx, gw
 
 
@@ -295,10 +265,8 @@ class _LogMeanNorm(torch.autograd.Function):
         _require(y, "y")
         L = y.shape[-1]
         x = torch.empty_like(y)
-        with _Launch("log_meannorm_forward", y.device, tensors=(y, x)):
-            st = _lib.load().advstep_log_meannorm_forward_f32(y.data_ptr(), eps, x.data_ptr(), y.numel() // max(L, 1), L,
-                                                              _stream(y.device))
-        _lib.check(st, "advstep_log_meannorm_forward_f32")
+        _call("advstep_log_meannorm_forward_f32", y.device, y, eps, x, y.numel() // max(L, 1), L,
+              bracket="log_meannorm_forward", tensors=(y, x))
         ctx.save_for_backward(y)
         ctx.eps = eps
         return x
@@ -309,10 +277,8 @@ class _LogMeanNorm(torch.autograd.Function):
         L = y.shape[-1]
         gx = gx.contiguous()
         gy = torch.empty_like(y)
-        with _Launch("log_meannorm_backward", y.device, tensors=(gx, y, gy)):
-            st = _lib.load().advstep_log_meannorm_backward_f32(gx.data_ptr(), y.data_ptr(), ctx.eps, gy.data_ptr(),
-                                                               y.numel() // max(L, 1), L, _stream(y.device))
-        _lib.check(st, "advstep_log_meannorm_backward_f32")
+        _call("advstep_log_meannorm_backward_f32", y.device, gx, y, ctx.eps, gy, y.numel() // max(L, 1), L,
+              bracket="log_meannorm_backward", tensors=(gx, y, gy))
         return gy, None
 
 
@@ -334,11 +300,8 @@ class _TailPool1d(torch.autograd.Function):
         N, C, L = h.shape
         y = torch.empty((N, C, L // k), dtype=h.dtype, device=h.device)
         sel = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=h.device)
-        with _Launch("tail_pool1d_forward", h.device, tensors=(h, res, y, sel)):
-            st = _lib.load().advstep_tail_pool1d_forward_f32(h.data_ptr(), res.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                             None if pre is None else pre.data_ptr(), y.data_ptr(), sel.data_ptr(),
-                                                             N, C, L, k, _stream(h.device))
-        _lib.check(st, "advstep_tail_pool1d_forward_f32")
+        _call("advstep_tail_pool1d_forward_f32", h.device, h, res, scale, shift, pre, y, sel, N, C, L, k,
+              bracket="tail_pool1d_forward", tensors=(h, res, y, sel))
         ctx.save_for_backward(h, sel, scale, *([pre] if pre is not None else []))
         ctx.k = k
         return y
@@ -349,11 +312,8 @@ class _TailPool1d(torch.autograd.Function):
         N, C, L = h.shape
         gy = gy.contiguous()
         g_h, g_res = torch.empty_like(h), torch.empty_like(h)
-        with _Launch("tail_pool1d_backward", h.device, tensors=(gy, sel, h, g_h, g_res)):
-            st = _lib.load().advstep_tail_pool1d_backward_f32(gy.data_ptr(), sel.data_ptr(), h.data_ptr(), scale.data_ptr(),
-                                                              pre[0].data_ptr() if pre else None, g_h.data_ptr(), g_res.data_ptr(),
-                                                              N, C, L, ctx.k, _stream(h.device))
-        _lib.check(st, "advstep_tail_pool1d_backward_f32")
+        _call("advstep_tail_pool1d_backward_f32", h.device, gy, sel, h, scale, pre[0] if pre else None, g_h, g_res, N, C, L, ctx.k,
+              bracket="tail_pool1d_backward", tensors=(gy, sel, h, g_h, g_res))
         return g_h, g_res, None, None, None, None
 
 
@@ -382,10 +342,8 @@ class _GateMaxPool2(torch.autograd.Function):
             raise ValueError("gate must hold one value per (sample, channel)")
         y = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
         sel = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=x.device)
-        with _Launch("gate_maxpool2_forward", x.device, tensors=(x, y, sel)):
-            st = _lib.load().advstep_gate_maxpool2_forward_f32(x.data_ptr(), gate.data_ptr(), y.data_ptr(), sel.data_ptr(), N, C,
-                                                               H, W, _stream(x.device))
-        _lib.check(st, "advstep_gate_maxpool2_forward_f32")
+        _call("advstep_gate_maxpool2_forward_f32", x.device, x, gate, y, sel, N, C, H, W,
+              bracket="gate_maxpool2_forward", tensors=(x, y, sel))
         ctx.save_for_backward(sel, x, gate)
         ctx.shape = (N, C, H, W)
         return y
@@ -395,14 +353,11 @@ class _GateMaxPool2(torch.autograd.Function):
         sel, x, gate = ctx.saved_tensors
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
-        lib = _lib.load()
-        blocks = max(lib.advstep_gate_maxpool2_blocks(H, W), 1)
+        blocks = max(_lib.load().advstep_gate_maxpool2_blocks(H, W), 1)
         gx = torch.empty_like(x)
         partial = torch.empty((N * C, blocks), dtype=x.dtype, device=x.device)
-        with _Launch("gate_maxpool2_backward", x.device, tensors=(gy, sel, gx)):
-            st = lib.advstep_gate_maxpool2_backward_f32(gy.data_ptr(), sel.data_ptr(), x.data_ptr(), gate.data_ptr(),
-                                                        gx.data_ptr(), partial.data_ptr(), N, C, H, W, _stream(x.device))
-        _lib.check(st, "advstep_gate_maxpool2_backward_f32")
+        _call("advstep_gate_maxpool2_backward_f32", x.device, gy, sel, x, gate, gx, partial, N, C, H, W,
+              bracket="gate_maxpool2_backward", tensors=(gy, sel, gx))
         return gx, partial.sum(dim=1).view_as(gate)
 
 
@@ -423,13 +378,10 @@ class _AttendPool(torch.autograd.Function):
         N, C, H, W = x.shape
         mean = torch.empty((N, C), dtype=x.dtype, device=x.device)
         _afms_row(0, x, None, None, None, None, mean, N * C, C, H * W)
-        lib = _lib.load()
         if C <= 256 and tuple(weight.shape) == (C, C) and weight.is_contiguous():
             gate = torch.empty((N, C), dtype=x.dtype, device=x.device)
-            with _Launch("attend_gate_fc", x.device, tensors=(mean, weight, gate)):
-                st = lib.advstep_gate_fc_forward_f32(mean.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                     gate.data_ptr(), N, C, _stream(x.device))
-            _lib.check(st, "advstep_gate_fc_forward_f32")
+            _call("advstep_gate_fc_forward_f32", x.device, mean, weight, bias, gate, N, C,
+                  bracket="attend_gate_fc", tensors=(mean, weight, gate))
         else:
             gate = torch.sigmoid(torch.addmm(bias, mean, weight.t()) if bias is not None else mean @ weight.t()).contiguous()
         y = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
@@ -438,10 +390,8 @@ class _AttendPool(torch.autograd.Function):
         # is not kept for backward (ADVSTEP_ATTEND_XW=0: gather them out of x in backward, A/B)
         compact = _attend_xw_enabled()
         xw = torch.empty_like(y) if compact else None
-        with _Launch("attend_pool_forward", x.device, tensors=(x, y, sel, xw)):
-            st = _lib.load().advstep_gate_maxpool2_forward_xw_f32(x.data_ptr(), gate.data_ptr(), y.data_ptr(), sel.data_ptr(),
-                                                                  None if xw is None else xw.data_ptr(), N, C, H, W, _stream(x.device))
-        _lib.check(st, "advstep_gate_maxpool2_forward_xw_f32")
+        _call("advstep_gate_maxpool2_forward_xw_f32", x.device, x, gate, y, sel, xw, N, C, H, W,
+              bracket="attend_pool_forward", tensors=(x, y, sel, xw))
         ctx.compact, ctx.shape = compact, (N, C, H, W)
         ctx.save_for_backward(xw if compact else x, sel, gate, weight)
         return y
@@ -451,34 +401,26 @@ class _AttendPool(torch.autograd.Function):
         kept, sel, gate, weight = ctx.saved_tensors          # kept: the pooling winners xw (compact) or x itself
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
-        dev, lib = gy.device, _lib.load()
+        dev = gy.device
         if ctx.compact:
             blocks = 1
             partial = torch.empty((N * C, 1), dtype=gy.dtype, device=dev)
-            with _Launch("attend_pool_backward", dev, tensors=(gy, kept)):
-                st = lib.advstep_gate_maxpool2_backward_gate_pooled_f32(gy.data_ptr(), kept.data_ptr(), partial.data_ptr(), N, C, H, W,
-                                                                        _stream(dev))
-            _lib.check(st, "advstep_gate_maxpool2_backward_gate_pooled_f32")
+            _call("advstep_gate_maxpool2_backward_gate_pooled_f32", dev, gy, kept, partial, N, C, H, W,
+                  bracket="attend_pool_backward", tensors=(gy, kept))
         else:
-            blocks = max(lib.advstep_gate_maxpool2_blocks(H, W), 1)
+            blocks = max(_lib.load().advstep_gate_maxpool2_blocks(H, W), 1)
             partial = torch.empty((N * C, blocks), dtype=gy.dtype, device=dev)
-            st = lib.advstep_gate_maxpool2_backward_gate_f32(gy.data_ptr(), sel.data_ptr(), kept.data_ptr(), partial.data_ptr(), N, C,
-                                                             H, W, _stream(dev))
-            _lib.check(st, "advstep_gate_maxpool2_backward_gate_f32")
+            _call("advstep_gate_maxpool2_backward_gate_f32", dev, gy, sel, kept, partial, N, C, H, W)
         if C <= 256 and tuple(weight.shape) == (C, C) and weight.is_contiguous():
             g_mean = torch.empty((N, C), dtype=gy.dtype, device=dev)
-            with _Launch("attend_gate_fc", dev, tensors=(partial, gate, weight, g_mean)):
-                st = lib.advstep_gate_fc_backward_f32(partial.data_ptr(), blocks, gate.data_ptr(), weight.data_ptr(), 1.0 / float(H * W),
-                                                      g_mean.data_ptr(), N, C, _stream(dev))
-            _lib.check(st, "advstep_gate_fc_backward_f32")
+            _call("advstep_gate_fc_backward_f32", dev, partial, blocks, gate, weight, 1.0 / float(H * W), g_mean, N, C,
+                  bracket="attend_gate_fc", tensors=(partial, gate, weight, g_mean))
         else:
             ggate = partial.sum(dim=1).view(N, C)
             g_mean = (((ggate * gate * (1.0 - gate)) @ weight) / float(H * W)).contiguous()
         gx = torch.empty((N, C, H, W), dtype=gy.dtype, device=dev)
-        with _Launch("attend_pool_backward", dev, tensors=(gy, sel, gx)):
-            st = lib.advstep_gate_maxpool2_backward_input_f32(gy.data_ptr(), sel.data_ptr(), gate.data_ptr(), g_mean.data_ptr(),
-                                                              gx.data_ptr(), N, C, H, W, _stream(dev))
-        _lib.check(st, "advstep_gate_maxpool2_backward_input_f32")
+        _call("advstep_gate_maxpool2_backward_input_f32", dev, gy, sel, gate, g_mean, gx, N, C, H, W,
+              bracket="attend_pool_backward", tensors=(gy, sel, gx))
         return gx, None, None
 
 
@@ -510,13 +452,9 @@ def resconv_prepare(w3: torch.Tensor, w1: Optional[torch.Tensor] = None, rscale:
     if n == 0:
         raise ValueError(f"unsupported convolution: K1={K1}, K2={K2}, rows={rows}")
     U = torch.empty(n, dtype=torch.float32, device=w3.device)
-    ptr = lambda t: None if t is None else t.contiguous().data_ptr()
-    keep = [t.contiguous() for t in (w3, w1, rscale, kscale) if t is not None]
-    with _Launch("resconv_prepare", w3.device):
-        st = lib.advstep_resconv_prepare_f32(keep[0].data_ptr(), ptr(w1), ptr(rscale), ptr(kscale), U.data_ptr(), rows, K1, K2,
-                                             int(transpose), _stream(w3.device))
-    _lib.check(st, "advstep_resconv_prepare_f32")
-    del keep
+    w3, w1, rscale, kscale = (None if t is None else t.contiguous() for t in (w3, w1, rscale, kscale))
+    _call("advstep_resconv_prepare_f32", w3.device, w3, w1, rscale, kscale, U, rows, K1, K2, int(transpose),
+          bracket="resconv_prepare")
     return U
 
 
@@ -538,12 +476,8 @@ def resconv(x1: torch.Tensor, x2: Optional[torch.Tensor], U: torch.Tensor, rows:
             raise ValueError("x1 and x2 must share batch and spatial dimensions")
     y = torch.empty((N, rows, H, W), dtype=x1.dtype, device=x1.device)
     act = _sign_bytes(N, rows, H, W, x1.device) if with_act else None
-    with _Launch("resconv_forward", x1.device, work=8.0 * N * rows * (K1 + K2) * H * W):
-        st = _lib.load().advstep_resconv_forward_act_f32(x1.data_ptr(), None if x2 is None else x2.data_ptr(), U.data_ptr(),
-                                                         None if shift is None else shift.data_ptr(), float(slope), y.data_ptr(),
-                                                         None if act is None else act.data_ptr(), N, K1, K2, rows, H, W,
-                                                         _stream(x1.device))
-    _lib.check(st, "advstep_resconv_forward_act_f32")
+    _call("advstep_resconv_forward_act_f32", x1.device, x1, x2, U, shift, float(slope), y, act, N, K1, K2, rows, H, W,
+          bracket="resconv_forward", work=8.0 * N * rows * (K1 + K2) * H * W)
     return (y, act) if with_act else y
 
 
@@ -557,11 +491,8 @@ def resconv_pool2(x1: torch.Tensor, x2: Optional[torch.Tensor], U: torch.Tensor,
         _require(x2, "x2")
     y = torch.empty((N, rows, H // 2, W // 2), dtype=x1.dtype, device=x1.device)
     sel = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=x1.device)
-    with _Launch("resconv_pool2_forward", x1.device, work=8.0 * N * rows * (K1 + K2) * H * W):
-        st = _lib.load().advstep_resconv_pool2_forward_f32(x1.data_ptr(), None if x2 is None else x2.data_ptr(), U.data_ptr(),
-                                                           None if bias is None else bias.data_ptr(), y.data_ptr(), sel.data_ptr(),
-                                                           N, K1, K2, rows, H, W, _stream(x1.device))
-    _lib.check(st, "advstep_resconv_pool2_forward_f32")
+    _call("advstep_resconv_pool2_forward_f32", x1.device, x1, x2, U, bias, y, sel, N, K1, K2, rows, H, W,
+          bracket="resconv_pool2_forward", work=8.0 * N * rows * (K1 + K2) * H * W)
     return y, sel
 
 
@@ -576,11 +507,8 @@ def resconv_pool2_few(x1: torch.Tensor, x2: torch.Tensor, U: torch.Tensor, wd: t
         raise ValueError("x2 must be (N, 1-2, H, W) and wd a contiguous (rows, K2)")
     y = torch.empty((N, rows, H // 2, W // 2), dtype=x1.dtype, device=x1.device)
     sel = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=x1.device)
-    with _Launch("resconv_pool2_forward", x1.device, work=8.0 * N * rows * K1 * H * W):
-        st = _lib.load().advstep_resconv_pool2_forward_few_f32(x1.data_ptr(), x2.data_ptr(), U.data_ptr(), wd.data_ptr(),
-                                                               None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                                               sel.data_ptr(), N, K1, K2, rows, H, W, _stream(x1.device))
-    _lib.check(st, "advstep_resconv_pool2_forward_few_f32")
+    _call("advstep_resconv_pool2_forward_few_f32", x1.device, x1, x2, U, wd, bias, y, sel, N, K1, K2, rows, H, W,
+          bracket="resconv_pool2_forward", work=8.0 * N * rows * K1 * H * W)
     return y, sel
 
 
@@ -605,13 +533,9 @@ def resconv_pooled_grad(gy: torch.Tensor, sel: torch.Tensor, U: torch.Tensor, ro
     g = torch.empty((N, rows, H, W), dtype=gy.dtype, device=gy.device)
     with _Launch("resconv_pooled_grad", gy.device, work=8.0 * N * rows * K * H * W):
         if act is not None:
-            st = _lib.load().advstep_resconv_pooled_grad_act_f32(gy.data_ptr(), sel.data_ptr(), U.data_ptr(), act.data_ptr(),
-                                                                 float(slope), g.data_ptr(), N, K, rows, H, W, _stream(gy.device))
+            _call("advstep_resconv_pooled_grad_act_f32", gy.device, gy, sel, U, act, float(slope), g, N, K, rows, H, W)
         else:
-            st = _lib.load().advstep_resconv_pooled_grad_f32(gy.data_ptr(), sel.data_ptr(), U.data_ptr(),
-                                                             None if h is None else h.data_ptr(), float(slope), g.data_ptr(), N, K,
-                                                             rows, H, W, _stream(gy.device))
-    _lib.check(st, "advstep_resconv_pooled_grad_f32")
+            _call("advstep_resconv_pooled_grad_f32", gy.device, gy, sel, U, h, float(slope), g, N, K, rows, H, W)
     return g
 
 
@@ -627,11 +551,8 @@ def conv3x3_fewin(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor
     Cout = w.shape[0]
     y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
     act = _sign_bytes(N, Cout, H, W, x.device) if with_act else None
-    with _Launch("conv3x3_fewin_forward", x.device, work=18.0 * N * Cout * x.shape[1] * H * W, tensors=(x, y, act)):
-        st = _lib.load().advstep_conv3x3_fewin_forward_act_f32(x.data_ptr(), w.data_ptr(), None if shift is None else shift.data_ptr(),
-                                                               float(slope), y.data_ptr(), None if act is None else act.data_ptr(),
-                                                               N, Cin, Cout, H, W, _stream(x.device))
-    _lib.check(st, "advstep_conv3x3_fewin_forward_act_f32")
+    _call("advstep_conv3x3_fewin_forward_act_f32", x.device, x, w, shift, float(slope), y, act, N, Cin, Cout, H, W,
+          bracket="conv3x3_fewin_forward", work=18.0 * N * Cout * x.shape[1] * H * W, tensors=(x, y, act))
     return (y, act) if with_act else y
 
 
@@ -649,11 +570,10 @@ def conv3x3_fewout_grad(g1: torch.Tensor, w3: torch.Tensor, gp: Optional[torch.T
         if gp.numel() == 0:                    # nothing was pooled (H or W < 2): the identity path carries no gradient
             gp = None
     gx = torch.empty((N, rows, H, W), dtype=g1.dtype, device=g1.device)
-    with _Launch("conv3x3_fewout_grad", g1.device, work=18.0 * N * K * rows * H * W, tensors=(g1, gp, gx)):
-        st = _lib.load().advstep_conv3x3_fewout_grad_f32(g1.data_ptr(), w3.data_ptr(), None if gp is None else gp.data_ptr(),
-                                                         None if gp is None else sel.data_ptr(), None if gp is None else wd.data_ptr(),
-                                                         gx.data_ptr(), N, K, rows, H, W, _stream(g1.device))
-    _lib.check(st, "advstep_conv3x3_fewout_grad_f32")
+    if gp is None:
+        sel = wd = None                        # the 1x1 part's three operands go in together or not at all
+    _call("advstep_conv3x3_fewout_grad_f32", g1.device, g1, w3, gp, sel, wd, gx, N, K, rows, H, W,
+          bracket="conv3x3_fewout_grad", work=18.0 * N * K * rows * H * W, tensors=(g1, gp, gx))
     return gx
 
 
@@ -779,7 +699,6 @@ class _ResBlock(torch.autograd.Function):
         x, kept, sel = ctx.saved_tensors                     # kept: h1's sign bytes (compact) or h1 itself
         N, _, H, W = x.shape
         gy = gy.contiguous()
-        lib = _lib.load()
         # d(conv1 out) / bn2 scale = conv2^T(unpool(gy)) * lrelu'(h1): unpooling in the operand load, lrelu' in the epilogue
         if ctx.compact:
             g_pre = resconv_pooled_grad(gy, sel, p.U2T, p.cout, H, W, None, p.slope, act=kept)
@@ -788,9 +707,8 @@ class _ResBlock(torch.autograd.Function):
         if p.fewin:
             return conv3x3_fewout_grad(g_pre, p.w1_scaled, gy, sel, p.wd), None
         g_h2 = torch.empty((N, p.cout, H, W), dtype=gy.dtype, device=gy.device)       # the identity path's gradient
-        with _Launch("maxpool2_backward", gy.device, tensors=(gy, sel, g_h2)):
-            st = lib.advstep_maxpool2_backward_f32(gy.data_ptr(), sel.data_ptr(), g_h2.data_ptr(), N, p.cout, H, W, _stream(gy.device))
-        _lib.check(st, "advstep_maxpool2_backward_f32")
+        _call("advstep_maxpool2_backward_f32", gy.device, gy, sel, g_h2, N, p.cout, H, W,
+              bracket="maxpool2_backward", tensors=(gy, sel, g_h2))
         gx = resconv(g_pre, g_h2 if p.downsample else None, p.U1T, p.cin)
         if not p.downsample:
             gx += g_h2

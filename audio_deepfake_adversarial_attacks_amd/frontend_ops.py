@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, fft_plans
-from .hip_ops import _Launch, _stream
+from .hip_ops import _Launch, _call
 from .lcnn_ops import _IdKeyed
 
 
@@ -88,17 +88,12 @@ def dct_fragments(dct: torch.Tensor) -> Optional[torch.Tensor]:
         # on the shipped path)
         return None
     frag = torch.empty(n, dtype=torch.float32, device=dct.device)
-    _lib.check(lib.advstep_lfcc_project_prepare_f32(dct.data_ptr(), M, K, frag.data_ptr(), _stream(dct.device)),
-               "advstep_lfcc_project_prepare_f32")
+    _call("advstep_lfcc_project_prepare_f32", dct.device, dct, M, K, frag)
     # once per weight version: the table is shared by every stream that calls later, so it must be complete before it is
     # published (a second stream's first call is not ordered behind this launch)
     torch.cuda.current_stream(dct.device).synchronize()
     _FRAGMENTS[dct] = (key, frag)
     return frag
-
-
-def _ptr(t: Optional[torch.Tensor]) -> int:
-    return 0 if t is None else t.data_ptr()
 
 
 def _rearm(ctx, stats: torch.Tensor) -> None:
@@ -153,18 +148,13 @@ class _Lfcc(torch.autograd.Function):
         # bytes on the fused path: waveform in, band rows out + back in, cepstra out
         with _Launch("lfcc_forward", dev, tensors=(x, band_db, band_db, out) if fused else ()):
             if fused:
-                st = lib.advstep_stft_bands_f32(x.data_ptr(), window.data_ptr(), tables.fb_start.data_ptr(),
-                                                tables.fb_w.data_ptr(), tables.span, band_db.data_ptr(), block_max.data_ptr(),
-                                                B, T, NF, hop, nfft, M, _stream(dev))
-                _lib.check(st, "advstep_stft_bands_f32")
+                _call("advstep_stft_bands_f32", dev, x, window, tables.fb_start, tables.fb_w, tables.span, band_db, block_max,
+                      B, T, NF, hop, nfft, M)
             else:
-                st = lib.advstep_lfcc_bands_f32(spec.data_ptr(), tables.fb_start.data_ptr(), tables.fb_w.data_ptr(),
-                                                tables.span, band_db.data_ptr(), block_max.data_ptr(), B, F, M, NF, _stream(dev))
-                _lib.check(st, "advstep_lfcc_bands_f32")
+                _call("advstep_lfcc_bands_f32", dev, spec, tables.fb_start, tables.fb_w, tables.span, band_db, block_max,
+                      B, F, M, NF)
             # batch maximum + floor + DCT: one launch (every workgroup reduces the block maxima itself)
-            st = lib.advstep_lfcc_max_project_f32(band_db.data_ptr(), dct.data_ptr(), _ptr(frag), block_max.data_ptr(), nblk,
-                                                  stats.data_ptr(), top_db, out.data_ptr(), B, M, NF, K, _stream(dev))
-            _lib.check(st, "advstep_lfcc_max_project_f32")
+            _call("advstep_lfcc_max_project_f32", dev, band_db, dct, frag, block_max, nblk, stats, top_db, out, B, M, NF, K)
         ctx.save_for_backward(spec, band_db, dct, tables.fbt_start, tables.fbt_w, window)
         ctx.stats, ctx.frag = stats, frag      # not saved tensors: see _rearm
         ctx.meta = (source, B, T, F, NF, M, K, tables.span_t, float(top_db), hop, nfft)
@@ -180,7 +170,6 @@ class _Lfcc(torch.autograd.Function):
         fused = source == "fused"
         dev = gout.device
         go = gout.transpose(1, 2).contiguous()     # (B, NF, K); a no-op when the consumer is frame-major
-        lib = _lib.load()
         dband = torch.empty((B, NF, M), dtype=torch.float32, device=dev)
         if fused:
             dx = torch.empty((B, T), dtype=torch.float32, device=dev)
@@ -189,26 +178,16 @@ class _Lfcc(torch.autograd.Function):
         _rearm(ctx, stats)
         with _Launch("lfcc_backward", dev, tensors=(go, band_db, dband, dband, spec, dx, dx) if fused else ()):
             # on the fused path this also zero-fills dx, which the overlap-add of the second launch accumulates into
-            st = lib.advstep_lfcc_project_backward_zero_f32(go.data_ptr(), dct.data_ptr(), _ptr(frag), band_db.data_ptr(),
-                                                            stats.data_ptr(), top_db, dband.data_ptr(), B, M, NF, K,
-                                                            dx.data_ptr() if fused else 0, dx.numel() if fused else 0,
-                                                            _stream(dev))
-            _lib.check(st, "advstep_lfcc_project_backward_zero_f32")
+            _call("advstep_lfcc_project_backward_zero_f32", dev, go, dct, frag, band_db, stats, top_db, dband, B, M, NF, K,
+                  dx if fused else None, dx.numel() if fused else 0)
             if fused:
-                st = lib.advstep_stft_bands_backward_fixup_f32(spec.data_ptr(), window.data_ptr(), dband.data_ptr(),
-                                                               band_db.data_ptr(), stats.data_ptr(), fbt_start.data_ptr(),
-                                                               fbt_w.data_ptr(), span_t, dx.data_ptr(), 1, B, T, NF, hop, nfft,
-                                                               M, _stream(dev))
-                _lib.check(st, "advstep_stft_bands_backward_fixup_f32")
+                _call("advstep_stft_bands_backward_fixup_f32", dev, spec, window, dband, band_db, stats, fbt_start, fbt_w, span_t,
+                      dx, 1, B, T, NF, hop, nfft, M)
             else:
-                st = lib.advstep_lfcc_floor_fixup_f32(band_db.data_ptr(), stats.data_ptr(), dband.data_ptr(),
-                                                      band_db.numel(), _stream(dev))
-                _lib.check(st, "advstep_lfcc_floor_fixup_f32")
+                _call("advstep_lfcc_floor_fixup_f32", dev, band_db, stats, dband, band_db.numel())
                 # hermitian_half on the frames path: its c2r inverse takes the pre-scaled half spectrum
-                st = lib.advstep_lfcc_bands_backward_f32(dband.data_ptr(), spec.data_ptr(), fbt_start.data_ptr(),
-                                                         fbt_w.data_ptr(), span_t, dspec.data_ptr(), B, F, M, NF,
-                                                         int(source == "frames"), _stream(dev))
-                _lib.check(st, "advstep_lfcc_bands_backward_f32")
+                _call("advstep_lfcc_bands_backward_f32", dev, dband, spec, fbt_start, fbt_w, span_t, dspec, B, F, M, NF,
+                      int(source == "frames"))
         if source == "tail":
             return None, torch.view_as_complex(dspec).transpose(1, 2), None, None, None, None, None
         if source == "frames":
@@ -223,10 +202,7 @@ def _frames_rfft(x: torch.Tensor, window: torch.Tensor, hop: int, NF: int) -> to
     F = nfft // 2 + 1
     dev = x.device
     frames = torch.empty((B, NF, nfft), dtype=torch.float32, device=dev)
-    with _Launch("stft_frames", dev):
-        st = _lib.load().advstep_stft_frames_f32(x.data_ptr(), window.data_ptr(), frames.data_ptr(), B, T, NF, hop, nfft,
-                                                 _stream(dev))
-    _lib.check(st, "advstep_stft_frames_f32")
+    _call("advstep_stft_frames_f32", dev, x, window, frames, B, T, NF, hop, nfft, bracket="stft_frames")
     sr = torch.empty((B, NF, F, 2), dtype=torch.float32, device=dev)
     if not (enabled("ADVSTEP_DIRECT_FFT") and fft_plans.rfft_into(frames.view(B * NF, nfft), sr.view(B * NF, F, 2))):
         sr = torch.view_as_real(torch.fft.rfft(frames, dim=-1))           # same library, plus a defensive input clone
@@ -243,10 +219,7 @@ def _irfft_overlap_add(dspec: torch.Tensor, window: torch.Tensor, hop: int, T: i
     if not (enabled("ADVSTEP_DIRECT_FFT") and fft_plans.irfft_into(dspec.view(B * NF, F, 2), dframes.view(B * NF, nfft))):
         dframes = torch.fft.irfft(torch.view_as_complex(dspec), n=nfft, dim=-1, norm="forward").contiguous()
     dx = torch.empty((B, T), dtype=torch.float32, device=dev)
-    with _Launch("stft_overlap_add", dev):
-        st = _lib.load().advstep_stft_overlap_add_f32(dframes.data_ptr(), window.data_ptr(), dx.data_ptr(), B, T, NF, hop,
-                                                      nfft, _stream(dev))
-    _lib.check(st, "advstep_stft_overlap_add_f32")
+    _call("advstep_stft_overlap_add_f32", dev, dframes, window, dx, B, T, NF, hop, nfft, bracket="stft_overlap_add")
     return dx
 
 
@@ -296,11 +269,8 @@ class _MelSpecFromWaveform(torch.autograd.Function):
         M = tables.fb_start.numel()
         dev = x.device
         out = torch.empty((B, 2, M, NF), dtype=torch.float32, device=dev)
-        with _Launch("stft_mel", dev, tensors=(x, out)):
-            st = _lib.load().advstep_stft_mel_f32(x.data_ptr(), window.data_ptr(), tables.fb_start.data_ptr(),
-                                                  tables.fb_w.data_ptr(), tables.span, out.data_ptr(), B, T, NF, hop, nfft, M,
-                                                  _stream(dev))
-        _lib.check(st, "advstep_stft_mel_f32")
+        _call("advstep_stft_mel_f32", dev, x, window, tables.fb_start, tables.fb_w, tables.span, out, B, T, NF, hop, nfft, M,
+              bracket="stft_mel", tensors=(x, out))
         ctx.from_output = enabled("ADVSTEP_MEL_BWD_FROM_OUTPUT")
         ctx.save_for_backward(out if ctx.from_output else x, window, tables.fb_start, tables.fb_w, tables.fbt_start, tables.fbt_w)
         ctx.meta = (B, T, NF, M, tables.span, tables.span_t, hop, nfft)
@@ -315,17 +285,11 @@ class _MelSpecFromWaveform(torch.autograd.Function):
         dx = torch.empty((B, T), dtype=torch.float32, device=dev)
         if ctx.from_output:
             # d x from d out and out alone (Y = |Y| e^{i phase} is all the gradient needs): no spectrum is recomputed
-            with _Launch("stft_mel_backward", dev, tensors=(go, x, dx, dx)):
-                st = _lib.load().advstep_stft_mel_backward_from_output_f32(window.data_ptr(), go.data_ptr(), x.data_ptr(),
-                                                                           fbt_start.data_ptr(), fbt_w.data_ptr(), span_t,
-                                                                           dx.data_ptr(), B, T, NF, hop, nfft, M, _stream(dev))
-            _lib.check(st, "advstep_stft_mel_backward_from_output_f32")
+            _call("advstep_stft_mel_backward_from_output_f32", dev, window, go, x, fbt_start, fbt_w, span_t, dx, B, T, NF, hop, nfft,
+                  M, bracket="stft_mel_backward", tensors=(go, x, dx, dx))
             return dx, None, None, None
-        with _Launch("stft_mel_backward", dev, tensors=(go, x, dx, dx)):
-            st = _lib.load().advstep_stft_mel_backward_f32(x.data_ptr(), window.data_ptr(), go.data_ptr(), fb_start.data_ptr(),
-                                                           fb_w.data_ptr(), span, fbt_start.data_ptr(), fbt_w.data_ptr(), span_t,
-                                                           dx.data_ptr(), B, T, NF, hop, nfft, M, _stream(dev))
-        _lib.check(st, "advstep_stft_mel_backward_f32")
+        _call("advstep_stft_mel_backward_f32", dev, x, window, go, fb_start, fb_w, span, fbt_start, fbt_w, span_t, dx, B, T, NF, hop,
+              nfft, M, bracket="stft_mel_backward", tensors=(go, x, dx, dx))
         return dx, None, None, None
 
 

@@ -161,6 +161,44 @@ class _Launch:
         return self.guard.__exit__(*exc)
 
 
+def _call(symbol: str, device: torch.device, *args, bracket: Optional[str] = None, work: float = 0.0, tensors=()) -> None:
+    """The one way into a status-returning entry point of the C ABI: `symbol` (its full name, given once) is called with
+    `args` — a tensor as its address, None as a null pointer, anything else as it is — and torch's current stream of `device`
+    as the last argument; a non-zero status raises under that name.  `bracket`: the call runs inside `_Launch(bracket, device,
+    work, tensors)`; None: no guard and no events (the caller holds a bracket of its own, or the call never had one)."""
+    if bracket is not None:
+        with _Launch(bracket, device, work, tensors):
+            return _call(symbol, device, *args)
+    status = getattr(_lib.load(), symbol)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], _stream(device))
+    _lib.check(status, symbol)
+
+
+def _on_device(t: torch.Tensor, name: str, device: torch.device) -> None:
+    if t.device != device:
+        raise ValueError(f"{name} must live on {device}, got {t.device}")
+
+
+def _stacked_out(out: Optional[torch.Tensor], n: int, like: torch.Tensor) -> torch.Tensor:
+    """`out`, or a fresh (n, *like.shape) tensor: n stacked copies' worth of float32 values on like's device."""
+    if out is None:
+        out = torch.empty((n,) + tuple(like.shape), dtype=torch.float32, device=like.device)
+    _require(out, "out")
+    if out.numel() != n * like.numel() or out.device != like.device:
+        B, T = _rows(like, "input")
+        raise ValueError(f"out must hold ({n}, {B}, {T}) values on {like.device}, got {tuple(out.shape)}@{out.device}")
+    return out
+
+
+def _shaped(t: Optional[torch.Tensor], name: str, shape: tuple, device: torch.device) -> torch.Tensor:
+    """`t`, or a fresh float32 tensor when it is None: exactly `shape`, on `device`."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    _require(t, name)
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{name} must be {tuple(shape)} on {device}, got {tuple(t.shape)}@{t.device}")
+    return t
+
+
 def start_profile(*entry_points: str, graph_ok: bool = False) -> None:
     """Bracket every later launch of the named entry points ("*": of every entry point) with HIP events on their launch
     stream.  graph_ok: the caller prices launches that stay OUTSIDE the attacks' captured graphs (the update steps,
@@ -201,9 +239,7 @@ def to_minmax(batch_x: torch.Tensor):
     mx = torch.empty((B, 1), dtype=torch.float32, device=x.device)
     with _Launch("minmax_normalize", x.device, tensors=(x, x, x01)):
         ws, ws_bytes = _workspace(x.device, B, T)
-        st = _lib.load().advstep_minmax_normalize_f32(x.data_ptr(), x01.data_ptr(), mn.data_ptr(), mx.data_ptr(), B, T,
-                                                      ws, ws_bytes, _stream(x.device))
-    _lib.check(st, "advstep_minmax_normalize_f32")
+        _call("advstep_minmax_normalize_f32", x.device, x, x01, mn, mx, B, T, ws, ws_bytes)
     return x01, mn, mx
 
 
@@ -215,10 +251,7 @@ def revert_minmax(batch_x: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor, out
     if mn.numel() != B or mx.numel() != B:
         raise ValueError(f"mn/mx must hold one value per row ({B}), got {mn.numel()} / {mx.numel()}")
     out = _out_like(x, out)
-    with _Launch("minmax_revert", x.device, tensors=(x, out)):
-        st = _lib.load().advstep_minmax_revert_f32(x.data_ptr(), mn.data_ptr(), mx.data_ptr(), out.data_ptr(), B, T,
-                                                   _stream(x.device))
-    _lib.check(st, "advstep_minmax_revert_f32")
+    _call("advstep_minmax_revert_f32", x.device, x, mn, mx, out, B, T, bracket="minmax_revert", tensors=(x, out))
     return out
 
 
@@ -230,10 +263,7 @@ def fgsm_step(x, grad, eps: float, lo: float = 0.0, hi: float = 1.0, out=None):
     _require(x, "x"), _require(grad, "grad")
     _same_shape(("x", x), ("grad", grad))
     out = _out_like(x, out)
-    with _Launch("fgsm_step", x.device, tensors=(x, grad, out)):
-        st = _lib.load().advstep_fgsm_step_f32(x.data_ptr(), grad.data_ptr(), out.data_ptr(), x.numel(), eps, lo, hi,
-                                               _stream(x.device))
-    _lib.check(st, "advstep_fgsm_step_f32")
+    _call("advstep_fgsm_step_f32", x.device, x, grad, out, x.numel(), eps, lo, hi, bracket="fgsm_step", tensors=(x, grad, out))
     return out
 
 
@@ -245,17 +275,13 @@ def pgd_linf_init(x, eps: float, noise=None, seed: Optional[int] = None, offset:
     if noise is not None:
         _require(noise, "noise")
         _same_shape(("x", x), ("noise", noise))
-        with _Launch("pgd_linf_init", x.device, tensors=(x, noise, out)):
-            st = _lib.load().advstep_pgd_linf_init_noise_f32(x.data_ptr(), noise.data_ptr(), out.data_ptr(), x.numel(),
-                                                             lo, hi, _stream(x.device))
-        _lib.check(st, "advstep_pgd_linf_init_noise_f32")
+        _call("advstep_pgd_linf_init_noise_f32", x.device, x, noise, out, x.numel(), lo, hi,
+              bracket="pgd_linf_init", tensors=(x, noise, out))
     else:
         if seed is None:
             raise ValueError("pgd_linf_init needs either `noise` or a Philox `seed`")
-        with _Launch("pgd_linf_init", x.device, tensors=(x, out)):
-            st = _lib.load().advstep_pgd_linf_init_philox_f32(x.data_ptr(), out.data_ptr(), x.numel(), eps, lo, hi,
-                                                              seed, offset, _stream(x.device))
-        _lib.check(st, "advstep_pgd_linf_init_philox_f32")
+        _call("advstep_pgd_linf_init_philox_f32", x.device, x, out, x.numel(), eps, lo, hi, seed, offset,
+              bracket="pgd_linf_init", tensors=(x, out))
     return out
 
 
@@ -263,10 +289,8 @@ def pgd_linf_step(adv, grad, orig, alpha: float, eps: float, lo: float = 0.0, hi
     _require(adv, "adv"), _require(grad, "grad"), _require(orig, "orig")
     _same_shape(("adv", adv), ("grad", grad), ("orig", orig))
     out = _out_like(adv, out)
-    with _Launch("pgd_linf_step", adv.device, tensors=(adv, grad, orig, out)):
-        st = _lib.load().advstep_pgd_linf_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), out.data_ptr(),
-                                                   adv.numel(), alpha, eps, lo, hi, _stream(adv.device))
-    _lib.check(st, "advstep_pgd_linf_step_f32")
+    _call("advstep_pgd_linf_step_f32", adv.device, adv, grad, orig, out, adv.numel(), alpha, eps, lo, hi,
+          bracket="pgd_linf_step", tensors=(adv, grad, orig, out))
     return out
 
 
@@ -288,16 +312,11 @@ def pgd_l2_init(x, eps: float, draws=None, seed: Optional[int] = None, offset: i
             _same_shape(("x", x), ("normal", normal))
             if r.numel() != B:
                 raise ValueError(f"r must hold one value per row ({B}), got {r.numel()}")
-            st = _lib.load().advstep_pgd_l2_init_noise_f32(x.data_ptr(), normal.data_ptr(), r.data_ptr(), out.data_ptr(),
-                                                           B, T, eps, lo, hi, ws, ws_bytes, _stream(x.device))
-            what = "advstep_pgd_l2_init_noise_f32"
+            _call("advstep_pgd_l2_init_noise_f32", x.device, x, normal, r, out, B, T, eps, lo, hi, ws, ws_bytes)
         else:
             if seed is None:
                 raise ValueError("pgd_l2_init needs either `draws` or a Philox `seed`")
-            st = _lib.load().advstep_pgd_l2_init_philox_f32(x.data_ptr(), out.data_ptr(), B, T, eps, lo, hi, seed,
-                                                            offset, ws, ws_bytes, _stream(x.device))
-            what = "advstep_pgd_l2_init_philox_f32"
-    _lib.check(st, what)
+            _call("advstep_pgd_l2_init_philox_f32", x.device, x, out, B, T, eps, lo, hi, seed, offset, ws, ws_bytes)
     return out
 
 
@@ -313,11 +332,7 @@ def pgd_l2_step(adv, grad, orig, alpha: float, eps: float, eps_div: float = 1e-1
         dn = torch.empty(B, dtype=torch.float32, device=adv.device)
     with _Launch("pgd_l2_step", adv.device, tensors=(adv, grad, orig, out)):
         ws, ws_bytes = _workspace(adv.device, B, T)
-        st = _lib.load().advstep_pgd_l2_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), out.data_ptr(), B, T,
-                                                 alpha, eps, eps_div, lo, hi, gn.data_ptr() if return_norms else None,
-                                                 dn.data_ptr() if return_norms else None, ws, ws_bytes,
-                                                 _stream(adv.device))
-    _lib.check(st, "advstep_pgd_l2_step_f32")
+        _call("advstep_pgd_l2_step_f32", adv.device, adv, grad, orig, out, B, T, alpha, eps, eps_div, lo, hi, gn, dn, ws, ws_bytes)
     return (out, gn, dn) if return_norms else out
 
 
@@ -329,8 +344,7 @@ def pgd_l2_repaired_rows(like: torch.Tensor) -> int:
     count = torch.zeros(1, dtype=torch.int32, device=like.device)
     with torch.cuda.device(like.device):
         ws, ws_bytes = _workspace(like.device, B, T)
-        st = _lib.load().advstep_pgd_l2_repaired_rows(ws, ws_bytes, B, T, count.data_ptr(), _stream(like.device))
-    _lib.check(st, "advstep_pgd_l2_repaired_rows")
+        _call("advstep_pgd_l2_repaired_rows", like.device, ws, ws_bytes, B, T, count)
     return int(count.item())
 
 
@@ -341,9 +355,7 @@ def pgd_l2_repaired_rows(like: torch.Tensor) -> int:
 def cw_init_w(x, out=None):
     _require(x, "x")
     out = _out_like(x, out)
-    with _Launch("cw_init_w", x.device, tensors=(x, out)):
-        st = _lib.load().advstep_cw_init_w_f32(x.data_ptr(), out.data_ptr(), x.numel(), _stream(x.device))
-    _lib.check(st, "advstep_cw_init_w_f32")
+    _call("advstep_cw_init_w_f32", x.device, x, out, x.numel(), bracket="cw_init_w", tensors=(x, out))
     return out
 
 
@@ -356,9 +368,7 @@ def cw_tanh_sqdist(w, x, adv_out=None):
     l2 = torch.empty(B, dtype=torch.float32, device=w.device)
     with _Launch("cw_tanh_sqdist", w.device, tensors=(w, x, adv)):
         ws, ws_bytes = _workspace(w.device, B, T)
-        st = _lib.load().advstep_cw_tanh_sqdist_f32(w.data_ptr(), x.data_ptr(), adv.data_ptr(), l2.data_ptr(), B, T, ws,
-                                                    ws_bytes, _stream(w.device))
-    _lib.check(st, "advstep_cw_tanh_sqdist_f32")
+        _call("advstep_cw_tanh_sqdist_f32", w.device, w, x, adv, l2, B, T, ws, ws_bytes)
     return adv, l2
 
 
@@ -368,11 +378,8 @@ def cw_adam_step(w, m, v, x, grad_adv, step: int, lr: float = 0.01, beta1: float
     for name, t in (("w", w), ("m", m), ("v", v), ("x", x), ("grad_adv", grad_adv)):
         _require(t, name)
     _same_shape(("w", w), ("m", m), ("v", v), ("x", x), ("grad_adv", grad_adv))
-    with _Launch("cw_adam_step", w.device, tensors=(w, w, m, m, v, v, x, grad_adv)):
-        st = _lib.load().advstep_cw_adam_step_f32(w.data_ptr(), m.data_ptr(), v.data_ptr(), x.data_ptr(),
-                                                  grad_adv.data_ptr(), w.numel(), step, lr, beta1, beta2, adam_eps,
-                                                  _stream(w.device))
-    _lib.check(st, "advstep_cw_adam_step_f32")
+    _call("advstep_cw_adam_step_f32", w.device, w, m, v, x, grad_adv, w.numel(), step, lr, beta1, beta2, adam_eps,
+          bracket="cw_adam_step", tensors=(w, w, m, m, v, v, x, grad_adv))
 
 
 def cw_best_update(adv, mask, best) -> None:
@@ -382,10 +389,7 @@ def cw_best_update(adv, mask, best) -> None:
     B, T = _rows(adv, "adv")
     if mask.numel() != B:
         raise ValueError(f"mask must hold one value per row ({B}), got {mask.numel()}")
-    with _Launch("cw_best_update", adv.device, tensors=(adv, best, best)):
-        st = _lib.load().advstep_cw_best_update_f32(adv.data_ptr(), mask.data_ptr(), best.data_ptr(), B, T,
-                                                    _stream(adv.device))
-    _lib.check(st, "advstep_cw_best_update_f32")
+    _call("advstep_cw_best_update_f32", adv.device, adv, mask, best, B, T, bracket="cw_best_update", tensors=(adv, best, best))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -401,10 +405,7 @@ def ce2_loss_grad(z, labels, scale: float = 1.0):
         raise ValueError(f"labels must hold one value per logit ({B}), got {labels.numel()}")
     dz = torch.empty_like(z)
     loss = torch.empty(1, dtype=torch.float32, device=z.device)
-    with _Launch("ce2_loss_grad", z.device):
-        st = _lib.load().advstep_ce2_loss_grad_f32(z.data_ptr(), labels.data_ptr(), dz.data_ptr(), loss.data_ptr(), B,
-                                                   scale, _stream(z.device))
-    _lib.check(st, "advstep_ce2_loss_grad_f32")
+    _call("advstep_ce2_loss_grad_f32", z.device, z, labels, dz, loss, B, scale, bracket="ce2_loss_grad")
     return dz, loss
 
 
@@ -431,17 +432,15 @@ def fab_hyperplane(gz, x, z=None, labels=None, norm: str = "Linf"):
     dev = gz.device
     gnorm, gdot = torch.empty(B, device=dev), torch.empty(B, device=dev)
     wscale = b = None
-    zp = lp = wp = bp = None
     if z is not None:
         _require(z, "z"), _require(labels, "labels", torch.int64)
         if z.numel() != B or labels.numel() != B:
             raise ValueError(f"z / labels must hold one value per row ({B})")
         wscale, b = torch.empty(B, device=dev), torch.empty(B, device=dev)
-        zp, lp, wp, bp = z.data_ptr(), labels.data_ptr(), wscale.data_ptr(), b.data_ptr()
-    with _Launch("fab_hyperplane", dev):
-        st = _lib.load().advstep_fab_hyperplane_f32(gz.data_ptr(), x.data_ptr(), zp, lp, wp, bp, gnorm.data_ptr(),
-                                                    gdot.data_ptr(), B, T, _fab_kind(norm), _stream(dev))
-    _lib.check(st, "advstep_fab_hyperplane_f32")
+    else:
+        labels = None                            # the selection's four operands go in together or not at all
+    _call("advstep_fab_hyperplane_f32", dev, gz, x, z, labels, wscale, b, gnorm, gdot, B, T, _fab_kind(norm),
+          bracket="fab_hyperplane")
     return wscale, b, gnorm, gdot
 
 
@@ -460,12 +459,8 @@ def fab_projection(points, w, b, norm: str = "Linf", wscale=None, out=None):
             raise ValueError(f"wscale must hold one value per row of w ({w_rows})")
     d = _out_like(points, out, "out")
     dnorm = torch.empty(R, device=points.device)
-    with _Launch("fab_projection", points.device):
-        st = _lib.load().advstep_fab_projection_f32(points.data_ptr(), w.data_ptr(),
-                                                    None if wscale is None else wscale.data_ptr(), b.data_ptr(),
-                                                    d.data_ptr(), dnorm.data_ptr(), R, w_rows, T, _fab_kind(norm),
-                                                    _stream(points.device))
-    _lib.check(st, "advstep_fab_projection_f32")
+    _call("advstep_fab_projection_f32", points.device, points, w, wscale, b, d, dnorm, R, w_rows, T, _fab_kind(norm),
+          bracket="fab_projection")
     return d, dnorm
 
 
@@ -478,10 +473,7 @@ def fab_combine(x1, x0, d1, d2, n1, n2, eta: float, alpha_max: float, out=None):
     if n1.numel() != B or n2.numel() != B:
         raise ValueError(f"n1 / n2 must hold one value per row ({B})")
     res = _out_like(x1, out, "out")
-    with _Launch("fab_combine", x1.device):
-        st = _lib.load().advstep_fab_combine_f32(x1.data_ptr(), x0.data_ptr(), d1.data_ptr(), d2.data_ptr(), n1.data_ptr(),
-                                                 n2.data_ptr(), res.data_ptr(), B, T, eta, alpha_max, _stream(x1.device))
-    _lib.check(st, "advstep_fab_combine_f32")
+    _call("advstep_fab_combine_f32", x1.device, x1, x0, d1, d2, n1, n2, res, B, T, eta, alpha_max, bracket="fab_combine")
     return res
 
 
@@ -496,10 +488,8 @@ def fab_backward_step(x1, x0, adv, res2, is_adv, beta: float, norm: str = "Linf"
     _require(is_adv, "is_adv", torch.uint8)
     if res2.numel() != B or is_adv.numel() != B:
         raise ValueError(f"res2 / is_adv must hold one value per row ({B})")
-    with _Launch("fab_backward_step", x1.device):
-        st = _lib.load().advstep_fab_backward_step_f32(x1.data_ptr(), x0.data_ptr(), adv.data_ptr(), res2.data_ptr(),
-                                                       is_adv.data_ptr(), B, T, beta, _fab_kind(norm), _stream(x1.device))
-    _lib.check(st, "advstep_fab_backward_step_f32")
+    _call("advstep_fab_backward_step_f32", x1.device, x1, x0, adv, res2, is_adv, B, T, beta, _fab_kind(norm),
+          bracket="fab_backward_step")
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -517,11 +507,18 @@ def _apgd_norm(norm: str) -> int:
         raise ValueError(f"APGD norm must be 'Linf' or 'L2', got {norm!r}") from None
 
 
-def _per_row(t: torch.Tensor, name: str, B: int, dtype=torch.float32) -> torch.Tensor:
+def _per_row(t: torch.Tensor, name: str, B: int, dtype=torch.float32, device=None) -> torch.Tensor:
     _require(t, name, dtype)
     if t.numel() != B:
         raise ValueError(f"{name} must hold one value per row ({B}), got {t.numel()}")
+    if device is not None:
+        _on_device(t, name, device)
     return t
+
+
+def _optional_rows(t: Optional[torch.Tensor], name: str, B: int, device) -> Optional[torch.Tensor]:
+    """One float32 value per row, (B,) or (B, 1), on `device` — or None, which the library takes as a null pointer."""
+    return None if t is None else _per_row(t, name, B, device=device)
 
 
 def apgd_init(x, eps: float, norm: str = "Linf", draw=None, seed: Optional[int] = None, offset: int = 0,
@@ -537,16 +534,11 @@ def apgd_init(x, eps: float, norm: str = "Linf", draw=None, seed: Optional[int] 
         if draw is not None:
             _require(draw, "draw")
             _same_shape(("x", x), ("draw", draw))
-            st = _lib.load().advstep_apgd_init_noise_f32(x.data_ptr(), draw.data_ptr(), out.data_ptr(), B, T, kind, eps, lo,
-                                                         hi, ws, ws_bytes, _stream(x.device))
-            what = "advstep_apgd_init_noise_f32"
+            _call("advstep_apgd_init_noise_f32", x.device, x, draw, out, B, T, kind, eps, lo, hi, ws, ws_bytes)
         else:
             if seed is None:
                 raise ValueError("apgd_init needs either `draw` or a Philox `seed`")
-            st = _lib.load().advstep_apgd_init_philox_f32(x.data_ptr(), out.data_ptr(), B, T, kind, eps, lo, hi, seed, offset,
-                                                          ws, ws_bytes, _stream(x.device))
-            what = "advstep_apgd_init_philox_f32"
-    _lib.check(st, what)
+            _call("advstep_apgd_init_philox_f32", x.device, x, out, B, T, kind, eps, lo, hi, seed, offset, ws, ws_bytes)
     return out
 
 
@@ -560,21 +552,18 @@ def apgd_eval(z, labels, state=None, mode: str = "grad", i: int = 0):
     m = _APGD_MODES[mode]
     dz = torch.empty_like(z)
     loss = torch.empty(B, dtype=torch.float32, device=z.device)
-    ptr = {}
+    rows = [None] * 6                            # mode 'grad': no state, six null pointers
     if m:
-        for name, dt in (("acc", torch.uint8), ("flags", torch.uint8), ("loss_best", torch.float32),
-                         ("loss_best_last_check", torch.float32), ("reduced_last_check", torch.uint8)):
-            ptr[name] = _per_row(getattr(state, name), name, B, dt).data_ptr()
+        rows = [_per_row(getattr(state, name), name, B, dt)
+                for name, dt in (("acc", torch.uint8), ("flags", torch.uint8), ("loss_best", torch.float32),
+                                 ("loss_best_last_check", torch.float32), ("reduced_last_check", torch.uint8))]
         _require(state.loss_steps, "loss_steps")
         if state.loss_steps.dim() != 2 or state.loss_steps.shape[1] != B or not 0 <= i < state.loss_steps.shape[0]:
             raise ValueError(f"loss_steps {tuple(state.loss_steps.shape)} has no row {i} of {B} losses")
-        ptr["loss_steps"] = state.loss_steps.data_ptr()
-    with _Launch("apgd_eval", z.device):
-        st = _lib.load().advstep_apgd_eval_f32(z.data_ptr(), labels.data_ptr(), dz.data_ptr(), loss.data_ptr(), m, i,
-                                               ptr.get("acc"), ptr.get("flags"), ptr.get("loss_best"),
-                                               ptr.get("loss_best_last_check"), ptr.get("reduced_last_check"),
-                                               ptr.get("loss_steps"), B, _stream(z.device))
-    _lib.check(st, "advstep_apgd_eval_f32")
+        rows.append(state.loss_steps)
+    acc, flags, best, last_check, reduced, steps = rows
+    _call("advstep_apgd_eval_f32", z.device, z, labels, dz, loss, m, i, acc, flags, best, last_check, reduced, steps, B,
+          bracket="apgd_eval")
     return dz, loss
 
 
@@ -588,12 +577,8 @@ def apgd_checkpoint(state, i: int, k: int, rho: float) -> None:
         _per_row(getattr(state, name), name, B, dt)
     if state.loss_steps.shape != (steps, B) or not (0 <= i < steps and k >= 1 and i - k >= -1):
         raise ValueError(f"checkpoint at i={i}, k={k} does not fit loss_steps {tuple(state.loss_steps.shape)}")
-    with _Launch("apgd_checkpoint", state.loss_best.device):
-        st = _lib.load().advstep_apgd_checkpoint_f32(state.loss_steps.data_ptr(), steps, i, k, rho,
-                                                     state.loss_best.data_ptr(), state.loss_best_last_check.data_ptr(),
-                                                     state.reduced_last_check.data_ptr(), state.step_size.data_ptr(),
-                                                     state.flags.data_ptr(), B, _stream(state.loss_best.device))
-    _lib.check(st, "advstep_apgd_checkpoint_f32")
+    _call("advstep_apgd_checkpoint_f32", state.loss_best.device, state.loss_steps, steps, i, k, rho, state.loss_best,
+          state.loss_best_last_check, state.reduced_last_check, state.step_size, state.flags, B, bracket="apgd_checkpoint")
 
 
 def apgd_track(x_adv, grad, x_best, grad_best, x_best_adv, flags) -> None:
@@ -605,10 +590,7 @@ def apgd_track(x_adv, grad, x_best, grad_best, x_best_adv, flags) -> None:
     _same_shape(*named)
     B, T = _rows(x_adv, "x_adv")
     _per_row(flags, "flags", B, torch.uint8)
-    with _Launch("apgd_track", x_adv.device):
-        st = _lib.load().advstep_apgd_track_f32(x_adv.data_ptr(), grad.data_ptr(), x_best.data_ptr(), grad_best.data_ptr(),
-                                                x_best_adv.data_ptr(), flags.data_ptr(), B, T, _stream(x_adv.device))
-    _lib.check(st, "advstep_apgd_track_f32")
+    _call("advstep_apgd_track_f32", x_adv.device, x_adv, grad, x_best, grad_best, x_best_adv, flags, B, T, bracket="apgd_track")
 
 
 def _apgd_step_args(cur, prev, grad, x, step_size):
@@ -625,10 +607,8 @@ def apgd_linf_step(cur, prev, grad, x, step_size, eps: float, a: float, out=None
     """The L-inf momentum step of apgd.py:141-149; `out` may be `prev` (ping-pong)."""
     B, T = _apgd_step_args(cur, prev, grad, x, step_size)
     out = _out_like(cur, out)
-    with _Launch("apgd_linf_step", cur.device, tensors=(cur, prev, grad, x, out)):
-        st = _lib.load().advstep_apgd_linf_step_f32(cur.data_ptr(), prev.data_ptr(), grad.data_ptr(), x.data_ptr(),
-                                                    step_size.data_ptr(), out.data_ptr(), B, T, eps, a, _stream(cur.device))
-    _lib.check(st, "advstep_apgd_linf_step_f32")
+    _call("advstep_apgd_linf_step_f32", cur.device, cur, prev, grad, x, step_size, out, B, T, eps, a,
+          bracket="apgd_linf_step", tensors=(cur, prev, grad, x, out))
     return out
 
 
@@ -641,10 +621,7 @@ def apgd_l2_step(cur, prev, grad, x, step_size, eps: float, a: float, out=None, 
     # compulsory traffic: grad x4, cur x3, x x3, prev x2, out x1 (four row passes that recompute rather than store)
     with _Launch("apgd_l2_step", cur.device, tensors=(grad,) * 4 + (cur,) * 3 + (x,) * 3 + (prev,) * 2 + (out,)):
         ws, ws_bytes = _workspace(cur.device, B, T)
-        st = _lib.load().advstep_apgd_l2_step_f32(cur.data_ptr(), prev.data_ptr(), grad.data_ptr(), x.data_ptr(),
-                                                  step_size.data_ptr(), out.data_ptr(), norms.data_ptr(), B, T, eps, a, ws,
-                                                  ws_bytes, _stream(cur.device))
-    _lib.check(st, "advstep_apgd_l2_step_f32")
+        _call("advstep_apgd_l2_step_f32", cur.device, cur, prev, grad, x, step_size, out, norms, B, T, eps, a, ws, ws_bytes)
     return (out, norms) if return_norms else out
 
 
@@ -665,10 +642,8 @@ def l1_box_project(x, u, eps: float, out=None):
     _same_shape(("x", x), ("u", u))
     B, T = _rows(x, "x")
     out = _out_like(u, out)
-    with _Launch("l1_box_project", x.device, tensors=(x, u, out)):
-        st = _lib.load().advstep_l1_box_project_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), _positive_eps(eps), B, T,
-                                                    _stream(x.device))
-    _lib.check(st, "advstep_l1_box_project_f32")
+    _call("advstep_l1_box_project_f32", x.device, x, u, out, _positive_eps(eps), B, T,
+          bracket="l1_box_project", tensors=(x, u, out))
     return out
 
 
@@ -682,16 +657,11 @@ def apgdl1_init(x, eps: float, draw=None, seed: Optional[int] = None, offset: in
         if draw is not None:
             _require(draw, "draw")
             _same_shape(("x", x), ("draw", draw))
-            st = _lib.load().advstep_apgdl1_init_f32(x.data_ptr(), draw.data_ptr(), out.data_ptr(), B, T, _positive_eps(eps),
-                                                     _stream(x.device))
-            what = "advstep_apgdl1_init_f32"
+            _call("advstep_apgdl1_init_f32", x.device, x, draw, out, B, T, _positive_eps(eps))
         else:
             if seed is None:
                 raise ValueError("apgdl1_init needs either `draw` or a Philox `seed`")
-            st = _lib.load().advstep_apgdl1_init_philox_f32(x.data_ptr(), out.data_ptr(), B, T, _positive_eps(eps), seed,
-                                                            offset, _stream(x.device))
-            what = "advstep_apgdl1_init_philox_f32"
-    _lib.check(st, what)
+            _call("advstep_apgdl1_init_philox_f32", x.device, x, out, B, T, _positive_eps(eps), seed, offset)
     return out
 
 
@@ -706,11 +676,8 @@ def apgdl1_step(cur, grad, x, step_size, topk, eps: float, out=None, return_stat
     _per_row(step_size, "step_size", B), _per_row(topk, "topk", B)
     out = _out_like(cur, out)
     stats = torch.empty((B, 2), dtype=torch.float32, device=cur.device) if return_stats else None
-    with _Launch("apgdl1_step", cur.device, tensors=(cur, grad, x, out)):
-        st = _lib.load().advstep_apgdl1_step_f32(cur.data_ptr(), grad.data_ptr(), x.data_ptr(), step_size.data_ptr(),
-                                                 topk.data_ptr(), out.data_ptr(), stats.data_ptr() if return_stats else None,
-                                                 B, T, _positive_eps(eps), _stream(cur.device))
-    _lib.check(st, "advstep_apgdl1_step_f32")
+    _call("advstep_apgdl1_step_f32", cur.device, cur, grad, x, step_size, topk, out, stats, B, T, _positive_eps(eps),
+          bracket="apgdl1_step", tensors=(cur, grad, x, out))
     return (out, stats) if return_stats else out
 
 
@@ -725,12 +692,8 @@ def apgdl1_checkpoint(cur, x_best, x, state, eps: float) -> None:
     for name, dt in (("flags", torch.uint8), ("sp_old", torch.float32), ("topk", torch.float32),
                      ("step_size", torch.float32)):
         _per_row(getattr(state, name), name, B, dt)
-    with _Launch("apgdl1_checkpoint", cur.device, tensors=(cur, x)):
-        st = _lib.load().advstep_apgdl1_checkpoint_f32(cur.data_ptr(), x_best.data_ptr(), x.data_ptr(),
-                                                       state.flags.data_ptr(), state.sp_old.data_ptr(),
-                                                       state.topk.data_ptr(), state.step_size.data_ptr(), B, T,
-                                                       _positive_eps(eps), _stream(cur.device))
-    _lib.check(st, "advstep_apgdl1_checkpoint_f32")
+    _call("advstep_apgdl1_checkpoint_f32", cur.device, cur, x_best, x, state.flags, state.sp_old, state.topk,
+          state.step_size, B, T, _positive_eps(eps), bracket="apgdl1_checkpoint", tensors=(cur, x))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -753,10 +716,7 @@ def l0_box_project(x, u, k: int, eps_inf: float = float("inf"), out=None):
     B, T = _rows(x, "x")
     k, eps_inf = _l0_budget(k, eps_inf)
     out = _out_like(u, out)
-    with _Launch("l0_box_project", x.device, tensors=(x, u, out)):
-        st = _lib.load().advstep_l0_box_project_f32(x.data_ptr(), u.data_ptr(), out.data_ptr(), k, eps_inf, B, T,
-                                                    _stream(x.device))
-    _lib.check(st, "advstep_l0_box_project_f32")
+    _call("advstep_l0_box_project_f32", x.device, x, u, out, k, eps_inf, B, T, bracket="l0_box_project", tensors=(x, u, out))
     return out
 
 
@@ -773,11 +733,8 @@ def pgdl0_step(cur, grad, x, step: float, k: int, eps_inf: float = float("inf"),
         raise ValueError(f"step must be non-negative, got {step!r}")
     out = _out_like(cur, out)
     stats = torch.empty((B, 4), dtype=torch.float32, device=cur.device) if return_stats else None
-    with _Launch("pgdl0_step", cur.device, tensors=(cur, grad, x, out)):
-        st = _lib.load().advstep_pgdl0_step_f32(cur.data_ptr(), grad.data_ptr(), x.data_ptr(), out.data_ptr(),
-                                                stats.data_ptr() if return_stats else None, step, k, eps_inf, B, T,
-                                                _stream(cur.device))
-    _lib.check(st, "advstep_pgdl0_step_f32")
+    _call("advstep_pgdl0_step_f32", cur.device, cur, grad, x, out, stats, step, k, eps_inf, B, T,
+          bracket="pgdl0_step", tensors=(cur, grad, x, out))
     return (out, stats) if return_stats else out
 
 
@@ -805,12 +762,8 @@ def mi_step(adv, grad, orig, momentum, alpha: float, eps: float, decay: float, v
     # compulsory traffic: grad twice, momentum in and back, adv, orig, out (+ v twice, + nes_out)
     with _Launch("mi_step", adv.device, tensors=(grad, grad, momentum, momentum, adv, orig, out, v, v, nes_out)):
         ws, ws_bytes = _workspace(adv.device, B, T)
-        st = _lib.load().advstep_mi_step_f32(adv.data_ptr(), grad.data_ptr(), v.data_ptr() if v is not None else None,
-                                             orig.data_ptr(), momentum.data_ptr(), out.data_ptr(),
-                                             nes_out.data_ptr() if nes_out is not None else None, B, T, alpha, eps, decay,
-                                             nes_scale, lo, hi, gmean.data_ptr() if return_mean else None, ws, ws_bytes,
-                                             _stream(adv.device))
-    _lib.check(st, "advstep_mi_step_f32")
+        _call("advstep_mi_step_f32", adv.device, adv, grad, v, orig, momentum, out, nes_out, B, T, alpha, eps, decay, nes_scale,
+              lo, hi, gmean, ws, ws_bytes)
     return (out, gmean) if return_mean else out
 
 
@@ -822,17 +775,13 @@ def vt_neighbor(adv, bound: float, draw=None, seed: Optional[int] = None, offset
     if draw is not None:
         _require(draw, "draw")
         _same_shape(("adv", adv), ("draw", draw))
-        with _Launch("vt_neighbor", adv.device, tensors=(adv, draw, out)):
-            st = _lib.load().advstep_vt_neighbor_noise_f32(adv.data_ptr(), draw.data_ptr(), out.data_ptr(), adv.numel(),
-                                                           _stream(adv.device))
-        _lib.check(st, "advstep_vt_neighbor_noise_f32")
+        _call("advstep_vt_neighbor_noise_f32", adv.device, adv, draw, out, adv.numel(),
+              bracket="vt_neighbor", tensors=(adv, draw, out))
     else:
         if seed is None:
             raise ValueError("vt_neighbor needs either `draw` or a Philox `seed`")
-        with _Launch("vt_neighbor", adv.device, tensors=(adv, out)):
-            st = _lib.load().advstep_vt_neighbor_philox_f32(adv.data_ptr(), out.data_ptr(), adv.numel(), bound, seed, offset,
-                                                            _stream(adv.device))
-        _lib.check(st, "advstep_vt_neighbor_philox_f32")
+        _call("advstep_vt_neighbor_philox_f32", adv.device, adv, out, adv.numel(), bound, seed, offset,
+              bracket="vt_neighbor", tensors=(adv, out))
     return out
 
 
@@ -840,10 +789,8 @@ def vt_accumulate(gv, g, first: bool) -> None:
     """In place: gv = g when `first` (the zero-filled accumulator of vmifgsm.py:82 plus g), else gv += g."""
     _require(gv, "gv"), _require(g, "g")
     _same_shape(("gv", gv), ("g", g))
-    with _Launch("vt_accumulate", gv.device, tensors=(g, gv) if first else (gv, g, gv)):
-        st = _lib.load().advstep_vt_accumulate_f32(gv.data_ptr(), g.data_ptr(), gv.numel(), 1 if first else 0,
-                                                   _stream(gv.device))
-    _lib.check(st, "advstep_vt_accumulate_f32")
+    _call("advstep_vt_accumulate_f32", gv.device, gv, g, gv.numel(), 1 if first else 0,
+          bracket="vt_accumulate", tensors=(g, gv) if first else (gv, g, gv))
 
 
 def vt_variance(gv, adv_grad, N: int, out=None):
@@ -853,10 +800,8 @@ def vt_variance(gv, adv_grad, N: int, out=None):
     if int(N) < 1:
         raise ValueError(f"N must be at least 1, got {N}")
     out = _out_like(gv, out)
-    with _Launch("vt_variance", gv.device, tensors=(gv, adv_grad, out)):
-        st = _lib.load().advstep_vt_variance_f32(gv.data_ptr(), adv_grad.data_ptr(), out.data_ptr(), gv.numel(), int(N),
-                                                 _stream(gv.device))
-    _lib.check(st, "advstep_vt_variance_f32")
+    _call("advstep_vt_variance_f32", gv.device, gv, adv_grad, out, gv.numel(), int(N),
+          bracket="vt_variance", tensors=(gv, adv_grad, out))
     return out
 
 
@@ -894,11 +839,8 @@ def multi_route(adv, x, z, labels, rows, final, next_x=None, next_y=None, next_r
     counts = (torch.zeros if n == 0 else torch.empty)(2, dtype=torch.int32, device=adv.device)
     scratch = torch.empty(max(n, 1), dtype=torch.int32, device=adv.device)
     # compulsory traffic: every row is read once (from adv or from x) and written once (to final or to next_x)
-    with _Launch("multi_route", adv.device, tensors=(adv, adv)):
-        st = _lib.load().advstep_multi_route_f32(adv.data_ptr(), x.data_ptr(), z.data_ptr(), labels.data_ptr(), rows.data_ptr(),
-                                                 final.data_ptr(), next_x.data_ptr(), next_y.data_ptr(), next_rows.data_ptr(),
-                                                 counts.data_ptr(), scratch.data_ptr(), n, B, T, _stream(adv.device))
-    _lib.check(st, "advstep_multi_route_f32")
+    _call("advstep_multi_route_f32", adv.device, adv, x, z, labels, rows, final, next_x, next_y, next_rows, counts, scratch,
+          n, B, T, bracket="multi_route", tensors=(adv, adv))
     return next_x, next_y, next_rows, counts
 
 
@@ -917,11 +859,7 @@ def perturbation_stats(x, adv, out=None):
     _require(x, "x"), _require(adv, "adv")
     _same_shape(("x", x), ("adv", adv))
     B, T = _rows(x, "x")
-    if out is None:
-        out = torch.empty((len(PERTURBATION_PLANES), B), dtype=torch.float32, device=x.device)
-    _require(out, "out")
-    if out.shape != (len(PERTURBATION_PLANES), B) or out.device != x.device:
-        raise ValueError(f"out must be ({len(PERTURBATION_PLANES)}, {B}) on {x.device}, got {tuple(out.shape)}@{out.device}")
+    out = _shaped(out, "out", (len(PERTURBATION_PLANES), B), x.device)
     lib = _lib.load()
     with _Launch("perturbation_stats", x.device, tensors=(x, adv)):
         # partials only, rewritten by every call: keyed by stream like the row workspace (two lanes never share one), and
@@ -930,8 +868,7 @@ def perturbation_stats(x, adv, out=None):
                "perturb")
         ws, ws_bytes = _scratch(key, lambda: torch.empty(max(lib.advstep_perturb_stats_workspace_bytes(B, T), 256),
                                                          dtype=torch.uint8, device=x.device))
-        st = lib.advstep_perturb_stats_f32(x.data_ptr(), adv.data_ptr(), out.data_ptr(), ws, ws_bytes, B, T, _stream(x.device))
-    _lib.check(st, "advstep_perturb_stats_f32")
+        _call("advstep_perturb_stats_f32", x.device, x, adv, out, ws, ws_bytes, B, T)
     return out
 
 
@@ -940,13 +877,6 @@ def perturbation_stats(x, adv, out=None):
 # ---------------------------------------------------------------------------------------------------------
 
 RADIUS_PLANES = ("lo", "hi", "eps", "best")     # the rows of a search state, in the order of include/advstep_radius.h
-
-
-def _radius_state(t: torch.Tensor, name: str, B: int, device) -> torch.Tensor:
-    _require(t, name)
-    if t.shape != (len(RADIUS_PLANES), B) or t.device != device:
-        raise ValueError(f"{name} must be ({len(RADIUS_PLANES)}, {B}) on {device}, got {tuple(t.shape)}@{t.device}")
-    return t
 
 
 def row_pgd_linf_step(adv, grad, orig, eps_rows, alpha_abs: float, alpha_rel: float, lo: float = 0.0, hi: float = 1.0,
@@ -958,10 +888,8 @@ def row_pgd_linf_step(adv, grad, orig, eps_rows, alpha_abs: float, alpha_rel: fl
     B, T = _rows(adv, "adv")
     _per_row(eps_rows, "eps_rows", B)
     out = _out_like(adv, out)
-    with _Launch("row_pgd_linf_step", adv.device, tensors=(adv, grad, orig, out)):
-        st = _lib.load().advstep_row_pgd_linf_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), eps_rows.data_ptr(),
-                                                       alpha_abs, alpha_rel, lo, hi, out.data_ptr(), B, T, _stream(adv.device))
-    _lib.check(st, "advstep_row_pgd_linf_step_f32")
+    _call("advstep_row_pgd_linf_step_f32", adv.device, adv, grad, orig, eps_rows, alpha_abs, alpha_rel, lo, hi, out, B, T,
+          bracket="row_pgd_linf_step", tensors=(adv, grad, orig, out))
     return out
 
 
@@ -981,12 +909,8 @@ def row_pgd_l2_step(adv, grad, orig, eps_rows, alpha_abs: float, alpha_rel: floa
     # compulsory traffic: grad three times, adv and orig twice, out once
     with _Launch("row_pgd_l2_step", adv.device, tensors=(grad,) * 3 + (adv,) * 2 + (orig,) * 2 + (out,)):
         ws, ws_bytes = _workspace(adv.device, B, T)
-        st = _lib.load().advstep_row_pgd_l2_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), eps_rows.data_ptr(),
-                                                     alpha_abs, alpha_rel, eps_div, lo, hi, out.data_ptr(),
-                                                     gn.data_ptr() if return_norms else None,
-                                                     dn.data_ptr() if return_norms else None, B, T, ws, ws_bytes,
-                                                     _stream(adv.device))
-    _lib.check(st, "advstep_row_pgd_l2_step_f32")
+        _call("advstep_row_pgd_l2_step_f32", adv.device, adv, grad, orig, eps_rows, alpha_abs, alpha_rel, eps_div, lo, hi, out,
+              gn, dn, B, T, ws, ws_bytes)
     return (out, gn, dn) if return_norms else out
 
 
@@ -998,13 +922,8 @@ def radius_begin(z0, labels, eps_max: float, state=None):
     _per_row(labels, "labels", B, torch.int64)
     if not float(eps_max) >= 0.0:
         raise ValueError(f"eps_max must be a radius >= 0, got {eps_max}")
-    if state is None:
-        state = torch.empty((len(RADIUS_PLANES), B), dtype=torch.float32, device=z0.device)
-    _radius_state(state, "state", B, z0.device)
-    with _Launch("radius_begin", z0.device):
-        st = _lib.load().advstep_radius_begin_f32(z0.data_ptr(), labels.data_ptr(), eps_max, state.data_ptr(), B,
-                                                  _stream(z0.device))
-    _lib.check(st, "advstep_radius_begin_f32")
+    state = _shaped(state, "state", (len(RADIUS_PLANES), B), z0.device)
+    _call("advstep_radius_begin_f32", z0.device, z0, labels, eps_max, state, B, bracket="radius_begin")
     return state
 
 
@@ -1020,16 +939,11 @@ def radius_round(adv, z, labels, first: bool, state, best_adv, out=None):
     if z.numel() != B or z.device != adv.device:
         raise ValueError(f"z must hold one logit per row of adv ({B}) on {adv.device}, got {tuple(z.shape)}@{z.device}")
     _per_row(labels, "labels", B, torch.int64)
-    _radius_state(state, "state", B, adv.device)
-    if out is None:
-        out = torch.empty_like(state)
-    _radius_state(out, "out", B, adv.device)
+    _shaped(_require(state, "state"), "state", (len(RADIUS_PLANES), B), adv.device)
+    out = _shaped(out, "out", (len(RADIUS_PLANES), B), adv.device)
     # compulsory traffic: at most one read and one write of every row (only the rows that improve move)
-    with _Launch("radius_round", adv.device, tensors=(adv, best_adv)):
-        st = _lib.load().advstep_radius_round_f32(adv.data_ptr(), z.data_ptr(), labels.data_ptr(), 1 if first else 0,
-                                                  state.data_ptr(), out.data_ptr(), best_adv.data_ptr(), B, T,
-                                                  _stream(adv.device))
-    _lib.check(st, "advstep_radius_round_f32")
+    _call("advstep_radius_round_f32", adv.device, adv, z, labels, 1 if first else 0, state, out, best_adv, B, T,
+          bracket="radius_round", tensors=(adv, best_adv))
     return out
 
 
@@ -1043,16 +957,6 @@ def _snr_rho(rho: float) -> float:
     return float(rho)
 
 
-def _offset_rows(offset_rows, B: int, device):
-    """The rows' c = mn / (mx - mn), (B,) or (B, 1), or None (c = 0) -> the pointer the library takes."""
-    if offset_rows is None:
-        return None
-    _per_row(offset_rows, "offset_rows", B)
-    if offset_rows.device != device:
-        raise ValueError(f"offset_rows lives on {offset_rows.device}, the rows on {device}")
-    return offset_rows.data_ptr()
-
-
 def seg_pgd_step(adv, grad, orig, offset_rows, rho: float, alpha_rel: float, eps_div: float, lo: float = 0.0, hi: float = 1.0,
                  out=None):
     """The PGD step under a segmental-SNR budget: every 256-sample segment of a row is an L2 ball of radius
@@ -1062,13 +966,11 @@ def seg_pgd_step(adv, grad, orig, offset_rows, rho: float, alpha_rel: float, eps
     _require(adv, "adv"), _require(grad, "grad"), _require(orig, "orig")
     _same_shape(("adv", adv), ("grad", grad), ("orig", orig))
     B, T = _rows(adv, "adv")
-    c = _offset_rows(offset_rows, B, adv.device)
+    c = _optional_rows(offset_rows, "offset_rows", B, adv.device)     # the rows' c = mn / (mx - mn), or None (c = 0)
     rho = _snr_rho(rho)
     out = _out_like(adv, out)
-    with _Launch("seg_pgd_step", adv.device, tensors=(adv, grad, orig, out)):
-        st = _lib.load().advstep_seg_pgd_step_f32(adv.data_ptr(), grad.data_ptr(), orig.data_ptr(), c, rho, alpha_rel, eps_div,
-                                                  lo, hi, out.data_ptr(), B, T, _stream(adv.device))
-    _lib.check(st, "advstep_seg_pgd_step_f32")
+    _call("advstep_seg_pgd_step_f32", adv.device, adv, grad, orig, c, rho, alpha_rel, eps_div, lo, hi, out, B, T,
+          bracket="seg_pgd_step", tensors=(adv, grad, orig, out))
     return out
 
 
@@ -1077,15 +979,14 @@ def snr_row_radius(x, offset_rows, rho: float, out=None):
     is the PGD step under a global SNR budget.  Two launches, no host read."""
     _require(x, "x")
     B, T = _rows(x, "x")
-    c = _offset_rows(offset_rows, B, x.device)
+    c = _optional_rows(offset_rows, "offset_rows", B, x.device)
     rho = _snr_rho(rho)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=x.device)
     _per_row(out, "out", B)
     with _Launch("snr_row_radius", x.device, tensors=(x,)):
         ws, ws_bytes = _workspace(x.device, B, T)
-        st = _lib.load().advstep_snr_row_radius_f32(x.data_ptr(), c, rho, out.data_ptr(), B, T, ws, ws_bytes, _stream(x.device))
-    _lib.check(st, "advstep_snr_row_radius_f32")
+        _call("advstep_snr_row_radius_f32", x.device, x, c, rho, out, B, T, ws, ws_bytes)
     return out
 
 
@@ -1096,16 +997,6 @@ def snr_row_radius(x, offset_rows, rho: float, out=None):
 UNIVERSAL_GROUP_ROWS = 16                       # ADVSTEP_UNIVERSAL_GROUP_ROWS: rows per group of universal_colsum's first launch
 
 
-def _row_weight(row_weight, B: int, device):
-    """The rows' w_b, (B,) or (B, 1), or None (w_b = 1) -> the pointer the library takes."""
-    if row_weight is None:
-        return None
-    _per_row(row_weight, "row_weight", B)
-    if row_weight.device != device:
-        raise ValueError(f"row_weight lives on {row_weight.device}, the rows on {device}")
-    return row_weight.data_ptr()
-
-
 def universal_colsum(grad, row_weight=None, out=None):
     """(1, T) float32: out[t] = sum_b w_b * grad[b, t], w_b = row_weight[b] (None: 1) — the gradient of the batch's loss with
     respect to one perturbation shared by its rows.  Every product rounds once and the order of the additions depends on (B, T)
@@ -1113,7 +1004,7 @@ def universal_colsum(grad, row_weight=None, out=None):
     read."""
     _require(grad, "grad")
     B, T = _rows(grad, "grad")
-    w = _row_weight(row_weight, B, grad.device)
+    w = _optional_rows(row_weight, "row_weight", B, grad.device)      # the rows' w_b, or None (w_b = 1)
     if out is None:
         out = torch.empty((1, T), dtype=torch.float32, device=grad.device)
     _require(out, "out")
@@ -1126,8 +1017,7 @@ def universal_colsum(grad, row_weight=None, out=None):
                int(T), "universal")
         ws, ws_bytes = _scratch(key, lambda: torch.empty(max(lib.advstep_universal_workspace_bytes(B, T), 256), dtype=torch.uint8,
                                                          device=grad.device))
-        st = lib.advstep_universal_colsum_f32(grad.data_ptr(), w, out.data_ptr(), B, T, ws, ws_bytes, _stream(grad.device))
-    _lib.check(st, "advstep_universal_colsum_f32")
+        _call("advstep_universal_colsum_f32", grad.device, grad, w, out, B, T, ws, ws_bytes)
     return out
 
 
@@ -1138,12 +1028,9 @@ def universal_apply(x, delta, row_weight=None, lo: float = 0.0, hi: float = 1.0,
     B, T = _rows(x, "x")
     if delta.numel() != T or delta.device != x.device:
         raise ValueError(f"delta must hold one value per sample of a row ({T}) on {x.device}, got {tuple(delta.shape)}@{delta.device}")
-    w = _row_weight(row_weight, B, x.device)
+    w = _optional_rows(row_weight, "row_weight", B, x.device)
     out = _out_like(x, out)
-    with _Launch("universal_apply", x.device, tensors=(x, out)):
-        st = _lib.load().advstep_universal_apply_f32(x.data_ptr(), delta.data_ptr(), w, out.data_ptr(), B, T, lo, hi,
-                                                     _stream(x.device))
-    _lib.check(st, "advstep_universal_apply_f32")
+    _call("advstep_universal_apply_f32", x.device, x, delta, w, out, B, T, lo, hi, bracket="universal_apply", tensors=(x, out))
     return out
 
 
@@ -1165,15 +1052,9 @@ def spsa_probe(adv, delta: float, seed: int, offset: int = 0, s0: int = 0, ns: i
     s0, ns = int(s0), int(ns)
     if s0 < 0 or ns < 0 or s0 + ns > 1 + 2 * SPSA_MAX_DIRECTIONS:
         raise ValueError(f"slots {s0} .. {s0 + ns - 1} are outside 0 .. {2 * SPSA_MAX_DIRECTIONS}")
-    if out is None:
-        out = torch.empty((ns,) + tuple(adv.shape), dtype=torch.float32, device=adv.device)
-    _require(out, "out")
-    if out.numel() != ns * B * T or out.device != adv.device:
-        raise ValueError(f"out must hold ({ns}, {B}, {T}) values on {adv.device}, got {tuple(out.shape)}@{out.device}")
-    with _Launch("spsa_probe", adv.device, tensors=(adv, out)):
-        st = _lib.load().advstep_spsa_probe_f32(adv.data_ptr(), out.data_ptr(), B, T, s0, ns, delta, lo, hi, seed, offset,
-                                                _stream(adv.device))
-    _lib.check(st, "advstep_spsa_probe_f32")
+    out = _stacked_out(out, ns, adv)
+    _call("advstep_spsa_probe_f32", adv.device, adv, out, B, T, s0, ns, delta, lo, hi, seed, offset,
+          bracket="spsa_probe", tensors=(adv, out))
     return out
 
 
@@ -1192,15 +1073,10 @@ def spsa_step(adv, orig, z, labels, queries, alpha: float, eps: float, seed: int
     n = (z.shape[0] - 1) // 2
     if n > SPSA_MAX_DIRECTIONS:
         raise ValueError(f"at most {SPSA_MAX_DIRECTIONS} direction pairs per iteration, got {n}")
-    _per_row(labels, "labels", B, torch.int64), _per_row(queries, "queries", B, torch.int32)
-    if labels.device != adv.device or queries.device != adv.device:
-        raise ValueError(f"labels and queries must live on {adv.device}, got {labels.device} and {queries.device}")
+    _per_row(labels, "labels", B, torch.int64, adv.device), _per_row(queries, "queries", B, torch.int32, adv.device)
     out = _out_like(adv, out)
-    with _Launch("spsa_step", adv.device, tensors=(adv, orig, out, z)):
-        st = _lib.load().advstep_spsa_step_f32(adv.data_ptr(), orig.data_ptr(), z.data_ptr(), labels.data_ptr(),
-                                               queries.data_ptr(), out.data_ptr(), B, T, n, alpha, eps, lo, hi, seed, offset,
-                                               _stream(adv.device))
-    _lib.check(st, "advstep_spsa_step_f32")
+    _call("advstep_spsa_step_f32", adv.device, adv, orig, z, labels, queries, out, B, T, n, alpha, eps, lo, hi, seed, offset,
+          bracket="spsa_step", tensors=(adv, orig, out, z))
     return out
 
 
@@ -1215,10 +1091,7 @@ HSJ_MAX_TRIALS = 8                              # ADVSTEP_HSJ_MAX_TRIALS: candid
 
 
 def _hsj_state(t: torch.Tensor, name: str, B: int, device) -> torch.Tensor:
-    _require(t, name)
-    if t.shape != (len(HSJ_PLANES), B) or t.device != device:
-        raise ValueError(f"{name} must be ({len(HSJ_PLANES)}, {B}) on {device}, got {tuple(t.shape)}@{t.device}")
-    return t
+    return _shaped(_require(t, name), name, (len(HSJ_PLANES), B), device)
 
 
 def _hsj_rows(cur, orig, B, **per_row):
@@ -1227,9 +1100,7 @@ def _hsj_rows(cur, orig, B, **per_row):
         _require(orig, "orig")
         _same_shape(("cur", cur), ("orig", orig))
     for name, (t, dtype) in per_row.items():
-        _per_row(t, name, B, dtype)
-        if t.device != cur.device:
-            raise ValueError(f"{name} must live on {cur.device}, got {t.device}")
+        _per_row(t, name, B, dtype, cur.device)
 
 
 def _hsj_logits(z, name: str, B: int, cap: int, device) -> int:
@@ -1249,13 +1120,9 @@ def hsj_search_open(cur, orig, dist, active, out, state=None, lo: float = 0.0, h
     _same_shape(("cur", cur), ("out", out))
     B, T = _rows(cur, "cur")
     _hsj_rows(cur, orig, B, dist=(dist, torch.float32), active=(active, torch.int32))
-    if state is None:
-        state = torch.empty((len(HSJ_PLANES), B), dtype=torch.float32, device=cur.device)
-    _hsj_state(state, "state", B, cur.device)
-    with _Launch("hsj_search_open", cur.device, tensors=(cur, orig, out)):
-        st = _lib.load().advstep_hsj_search_open_f32(cur.data_ptr(), orig.data_ptr(), dist.data_ptr(), active.data_ptr(),
-                                                     state.data_ptr(), out.data_ptr(), B, T, lo, hi, _stream(cur.device))
-    _lib.check(st, "advstep_hsj_search_open_f32")
+    state = _shaped(state, "state", (len(HSJ_PLANES), B), cur.device)
+    _call("advstep_hsj_search_open_f32", cur.device, cur, orig, dist, active, state, out, B, T, lo, hi,
+          bracket="hsj_search_open", tensors=(cur, orig, out))
     return state
 
 
@@ -1268,14 +1135,9 @@ def hsj_search_next(cur, orig, z, labels, active, state, out, state_out=None, lo
     B, T = _rows(cur, "cur")
     _hsj_rows(cur, orig, B, z=(z, torch.float32), labels=(labels, torch.int64), active=(active, torch.int32))
     _hsj_state(state, "state", B, cur.device)
-    if state_out is None:
-        state_out = torch.empty_like(state)
-    _hsj_state(state_out, "state_out", B, cur.device)
-    with _Launch("hsj_search_next", cur.device, tensors=(cur, orig, out)):
-        st = _lib.load().advstep_hsj_search_next_f32(cur.data_ptr(), orig.data_ptr(), z.data_ptr(), labels.data_ptr(),
-                                                     active.data_ptr(), state.data_ptr(), state_out.data_ptr(), out.data_ptr(),
-                                                     B, T, lo, hi, _stream(cur.device))
-    _lib.check(st, "advstep_hsj_search_next_f32")
+    state_out = _shaped(state_out, "state_out", (len(HSJ_PLANES), B), cur.device)
+    _call("advstep_hsj_search_next_f32", cur.device, cur, orig, z, labels, active, state, state_out, out, B, T, lo, hi,
+          bracket="hsj_search_next", tensors=(cur, orig, out))
     return state_out
 
 
@@ -1291,11 +1153,8 @@ def hsj_search_close(cur, orig, z, labels, active, state, queries, rounds: int, 
     if int(rounds) < 0:
         raise ValueError(f"rounds must be >= 0, got {rounds}")
     out = _out_like(cur, out)
-    with _Launch("hsj_search_close", cur.device, tensors=(cur, orig, out)):
-        st = _lib.load().advstep_hsj_search_close_f32(cur.data_ptr(), orig.data_ptr(), z.data_ptr(), labels.data_ptr(),
-                                                      active.data_ptr(), state.data_ptr(), queries.data_ptr(), int(rounds),
-                                                      out.data_ptr(), B, T, lo, hi, _stream(cur.device))
-    _lib.check(st, "advstep_hsj_search_close_f32")
+    _call("advstep_hsj_search_close_f32", cur.device, cur, orig, z, labels, active, state, queries, int(rounds), out, B, T, lo, hi,
+          bracket="hsj_search_close", tensors=(cur, orig, out))
     return out
 
 
@@ -1309,15 +1168,9 @@ def hsj_probe(cur, mag, active, seed: int, offset: int = 0, s0: int = 0, ns: int
     s0, ns = int(s0), int(ns)
     if s0 < 0 or ns < 0 or s0 + ns > HSJ_MAX_DIRECTIONS:
         raise ValueError(f"slots {s0} .. {s0 + ns - 1} are outside 0 .. {HSJ_MAX_DIRECTIONS - 1}")
-    if out is None:
-        out = torch.empty((ns,) + tuple(cur.shape), dtype=torch.float32, device=cur.device)
-    _require(out, "out")
-    if out.numel() != ns * B * T or out.device != cur.device:
-        raise ValueError(f"out must hold ({ns}, {B}, {T}) values on {cur.device}, got {tuple(out.shape)}@{out.device}")
-    with _Launch("hsj_probe", cur.device, tensors=(cur, out)):
-        st = _lib.load().advstep_hsj_probe_f32(cur.data_ptr(), mag.data_ptr(), active.data_ptr(), out.data_ptr(), B, T, s0, ns,
-                                               lo, hi, seed, offset, _stream(cur.device))
-    _lib.check(st, "advstep_hsj_probe_f32")
+    out = _stacked_out(out, ns, cur)
+    _call("advstep_hsj_probe_f32", cur.device, cur, mag, active, out, B, T, s0, ns, lo, hi, seed, offset,
+          bracket="hsj_probe", tensors=(cur, out))
     return out
 
 
@@ -1333,16 +1186,9 @@ def hsj_candidates(cur, z, labels, dist, active, xi_rel: float, trials: int, see
     trials = int(trials)
     if not 0 <= trials <= HSJ_MAX_TRIALS:
         raise ValueError(f"trials must be in 0 .. {HSJ_MAX_TRIALS}, got {trials}")
-    if out is None:
-        out = torch.empty((trials,) + tuple(cur.shape), dtype=torch.float32, device=cur.device)
-    _require(out, "out")
-    if out.numel() != trials * B * T or out.device != cur.device:
-        raise ValueError(f"out must hold ({trials}, {B}, {T}) values on {cur.device}, got {tuple(out.shape)}@{out.device}")
-    with _Launch("hsj_candidates", cur.device, tensors=(cur, out, z)):
-        st = _lib.load().advstep_hsj_candidates_f32(cur.data_ptr(), z.data_ptr(), labels.data_ptr(), dist.data_ptr(),
-                                                    active.data_ptr(), out.data_ptr(), B, T, n, trials, xi_rel, lo, hi, seed,
-                                                    offset, _stream(cur.device))
-    _lib.check(st, "advstep_hsj_candidates_f32")
+    out = _stacked_out(out, trials, cur)
+    _call("advstep_hsj_candidates_f32", cur.device, cur, z, labels, dist, active, out, B, T, n, trials, xi_rel, lo, hi, seed, offset,
+          bracket="hsj_candidates", tensors=(cur, out, z))
     return out
 
 
@@ -1359,10 +1205,8 @@ def hsj_take(cur, cand, zc, labels, active, queries, n: int, out=None):
     if not 0 <= int(n) <= HSJ_MAX_DIRECTIONS:
         raise ValueError(f"n must be in 0 .. {HSJ_MAX_DIRECTIONS}, got {n}")
     out = _out_like(cur, out)
-    with _Launch("hsj_take", cur.device, tensors=(cur, out)):
-        st = _lib.load().advstep_hsj_take_f32(cur.data_ptr(), cand.data_ptr(), zc.data_ptr(), labels.data_ptr(), active.data_ptr(),
-                                              queries.data_ptr(), out.data_ptr(), B, T, int(n), trials, _stream(cur.device))
-    _lib.check(st, "advstep_hsj_take_f32")
+    _call("advstep_hsj_take_f32", cur.device, cur, cand, zc, labels, active, queries, out, B, T, int(n), trials,
+          bracket="hsj_take", tensors=(cur, out))
     return out
 
 
@@ -1389,8 +1233,7 @@ def _channel_params(taps, shift, gain, B: int, device, noise=None) -> Tuple[int,
         if tuple(t.shape) != (K, B):
             raise ValueError(f"{name} must be ({K}, {B}), got {tuple(t.shape)}")
     for name, t in [("taps", taps)] + named:
-        if t.device != device:
-            raise ValueError(f"{name} must live on {device}, got {t.device}")
+        _on_device(t, name, device)
     return K, L
 
 
@@ -1401,20 +1244,11 @@ def channel_apply(x, center, taps, shift, gain, noise, seed: int, offset: int = 
     sample, no host read."""
     _require(x, "x")
     B, T = _rows(x, "x")
-    _per_row(center, "center", B)
-    if center.device != x.device:
-        raise ValueError(f"center must live on {x.device}, got {center.device}")
+    _per_row(center, "center", B, device=x.device)
     K, L = _channel_params(taps, shift, gain, B, x.device, noise)
-    if out is None:
-        out = torch.empty((K,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-    _require(out, "out")
-    if out.numel() != K * B * T or out.device != x.device:
-        raise ValueError(f"out must hold ({K}, {B}, {T}) values on {x.device}, got {tuple(out.shape)}@{out.device}")
-    with _Launch("channel_apply", x.device, work=2.0 * K * L * B * T, tensors=(x, out)):
-        st = _lib.load().advstep_channel_apply_f32(x.data_ptr(), center.data_ptr(), taps.data_ptr(), shift.data_ptr(),
-                                                   gain.data_ptr(), noise.data_ptr(), out.data_ptr(), B, T, K, L, seed, offset,
-                                                   _stream(x.device))
-    _lib.check(st, "advstep_channel_apply_f32")
+    out = _stacked_out(out, K, x)
+    _call("advstep_channel_apply_f32", x.device, x, center, taps, shift, gain, noise, out, B, T, K, L, seed, offset,
+          bracket="channel_apply", work=2.0 * K * L * B * T, tensors=(x, out))
     return out
 
 
@@ -1438,10 +1272,8 @@ def channel_adjoint(grads, taps, shift, gain, out=None):
     if K != grads.shape[0]:
         raise ValueError(f"grads holds {grads.shape[0]} draws, the parameters {K}")
     out = _out_like(like, out)
-    with _Launch("channel_adjoint", grads.device, work=2.0 * K * L * B * T, tensors=(grads, out)):
-        st = _lib.load().advstep_channel_adjoint_f32(grads.data_ptr(), taps.data_ptr(), shift.data_ptr(), gain.data_ptr(),
-                                                     out.data_ptr(), B, T, K, L, _stream(grads.device))
-    _lib.check(st, "advstep_channel_adjoint_f32")
+    _call("advstep_channel_adjoint_f32", grads.device, grads, taps, shift, gain, out, B, T, K, L,
+          bracket="channel_adjoint", work=2.0 * K * L * B * T, tensors=(grads, out))
     return out
 
 
@@ -1456,11 +1288,8 @@ def channel_eot_step(adv, orig, grads, taps, shift, gain, alpha: float, eps: flo
     if K != Kg:
         raise ValueError(f"grads holds {Kg} draws, the parameters {K}")
     out = _out_like(adv, out)
-    with _Launch("channel_eot_step", adv.device, work=2.0 * K * L * B * T, tensors=(adv, orig, grads, out)):
-        st = _lib.load().advstep_channel_eot_step_f32(adv.data_ptr(), orig.data_ptr(), grads.data_ptr(), taps.data_ptr(),
-                                                      shift.data_ptr(), gain.data_ptr(), out.data_ptr(), B, T, K, L, alpha, eps,
-                                                      lo, hi, _stream(adv.device))
-    _lib.check(st, "advstep_channel_eot_step_f32")
+    _call("advstep_channel_eot_step_f32", adv.device, adv, orig, grads, taps, shift, gain, out, B, T, K, L, alpha, eps, lo, hi,
+          bracket="channel_eot_step", work=2.0 * K * L * B * T, tensors=(adv, orig, grads, out))
     return out
 
 
@@ -1491,16 +1320,9 @@ def stft_power(a, b, window, hop: int, out=None):
         _require(b, "b")
         _same_shape(("a", a), ("b", b))
     B, T, NF = _masking_frames(a, window, hop)
-    if out is None:
-        out = torch.empty((B, NF, MASKING_BINS), dtype=torch.float32, device=a.device)
-    else:
-        _require(out, "out")
-        if tuple(out.shape) != (B, NF, MASKING_BINS) or out.device != a.device:
-            raise ValueError(f"out must be {(B, NF, MASKING_BINS)} on {a.device}, got {tuple(out.shape)}@{out.device}")
-    with _Launch("stft_power", a.device, tensors=(a, out) if b is None else (a, b, out)):
-        st = _lib.load().advstep_stft_power_f32(a.data_ptr(), None if b is None else b.data_ptr(), window.data_ptr(),
-                                                out.data_ptr(), B, T, NF, int(hop), MASKING_NFFT, _stream(a.device))
-    _lib.check(st, "advstep_stft_power_f32")
+    out = _shaped(out, "out", (B, NF, MASKING_BINS), a.device)
+    _call("advstep_stft_power_f32", a.device, a, b, window, out, B, T, NF, int(hop), MASKING_NFFT,
+          bracket="stft_power", tensors=(a, out) if b is None else (a, b, out))
     return out
 
 
@@ -1513,21 +1335,11 @@ def masking_hinge_grad(adv, x, window, theta, row_scale, hop: int, out=None, sta
     B, T, NF = _masking_frames(adv, window, hop)
     if tuple(theta.shape) != (B, NF, MASKING_BINS) or theta.device != adv.device:
         raise ValueError(f"theta must be {(B, NF, MASKING_BINS)} on {adv.device}, got {tuple(theta.shape)}@{theta.device}")
-    row_scale = _per_row(row_scale, "row_scale", B)
-    if row_scale.device != adv.device:
-        raise ValueError(f"row_scale lives on {row_scale.device}, adv on {adv.device}")
+    _per_row(row_scale, "row_scale", B, device=adv.device)
     out = _out_like(adv, out)
-    if stats is None:
-        stats = torch.empty((B, 3), dtype=torch.float32, device=adv.device)
-    else:
-        _require(stats, "stats")
-        if tuple(stats.shape) != (B, 3) or stats.device != adv.device:
-            raise ValueError(f"stats must be {(B, 3)} on {adv.device}, got {tuple(stats.shape)}@{stats.device}")
-    with _Launch("masking_hinge_grad", adv.device, tensors=(adv, x, theta, out, out)):
-        st = _lib.load().advstep_masking_hinge_grad_f32(adv.data_ptr(), x.data_ptr(), window.data_ptr(), theta.data_ptr(),
-                                                        row_scale.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, NF,
-                                                        int(hop), MASKING_NFFT, _stream(adv.device))
-    _lib.check(st, "advstep_masking_hinge_grad_f32")
+    stats = _shaped(stats, "stats", (B, 3), adv.device)
+    _call("advstep_masking_hinge_grad_f32", adv.device, adv, x, window, theta, row_scale, out, stats, B, T, NF, int(hop),
+          MASKING_NFFT, bracket="masking_hinge_grad", tensors=(adv, x, theta, out, out))
     return out, stats
 
 
@@ -1547,9 +1359,6 @@ def psy_step(cur, g_ce, g_mask, x, lam: float, step: float, eps: float, out=None
         raise ValueError(f"lam, step and eps must be non-negative, got {lam!r}, {step!r}, {eps!r}")
     B, T = _rows(cur, "cur")
     out = _out_like(cur, out)
-    with _Launch("psy_step", cur.device, tensors=tuple(t for _, t in named) + (out,)):
-        st = _lib.load().advstep_psy_step_f32(cur.data_ptr(), g_ce.data_ptr(), None if g_mask is None else g_mask.data_ptr(),
-                                              x.data_ptr(), float(lam), float(step), float(eps), out.data_ptr(), B, T,
-                                              _stream(cur.device))
-    _lib.check(st, "advstep_psy_step_f32")
+    _call("advstep_psy_step_f32", cur.device, cur, g_ce, g_mask, x, float(lam), float(step), float(eps), out, B, T,
+          bracket="psy_step", tensors=tuple(t for _, t in named) + (out,))
     return out

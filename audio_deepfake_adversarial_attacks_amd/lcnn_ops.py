@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .hip_ops import _Launch, _require, _stream
+from .hip_ops import _Launch, _call, _require
 
 
 def _gemm(fn, a2d: torch.Tensor, b2d: torch.Tensor, *lead):
@@ -39,29 +39,25 @@ def _bias_grad(gx: torch.Tensor, needed: bool):
     return gx.sum(dim=(0, 2, 3)) if needed else None
 
 
-def _bn_ptrs(bn):
+def _bn_pair(bn):
     """bn = (mean (C), invstd (C)) of an eval-mode BatchNorm2d(affine=False) folded into the kernel, or None."""
     if bn is None:
         return None, None
     mean, invstd = bn
-    _require(mean, "bn mean"), _require(invstd, "bn invstd")
-    return mean.data_ptr(), invstd.data_ptr()
+    return _require(mean, "bn mean"), _require(invstd, "bn invstd")
 
 
 class _Mfm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, bn):
         _check_input(x, bias)
-        bn_mean, bn_invstd = _bn_ptrs(bn)
+        bn_mean, bn_invstd = _bn_pair(bn)
         N, C2, H, W = x.shape
         C, HW = C2 // 2, H * W
         y = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device)
-        lib = _lib.load()
-        sel = torch.empty(max(lib.advstep_mfm_sel_bytes(N, C, HW), 1), dtype=torch.uint8, device=x.device)
-        with _Launch("mfm_forward", x.device, tensors=(x, y, sel)):
-            st = lib.advstep_mfm_forward_f32(x.data_ptr(), bias.data_ptr() if bias is not None else None, bn_mean,
-                                             bn_invstd, y.data_ptr(), sel.data_ptr(), N, C, HW, _stream(x.device))
-        _lib.check(st, "advstep_mfm_forward_f32")
+        sel = torch.empty(max(_lib.load().advstep_mfm_sel_bytes(N, C, HW), 1), dtype=torch.uint8, device=x.device)
+        _call("advstep_mfm_forward_f32", x.device, x, bias, bn_mean, bn_invstd, y, sel, N, C, HW,
+              bracket="mfm_forward", tensors=(x, y, sel))
         ctx.save_for_backward(sel, *([bn[1]] if bn is not None else []))
         ctx.shape = (N, C, H, W)
         ctx.has_bias = bias is not None
@@ -73,10 +69,8 @@ class _Mfm(torch.autograd.Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty((N, 2 * C, H, W), dtype=gy.dtype, device=gy.device)
-        with _Launch("mfm_backward", gy.device, tensors=(gy, sel, gx)):
-            st = _lib.load().advstep_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), scale[0].data_ptr() if scale else None,
-                                                      gx.data_ptr(), N, C, H * W, _stream(gy.device))
-        _lib.check(st, "advstep_mfm_backward_f32")
+        _call("advstep_mfm_backward_f32", gy.device, gy, sel, scale[0] if scale else None, gx, N, C, H * W,
+              bracket="mfm_backward", tensors=(gy, sel, gx))
         return gx, _bias_grad(gx, ctx.has_bias and ctx.needs_input_grad[1]), None
 
 
@@ -84,16 +78,13 @@ class _MfmPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, bn):
         _check_input(x, bias)
-        bn_mean, bn_invstd = _bn_ptrs(bn)
+        bn_mean, bn_invstd = _bn_pair(bn)
         N, C2, H, W = x.shape
         C = C2 // 2
         y = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
         idx = torch.empty(max(y.numel(), 2), dtype=torch.uint8, device=x.device)
-        with _Launch("mfm_pool2_forward", x.device, tensors=(x, y, idx)):
-            st = _lib.load().advstep_mfm_pool2_forward_f32(x.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                           bn_mean, bn_invstd, y.data_ptr(), idx.data_ptr(), N, C, H, W,
-                                                           _stream(x.device))
-        _lib.check(st, "advstep_mfm_pool2_forward_f32")
+        _call("advstep_mfm_pool2_forward_f32", x.device, x, bias, bn_mean, bn_invstd, y, idx, N, C, H, W,
+              bracket="mfm_pool2_forward", tensors=(x, y, idx))
         ctx.save_for_backward(idx, *([bn[1]] if bn is not None else []))
         ctx.shape = (N, C, H, W)
         ctx.has_bias = bias is not None
@@ -105,11 +96,8 @@ class _MfmPool2(torch.autograd.Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty((N, 2 * C, H, W), dtype=gy.dtype, device=gy.device)
-        with _Launch("mfm_pool2_backward", gy.device, tensors=(gy, idx, gx)):
-            st = _lib.load().advstep_mfm_pool2_backward_f32(gy.data_ptr(), idx.data_ptr(),
-                                                            scale[0].data_ptr() if scale else None, gx.data_ptr(), N, C, H,
-                                                            W, _stream(gy.device))
-        _lib.check(st, "advstep_mfm_pool2_backward_f32")
+        _call("advstep_mfm_pool2_backward_f32", gy.device, gy, idx, scale[0] if scale else None, gx, N, C, H, W,
+              bracket="mfm_pool2_backward", tensors=(gy, idx, gx))
         return gx, _bias_grad(gx, ctx.has_bias and ctx.needs_input_grad[1]), None
 
 
@@ -129,11 +117,8 @@ class _Conv5MfmPool2(torch.autograd.Function):
         C = weight.shape[0] // 2
         y = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
         idx = torch.empty(max(y.numel(), 1), dtype=torch.uint8, device=x.device)
-        with _Launch("conv5_mfm_pool2_forward", x.device, work=100.0 * N * C * H * W, tensors=(x, y, idx)):
-            st = _lib.load().advstep_conv5_mfm_pool2_forward_f32(
-                x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                idx.data_ptr(), N, C, H, W, _stream(x.device))
-        _lib.check(st, "advstep_conv5_mfm_pool2_forward_f32")
+        _call("advstep_conv5_mfm_pool2_forward_f32", x.device, x, weight, bias, y, idx, N, C, H, W,
+              bracket="conv5_mfm_pool2_forward", work=100.0 * N * C * H * W, tensors=(x, y, idx))
         ctx.save_for_backward(idx, weight)
         ctx.shape = (N, C, H, W)
         return y
@@ -149,10 +134,8 @@ class _Conv5MfmPool2(torch.autograd.Function):
         gx = torch.empty((N, 1, H, W), dtype=gy.dtype, device=gy.device)
         # work = the multiply-adds the gradient needs: 25 taps per pooled output and channel (2 x 25 x N C H/2 W/2) - an eighth of
         # the dense transposed convolution rounds 1-4 priced here, which no kernel of this library executes
-        with _Launch("conv5_mfm_pool2_backward", gy.device, work=12.5 * N * C * H * W, tensors=(gy, idx, gx)):
-            st = _lib.load().advstep_conv5_mfm_pool2_backward_f32(gy.data_ptr(), idx.data_ptr(), weight.data_ptr(),
-                                                                  gx.data_ptr(), N, C, H, W, _stream(gy.device))
-        _lib.check(st, "advstep_conv5_mfm_pool2_backward_f32")
+        _call("advstep_conv5_mfm_pool2_backward_f32", gy.device, gy, idx, weight, gx, N, C, H, W,
+              bracket="conv5_mfm_pool2_backward", work=12.5 * N * C * H * W, tensors=(gy, idx, gx))
         return gx, None, None
 
 
@@ -169,7 +152,7 @@ class _Conv1x1Mfm(torch.autograd.Function):
         _require(x, "x"), _require(weight, "weight")
         if bias is not None:
             _require(bias, "bias")
-        bn_mean, bn_invstd = _bn_ptrs(bn)
+        bn_mean, bn_invstd = _bn_pair(bn)
         if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or weight.shape[1] != x.shape[1] \
                 or weight.shape[0] % 2 != 0 or (bias is not None and bias.numel() != weight.shape[0]):
             raise ValueError(f"expected x (N, Cin, H, W), weight (2C, Cin, 1, 1), bias (2C); got {tuple(x.shape)}, "
@@ -181,11 +164,8 @@ class _Conv1x1Mfm(torch.autograd.Function):
             raise ValueError(f"conv1x1_mfm supports Cin in (32, 48, 64), got {Cin}")
         y = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device)
         sel = torch.empty(max(lib.advstep_conv1x1_mfm_sel_bytes(N, C, P), 4), dtype=torch.uint8, device=x.device)
-        with _Launch("conv1x1_mfm_forward", x.device, work=4.0 * N * Cin * C * P, tensors=(x, y, sel)):
-            st = lib.advstep_conv1x1_mfm_forward_f32(x.data_ptr(), weight.data_ptr(),
-                                                     bias.data_ptr() if bias is not None else None, bn_mean, bn_invstd,
-                                                     y.data_ptr(), sel.data_ptr(), N, Cin, C, P, _stream(x.device))
-        _lib.check(st, "advstep_conv1x1_mfm_forward_f32")
+        _call("advstep_conv1x1_mfm_forward_f32", x.device, x, weight, bias, bn_mean, bn_invstd, y, sel, N, Cin, C, P,
+              bracket="conv1x1_mfm_forward", work=4.0 * N * Cin * C * P, tensors=(x, y, sel))
         ctx.save_for_backward(sel, weight, *([bn[1]] if bn is not None else []))
         ctx.shape = (N, Cin, C, H, W)
         return y
@@ -199,11 +179,8 @@ class _Conv1x1Mfm(torch.autograd.Function):
         N, Cin, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty((N, Cin, H, W), dtype=gy.dtype, device=gy.device)
-        with _Launch("conv1x1_mfm_backward", gy.device, work=4.0 * N * Cin * C * H * W, tensors=(gy, sel, gx)):
-            st = _lib.load().advstep_conv1x1_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), weight.data_ptr(),
-                                                              scale[0].data_ptr() if scale else None, gx.data_ptr(), N, Cin,
-                                                              C, H * W, _stream(gy.device))
-        _lib.check(st, "advstep_conv1x1_mfm_backward_f32")
+        _call("advstep_conv1x1_mfm_backward_f32", gy.device, gy, sel, weight, scale[0] if scale else None, gx, N, Cin, C, H * W,
+              bracket="conv1x1_mfm_backward", work=4.0 * N * Cin * C * H * W, tensors=(gy, sel, gx))
         return gx, None, None, None
 
 
@@ -237,7 +214,7 @@ class _Conv5Conv1x1Mfm(torch.autograd.Function):
         for t, name in ((bias, "bias"), (bias1, "bias1")):
             if t is not None:
                 _require(t, name)
-        bn_mean, bn_invstd = _bn_ptrs(bn)
+        bn_mean, bn_invstd = _bn_pair(bn)
         if x.dim() != 4 or x.shape[1] != 1 or weight.dim() != 4 or tuple(weight.shape[1:]) != (1, 5, 5) \
                 or weight1.dim() != 4 or tuple(weight1.shape[1:]) != (weight.shape[0] // 2, 1, 1) \
                 or (bias is not None and bias.numel() != weight.shape[0]) \
@@ -254,13 +231,9 @@ class _Conv5Conv1x1Mfm(torch.autograd.Function):
         idx = torch.empty(max(N * C * P, 1), dtype=torch.uint8, device=x.device)
         sel = torch.empty(max(lib.advstep_conv1x1_mfm_sel_bytes(N, C1, P), 4), dtype=torch.uint8, device=x.device)
         # priced as both convolutions (the benchmark's family table keeps one first-block row)
-        with _Launch("conv5_mfm_pool2_forward", x.device, work=100.0 * N * C * H * W + 4.0 * N * C * C1 * P,
-                     tensors=(x, y, idx, sel)):
-            st = lib.advstep_conv5_conv1x1_mfm_forward_f32(
-                x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, weight1.data_ptr(),
-                bias1.data_ptr() if bias1 is not None else None, bn_mean, bn_invstd, y.data_ptr(), idx.data_ptr(),
-                sel.data_ptr(), N, C, C1, H, W, _stream(x.device))
-        _lib.check(st, "advstep_conv5_conv1x1_mfm_forward_f32")
+        _call("advstep_conv5_conv1x1_mfm_forward_f32", x.device, x, weight, bias, weight1, bias1, bn_mean, bn_invstd, y, idx, sel,
+              N, C, C1, H, W, bracket="conv5_mfm_pool2_forward", work=100.0 * N * C * H * W + 4.0 * N * C * C1 * P,
+              tensors=(x, y, idx, sel))
         ctx.save_for_backward(idx, sel, weight, weight1, *([bn[1]] if bn is not None else []))
         ctx.shape = (N, C, C1, H, W)
         return y
@@ -278,25 +251,16 @@ class _Conv5Conv1x1Mfm(torch.autograd.Function):
         gx = torch.empty((N, 1, H, W), dtype=gy.dtype, device=gy.device)
         if _block0_pair_bwd_enabled() and lib.advstep_conv5_conv1x1_mfm_backward_supported(C, C1, H, W):
             # one kernel, priced as both gradients
-            with _Launch("conv5_mfm_pool2_backward", gy.device, work=12.5 * N * C * H * W + 4.0 * N * C * C1 * Ho * Wo,
-                         tensors=(gy, sel, idx, gx)):
-                st = lib.advstep_conv5_conv1x1_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), weight1.data_ptr(),
-                                                                scale[0].data_ptr() if scale else None, idx.data_ptr(),
-                                                                weight.data_ptr(), gx.data_ptr(), N, C, C1, H, W,
-                                                                _stream(gy.device))
-            _lib.check(st, "advstep_conv5_conv1x1_mfm_backward_f32")
+            _call("advstep_conv5_conv1x1_mfm_backward_f32", gy.device, gy, sel, weight1, scale[0] if scale else None, idx, weight,
+                  gx, N, C, C1, H, W, bracket="conv5_mfm_pool2_backward",
+                  work=12.5 * N * C * H * W + 4.0 * N * C * C1 * Ho * Wo, tensors=(gy, sel, idx, gx))
             return gx, None, None, None, None, None
         # the two blocks' own backward kernels, through a temporary gradient of the pooled tensor
         gp = torch.empty((N, C, Ho, Wo), dtype=gy.dtype, device=gy.device)
-        with _Launch("conv1x1_mfm_backward", gy.device, work=4.0 * N * C * C1 * Ho * Wo, tensors=(gy, sel, gp)):
-            st = lib.advstep_conv1x1_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), weight1.data_ptr(),
-                                                      scale[0].data_ptr() if scale else None, gp.data_ptr(), N, C, C1,
-                                                      Ho * Wo, _stream(gy.device))
-        _lib.check(st, "advstep_conv1x1_mfm_backward_f32")
-        with _Launch("conv5_mfm_pool2_backward", gy.device, work=12.5 * N * C * H * W, tensors=(gp, idx, gx)):
-            st = lib.advstep_conv5_mfm_pool2_backward_f32(gp.data_ptr(), idx.data_ptr(), weight.data_ptr(), gx.data_ptr(), N,
-                                                          C, H, W, _stream(gy.device))
-        _lib.check(st, "advstep_conv5_mfm_pool2_backward_f32")
+        _call("advstep_conv1x1_mfm_backward_f32", gy.device, gy, sel, weight1, scale[0] if scale else None, gp, N, C, C1, Ho * Wo,
+              bracket="conv1x1_mfm_backward", work=4.0 * N * C * C1 * Ho * Wo, tensors=(gy, sel, gp))
+        _call("advstep_conv5_mfm_pool2_backward_f32", gy.device, gp, idx, weight, gx, N, C, H, W,
+              bracket="conv5_mfm_pool2_backward", work=12.5 * N * C * H * W, tensors=(gp, idx, gx))
         return gx, None, None, None, None, None
 
 
@@ -339,10 +303,7 @@ def _prepared_weights(weight: torch.Tensor, mode: int, gscale: Optional[torch.Te
         Cout, Cin = weight.shape[0], weight.shape[1]
         lib = _lib.load()
         U = torch.empty(lib.advstep_conv3x3_prepared_floats(Cin, Cout, mode), dtype=torch.float32, device=weight.device)
-        with _Launch("conv3x3_prepare", weight.device):
-            st = lib.advstep_conv3x3_prepare_f32(weight.data_ptr(), None if gscale is None else gscale.data_ptr(), U.data_ptr(),
-                                                 Cin, Cout, mode, _stream(weight.device))
-        _lib.check(st, "advstep_conv3x3_prepare_f32")
+        _call("advstep_conv3x3_prepare_f32", weight.device, weight, gscale, U, Cin, Cout, mode, bracket="conv3x3_prepare")
         if len(cache[1]) >= 8:
             cache[1].clear()
         cache[1][slot] = (U, gscale)       # keeps the scale tensor alive: its address is part of the key
@@ -367,18 +328,14 @@ class _Conv3x3MfmPool2(torch.autograd.Function):
             _require(bias, "bias")
         N, Cin, H, W = x.shape
         C = weight.shape[0] // 2
-        bn_mean, bn_invstd = _bn_ptrs(bn)
+        bn_mean, bn_invstd = _bn_pair(bn)
         y = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
         idx = torch.empty(max(y.numel(), 2), dtype=torch.uint8, device=x.device)
-        lib = _lib.load()
         per_out = C * (H // 2) * (W // 2)
         for lo, hi in _batch_chunks(N, max(Cin * H * W, 1)):
-            with _Launch("conv3x3_mfm_pool2_forward", x.device, work=16.0 * (hi - lo) * C * Cin * H * W):
-                st = lib.advstep_conv3x3_mfm_pool2_forward_f32(
-                    x[lo:hi].data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None, bn_mean, bn_invstd,
-                    y[lo:hi].data_ptr() if hi > lo else None, idx.data_ptr() + lo * per_out, hi - lo, Cin, C, H, W,
-                    _stream(x.device))
-            _lib.check(st, "advstep_conv3x3_mfm_pool2_forward_f32")
+            _call("advstep_conv3x3_mfm_pool2_forward_f32", x.device, x[lo:hi], U, bias, bn_mean, bn_invstd,
+                  y[lo:hi] if hi > lo else None, idx.data_ptr() + lo * per_out, hi - lo, Cin, C, H, W,
+                  bracket="conv3x3_mfm_pool2_forward", work=16.0 * (hi - lo) * C * Cin * H * W)
         ctx.save_for_backward(idx, U_grad)
         ctx.shape = (N, Cin, C, H, W)
         return y
@@ -388,17 +345,13 @@ class _Conv3x3MfmPool2(torch.autograd.Function):
         idx, U = ctx.saved_tensors
         N, Cin, C, H, W = ctx.shape
         gy = gy.contiguous()
-        lib = _lib.load()
         # d(conv out) — gy routed to the winning position of the winning half — is expanded inside the kernel's operand
         # load; the BatchNorm scale is folded into the prepared weights
         gx = torch.empty((N, Cin, H, W), dtype=gy.dtype, device=gy.device)
         per_cell = C * (H // 2) * (W // 2)
         for lo, hi in _batch_chunks(N, max(4 * per_cell, Cin * H * W, 1)):
-            with _Launch("conv3x3_mfm_pool2_backward", gy.device, work=16.0 * (hi - lo) * C * Cin * H * W):
-                st = lib.advstep_conv3x3_mfm_pool2_backward_f32(gy[lo:hi].data_ptr(), idx.data_ptr() + lo * per_cell,
-                                                                U.data_ptr(), gx[lo:hi].data_ptr(), hi - lo, Cin, C, H, W,
-                                                                _stream(gy.device))
-            _lib.check(st, "advstep_conv3x3_mfm_pool2_backward_f32")
+            _call("advstep_conv3x3_mfm_pool2_backward_f32", gy.device, gy[lo:hi], idx.data_ptr() + lo * per_cell, U, gx[lo:hi],
+                  hi - lo, Cin, C, H, W, bracket="conv3x3_mfm_pool2_backward", work=16.0 * (hi - lo) * C * Cin * H * W)
         return gx, None, None, None, None, None
 
 
@@ -412,17 +365,14 @@ class _Conv3x3Mfm(torch.autograd.Function):
             _require(bias, "bias")
         N, Cin, H, W = x.shape
         C = weight.shape[0] // 2
-        bn_mean, bn_invstd = _bn_ptrs(bn)
-        lib = _lib.load()
+        bn_mean, bn_invstd = _bn_pair(bn)
         y = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device)
         per_sel = C * ((H + 1) // 2) * ((W + 1) // 2)
         sel = torch.empty(max(N * per_sel, 1), dtype=torch.uint8, device=x.device)
         for lo, hi in _batch_chunks(N, max(Cin * H * W, 1)):
-            with _Launch("conv3x3_mfm_forward", x.device, work=16.0 * (hi - lo) * C * Cin * H * W):
-                st = lib.advstep_conv3x3_mfm_forward_f32(
-                    x[lo:hi].data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None, bn_mean, bn_invstd,
-                    y[lo:hi].data_ptr(), sel.data_ptr() + lo * per_sel, hi - lo, Cin, C, H, W, _stream(x.device))
-            _lib.check(st, "advstep_conv3x3_mfm_forward_f32")
+            _call("advstep_conv3x3_mfm_forward_f32", x.device, x[lo:hi], U, bias, bn_mean, bn_invstd, y[lo:hi],
+                  sel.data_ptr() + lo * per_sel, hi - lo, Cin, C, H, W,
+                  bracket="conv3x3_mfm_forward", work=16.0 * (hi - lo) * C * Cin * H * W)
         ctx.save_for_backward(sel, U_grad, *([bn[1]] if bn is not None else []))
         ctx.shape = (N, Cin, C, H, W)
         return y
@@ -432,18 +382,13 @@ class _Conv3x3Mfm(torch.autograd.Function):
         sel, U, *scale = ctx.saved_tensors
         N, Cin, C, H, W = ctx.shape
         gy = gy.contiguous()
-        lib = _lib.load()
         gconv = torch.empty((N, 2 * C, H, W), dtype=gy.dtype, device=gy.device)
-        with _Launch("conv3x3_mfm_backward", gy.device, tensors=(gy, sel, gconv)):
-            st = lib.advstep_conv3x3_mfm_backward_f32(gy.data_ptr(), sel.data_ptr(), scale[0].data_ptr() if scale else None,
-                                                      gconv.data_ptr(), N, C, H, W, _stream(gy.device))
-        _lib.check(st, "advstep_conv3x3_mfm_backward_f32")
+        _call("advstep_conv3x3_mfm_backward_f32", gy.device, gy, sel, scale[0] if scale else None, gconv, N, C, H, W,
+              bracket="conv3x3_mfm_backward", tensors=(gy, sel, gconv))
         gx = torch.empty((N, Cin, H, W), dtype=gy.dtype, device=gy.device)
         for lo, hi in _batch_chunks(N, max(2 * C * H * W, 1)):
-            with _Launch("conv3x3_backward_data", gy.device, work=16.0 * (hi - lo) * C * Cin * H * W):
-                st = lib.advstep_conv3x3_backward_data_f32(gconv[lo:hi].data_ptr(), U.data_ptr(), gx[lo:hi].data_ptr(), hi - lo,
-                                                           Cin, 2 * C, H, W, _stream(gy.device))
-            _lib.check(st, "advstep_conv3x3_backward_data_f32")
+            _call("advstep_conv3x3_backward_data_f32", gy.device, gconv[lo:hi], U, gx[lo:hi], hi - lo, Cin, 2 * C, H, W,
+                  bracket="conv3x3_backward_data", work=16.0 * (hi - lo) * C * Cin * H * W)
         return gx, None, None, None, None, None
 
 
@@ -480,10 +425,8 @@ class _LstmLayer(torch.autograd.Function):
         out = torch.empty((T, B, D * H), dtype=x.dtype, device=x.device)
         gates = torch.empty((T, B, D, H4), dtype=x.dtype, device=x.device)
         cell = torch.empty((T, B, D, H), dtype=x.dtype, device=x.device)
-        with _Launch("lstm_forward", x.device, tensors=(gx, out, gates, cell)):
-            st = _lib.load().advstep_lstm_forward_f32(gx.data_ptr(), w_hh.data_ptr(), out.data_ptr(), gates.data_ptr(),
-                                                      cell.data_ptr(), T, B, D, H, _stream(x.device))
-        _lib.check(st, "advstep_lstm_forward_f32")
+        _call("advstep_lstm_forward_f32", x.device, gx, w_hh, out, gates, cell, T, B, D, H,
+              bracket="lstm_forward", tensors=(gx, out, gates, cell))
         ctx.save_for_backward(gates, cell, w_hh, w_ih)
         ctx.dims = (T, B, I, D, H)
         return out
@@ -497,10 +440,8 @@ class _LstmLayer(torch.autograd.Function):
         T, B, I, D, H = ctx.dims
         dout = dout.contiguous()
         dgx = torch.empty((T, B, D, 4 * H), dtype=dout.dtype, device=dout.device)
-        with _Launch("lstm_backward", dout.device, tensors=(dout, gates, cell, dgx)):
-            st = _lib.load().advstep_lstm_backward_f32(dout.data_ptr(), w_hh.data_ptr(), gates.data_ptr(),
-                                                       cell.data_ptr(), dgx.data_ptr(), T, B, D, H, _stream(dout.device))
-        _lib.check(st, "advstep_lstm_backward_f32")
+        _call("advstep_lstm_backward_f32", dout.device, dout, w_hh, gates, cell, dgx, T, B, D, H,
+              bracket="lstm_backward", tensors=(dout, gates, cell, dgx))
         dx = _gemm(torch.mm, dgx.view(T * B, D * 4 * H), w_ih).view(T, B, I)
         return dx, None, None, None
 
@@ -543,31 +484,24 @@ class _LcnnTail(torch.autograd.Function):
         B, C, T, W = x4.shape
         F = C * W
         D, H4, H = w_hh1.shape
-        lib, dev = _lib.load(), x4.device
-        st = _stream(dev)
+        dev = x4.device
 
         def layer(xin, w_ih, w_hh, bias):
             gx = _gemm(torch.addmm, xin.view(T * B, -1), w_ih.t(), bias)
             out = torch.empty((T, B, D * H), dtype=x4.dtype, device=dev)
             gates = torch.empty((T, B, D, H4), dtype=x4.dtype, device=dev)
             cell = torch.empty((T, B, D, H), dtype=x4.dtype, device=dev)
-            with _Launch("lstm_forward", dev, tensors=(gx, out, gates, cell)):
-                s_ = lib.advstep_lstm_forward_f32(gx.data_ptr(), w_hh.data_ptr(), out.data_ptr(), gates.data_ptr(), cell.data_ptr(),
-                                                  T, B, D, H, st)
-            _lib.check(s_, "advstep_lstm_forward_f32")
+            _call("advstep_lstm_forward_f32", dev, gx, w_hh, out, gates, cell, T, B, D, H,
+                  bracket="lstm_forward", tensors=(gx, out, gates, cell))
             return out, gates, cell
 
         xt = torch.empty((T, B, F), dtype=x4.dtype, device=dev)
-        with _Launch("lcnn_tail_pack", dev, tensors=(x4, xt)):
-            s_ = lib.advstep_lcnn_tail_pack_f32(x4.data_ptr(), xt.data_ptr(), B, C, T, W, st)
-        _lib.check(s_, "advstep_lcnn_tail_pack_f32")
+        _call("advstep_lcnn_tail_pack_f32", dev, x4, xt, B, C, T, W, bracket="lcnn_tail_pack", tensors=(x4, xt))
         out1, gates1, cell1 = layer(xt, w_ih1, w_hh1, b1)
         out2, gates2, cell2 = layer(out1, w_ih2, w_hh2, b2)
         z = torch.empty((B, 1), dtype=x4.dtype, device=dev)
-        with _Launch("lcnn_tail_forward", dev, tensors=(out2, xt)):
-            s_ = lib.advstep_lcnn_tail_forward_f32(out2.data_ptr(), xt.data_ptr(), w_out.data_ptr(),
-                                                   b_out.data_ptr() if b_out is not None else None, z.data_ptr(), T, B, F, st)
-        _lib.check(s_, "advstep_lcnn_tail_forward_f32")
+        _call("advstep_lcnn_tail_forward_f32", dev, out2, xt, w_out, b_out, z, T, B, F,
+              bracket="lcnn_tail_forward", tensors=(out2, xt))
         # w / T for the mean's gradient row: one launch per weight version, not per call.  Kept in a module-level weak table
         # (an attribute on the Parameter would be pickled by torch.save(model))
         cache = _OVER_T.get(w_out)
@@ -586,28 +520,21 @@ class _LcnnTail(torch.autograd.Function):
         gates1, cell1, gates2, cell2, w_ih1, w_hh1, w_ih2, w_hh2, w_over_t = ctx.saved_tensors
         B, C, T, W, D, H = ctx.dims
         F = C * W
-        lib, dev = _lib.load(), dz.device
-        st = _stream(dev)
+        dev = dz.device
         # the mean's gradient dz[b] * (w / T)[f]: the same row for every frame — of the second layer's output and of the skip
         # connection — formed inside the two kernels that read it (one elementwise launch less)
         dzc = dz.reshape(B).contiguous()
         dgx2 = torch.empty((T, B, D, 4 * H), dtype=dz.dtype, device=dev)
-        with _Launch("lstm_backward", dev, tensors=(gates2, cell2, dgx2)):
-            s_ = lib.advstep_lstm_backward_outer_f32(dzc.data_ptr(), w_over_t.data_ptr(), w_hh2.data_ptr(), gates2.data_ptr(),
-                                                     cell2.data_ptr(), dgx2.data_ptr(), T, B, D, H, st)
-        _lib.check(s_, "advstep_lstm_backward_outer_f32")
+        _call("advstep_lstm_backward_outer_f32", dev, dzc, w_over_t, w_hh2, gates2, cell2, dgx2, T, B, D, H,
+              bracket="lstm_backward", tensors=(gates2, cell2, dgx2))
         dout1 = _gemm(torch.mm, dgx2.view(T * B, D * 4 * H), w_ih2)                     # (T B, F) = d(first layer's output)
         dgx1 = torch.empty((T, B, D, 4 * H), dtype=dz.dtype, device=dev)
-        with _Launch("lstm_backward", dev, tensors=(dout1, gates1, cell1, dgx1)):
-            s_ = lib.advstep_lstm_backward_f32(dout1.data_ptr(), w_hh1.data_ptr(), gates1.data_ptr(), cell1.data_ptr(),
-                                               dgx1.data_ptr(), T, B, D, H, st)
-        _lib.check(s_, "advstep_lstm_backward_f32")
+        _call("advstep_lstm_backward_f32", dev, dout1, w_hh1, gates1, cell1, dgx1, T, B, D, H,
+              bracket="lstm_backward", tensors=(dout1, gates1, cell1, dgx1))
         dxt = _gemm(torch.mm, dgx1.view(T * B, D * 4 * H), w_ih1)
         dx4 = torch.empty((B, C, T, W), dtype=dz.dtype, device=dev)
-        with _Launch("lcnn_tail_unpack_add", dev, tensors=(dxt, dx4)):
-            s_ = lib.advstep_lcnn_tail_unpack_add_outer_f32(dxt.data_ptr(), dzc.data_ptr(), w_over_t.data_ptr(), dx4.data_ptr(), B, C,
-                                                            T, W, st)
-        _lib.check(s_, "advstep_lcnn_tail_unpack_add_outer_f32")
+        _call("advstep_lcnn_tail_unpack_add_outer_f32", dev, dxt, dzc, w_over_t, dx4, B, C, T, W,
+              bracket="lcnn_tail_unpack_add", tensors=(dxt, dx4))
         return (dx4,) + (None,) * 8
 
 
@@ -637,10 +564,8 @@ class _GruLayer(torch.autograd.Function):
         gx = _gemm(torch.addmm, x.reshape(T * B, I), w_ih.t(), b_ih)   # one GEMM for all steps and directions
         out = torch.empty((T, B, D * H), dtype=x.dtype, device=x.device)
         saved = torch.empty((T, B, D, 4 * H), dtype=x.dtype, device=x.device)
-        with _Launch("gru_forward", x.device, tensors=(gx, out, saved)):
-            st = _lib.load().advstep_gru_forward_f32(gx.data_ptr(), w_hh.data_ptr(), b_hh.data_ptr(), out.data_ptr(),
-                                                     saved.data_ptr(), T, B, D, H, _stream(x.device))
-        _lib.check(st, "advstep_gru_forward_f32")
+        _call("advstep_gru_forward_f32", x.device, gx, w_hh, b_hh, out, saved, T, B, D, H,
+              bracket="gru_forward", tensors=(gx, out, saved))
         ctx.save_for_backward(saved, out, w_hh, w_ih)
         ctx.dims = (T, B, I, D, H)
         return out
@@ -654,10 +579,8 @@ class _GruLayer(torch.autograd.Function):
         T, B, I, D, H = ctx.dims
         dout = dout.contiguous()
         dgx = torch.empty((T, B, D, 3 * H), dtype=dout.dtype, device=dout.device)
-        with _Launch("gru_backward", dout.device, tensors=(dout, saved, out, dgx)):
-            st = _lib.load().advstep_gru_backward_f32(dout.data_ptr(), w_hh.data_ptr(), saved.data_ptr(), out.data_ptr(),
-                                                      dgx.data_ptr(), T, B, D, H, _stream(dout.device))
-        _lib.check(st, "advstep_gru_backward_f32")
+        _call("advstep_gru_backward_f32", dout.device, dout, w_hh, saved, out, dgx, T, B, D, H,
+              bracket="gru_backward", tensors=(dout, saved, out, dgx))
         dx = _gemm(torch.mm, dgx.view(T * B, D * 3 * H), w_ih).view(T, B, I)
         return dx, None, None, None, None
 
