@@ -13,21 +13,17 @@ log line.  What is different is how the work is placed on the machine:
     :261-265); one D2H copy per run;
   * the final aggregate is the only communication: an all-reduce(SUM) of the two counters and one all-gather of
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
-    (a MultiAttack adds one all-reduce of its (n_members + 1) per-member survivor counts; `perturbation_stats=True` one
-    all-gather of the six per-utterance perturbation planes; an attack that carries `last_radius` — MinRadiusPGD, HopSkipJump —
-    one all-gather of the per-utterance radii; an attack that carries `last_queries` — SPSA, HopSkipJump — one of the
-    per-utterance queries;
-    an attack that carries `last_changed` — PGDL0 — one of the per-utterance changed-sample counts;
-    an attack that carries `last_masking` — PsyPGD — or `masking_stats=True` one of the per-utterance (3,) masking statistics;
-    `channel=` one all-reduce of its five counters).
-    A universal attack (`is_universal`: torchattacks.UniversalPGD) is fitted by ONE process before the loop, or loaded from a
-    file by every rank: no communication either way.
+    Every optional report of the run (`_active_reports`) adds at most one exchange of its own behind them, in the reports'
+    order: a per-utterance report (`_RowReport`) one all-gather of its rows, a MultiAttack one all-reduce of its survivor
+    counts, `channel=` one all-reduce of its five counters, a universal attack none.
 """
 from __future__ import annotations
 
 import logging
 import contextlib
+import functools
 import os
+from types import SimpleNamespace
 from typing import Any, Callable, Dict, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
@@ -144,39 +140,74 @@ def format_report(report: Dict[str, float]) -> str:
     return ", ".join(f"adv_eval/{k}: {report['adv_eval/' + k]:.4f}" for k in order)
 
 
-def format_perturbation(report: Dict[str, float]) -> str:
-    """The second log line of a `perturbation_stats=True` run: the summary over all utterances (metrics.perturbation_summary)."""
-    keys = [k for k in report if k.startswith("perturbation/") and not k.startswith("perturbation/misclassified/")]
-    return ", ".join(f"{k}: {report[k]}" if k.endswith("nan_rows") else f"{k}: {report[k]:.4g}" for k in keys)
+def format_keys(report: Dict[str, float], prefix: str, integer_suffixes=(), float_spec: str = ".4g", exclude: Optional[str] = None) -> str:
+    """The log line of one optional report: the report's `prefix/` keys in their order (without those under `exclude`), a value
+    whose key ends in one of `integer_suffixes` as it is (a count), every other one with `float_spec`."""
+    keys = [k for k in report if k.startswith(prefix + "/") and not (exclude and k.startswith(exclude))]
+    return ", ".join(f"{k}: {report[k]}" if k.endswith(integer_suffixes) else f"{k}: {report[k]:{float_spec}}" for k in keys)
 
 
-def format_min_radius(report: Dict[str, float]) -> str:
-    """The log line of a run whose attack carries `last_radius` (MinRadiusPGD): the summary of metrics.radius_summary."""
-    return ", ".join(f"{k}: {v:.4g}" for k, v in report.items() if k.startswith("min_radius/"))
+# the public names of the optional reports' log lines (metrics.*_summary says what the keys mean)
+format_perturbation = functools.partial(format_keys, prefix="perturbation", integer_suffixes="nan_rows",
+                                        exclude="perturbation/misclassified/")
+format_min_radius = functools.partial(format_keys, prefix="min_radius")
+format_universal = functools.partial(format_keys, prefix="universal", integer_suffixes="_utterances")
+format_blackbox = functools.partial(format_keys, prefix="blackbox", integer_suffixes="budget")
+format_sparse = functools.partial(format_keys, prefix="sparse", integer_suffixes=("_max", "/k"))
+format_masking = functools.partial(format_keys, prefix="masking")
+format_channel = functools.partial(format_keys, prefix="channel", integer_suffixes=("draws", "flipped"), float_spec=".4f")
 
 
-def format_universal(report: Dict[str, float]) -> str:
-    """The log line of a run whose attack is universal (torchattacks.UniversalPGD): the summary of metrics.universal_summary."""
-    return ", ".join(f"{k}: {v}" if k.endswith("_utterances") else f"{k}: {v:.4g}" for k, v in report.items()
-                     if k.startswith("universal/"))
+# ---------------------------------------------------------------------------------------------------------
+# optional reports
+# ---------------------------------------------------------------------------------------------------------
+
+class _Report:
+    """One optional report of a run; everything the loop does for it is here.  `generate_attacks` asks `_active_reports` once
+    which ones a run has and from then on only walks that list, in the order of the report's keys and of the log lines:
+      batch(atk, clean, attacked)    after the attack (or the copy of a run without one), under the lane's stream, on the loop's
+                                     waveform-domain tensors; returns the tensors it produced there, which the loop hands to
+                                     `lanes.keep`: the caller's stream reads them after join()
+      scored(lane, model, ...)       after the detector has scored the attacked batch; returns the same
+      finish(ctx)                    after the lanes have joined: the report's keys, in order, and whatever it communicates.  `ctx`:
+                                     all_y, all_label (the whole job's numpy arrays), samples (of an utterance), rank, world, device
+      scores()                       after finish: its entries of report["scores"] (`return_scores`)
+      line(report)                   its log line; `leads`: ahead of the reference's line, not behind it"""
+    leads = False
+
+    def batch(self, atk, clean, attacked):
+        return ()
+
+    def scored(self, lane, model, clean, attacked, labels, attacked_label, post):
+        return ()
+
+    def scores(self) -> Dict[str, Any]:
+        return {}
 
 
-def format_blackbox(report: Dict[str, float]) -> str:
-    """The log line of a run whose attack carries `last_queries` (torchattacks.SPSA): the summary of metrics.query_summary."""
-    return ", ".join(f"{k}: {v}" if k.endswith("budget") else f"{k}: {v:.4g}" for k, v in report.items()
-                     if k.startswith("blackbox/"))
+class _RowReport(_Report):
+    """A per-utterance report.  `source(atk, clean, attacked)` gives a batch's rows, (B,) or (B, width) on the device, without a
+    host read; at the end ONE all-gather brings the job's rows to the host, in utterance order like `y_pred` and as `dtype`
+    (`names`: as a dict of the named columns), `summary(rows, ctx)` turns them into the report's keys, `scores()` returns them
+    under `key` and `line` is the report's `format_*`."""
 
+    def __init__(self, key: str, source, dtype, summary, line, width: int = 1, names=None):
+        self.key, self.source, self.dtype, self.summary, self.line, self.width, self.names = key, source, dtype, summary, line, width, names
+        self.parts: List[torch.Tensor] = []
 
-def format_sparse(report: Dict[str, float]) -> str:
-    """The log line of a run whose attack carries `last_changed` (torchattacks.PGDL0): the summary of metrics.sparsity_summary."""
-    return ", ".join(f"{k}: {v}" if k.endswith(("_max", "/k")) else f"{k}: {v:.4g}" for k, v in report.items()
-                     if k.startswith("sparse/"))
+    def batch(self, atk, clean, attacked):
+        self.parts.append(self.source(atk, clean, attacked))
+        return self.parts[-1:]
 
+    def finish(self, ctx):
+        rows = gather_rows_across_ranks(torch.cat(self.parts).reshape(-1, self.width))
+        self.rows = np.ascontiguousarray(rows[:, 0] if self.width == 1 else rows, dtype=self.dtype)
+        if self.names:
+            self.rows = {name: np.ascontiguousarray(self.rows[:, k]) for k, name in enumerate(self.names)}
+        return self.summary(self.rows, ctx)
 
-def format_masking(report: Dict[str, float]) -> str:
-    """The log line of a run with masking statistics (torchattacks.PsyPGD's `last_masking`, or `masking_stats=True`): the
-    summary of metrics.masking_summary."""
-    return ", ".join(f"{k}: {v:.4g}" for k, v in report.items() if k.startswith("masking/"))
+    def scores(self):
+        return {self.key: self.rows}
 
 
 def masking_pass(masking, batch_x: torch.Tensor, batch_x_attacked: torch.Tensor) -> torch.Tensor:
@@ -193,20 +224,68 @@ def masking_pass(masking, batch_x: torch.Tensor, batch_x_attacked: torch.Tensor)
     return hip_ops.masking_hinge_grad(adv01, x01, masking.window(x.device), theta, scale, masking.hop)[1]
 
 
-def format_channel(report: Dict[str, float]) -> str:
-    """The log line of a `channel=` run: what is left of the attack after the simulated channel."""
-    return ", ".join(f"{k}: {v}" if k.endswith(("draws", "flipped")) else f"{k}: {v:.4f}" for k, v in report.items()
-                     if k.startswith("channel/"))
+class _UniversalReport(_Report):
+    """A universal attack (`is_universal`: torchattacks.UniversalPGD) gets its perturbation BEFORE the loop (`prepare_universal`,
+    when this object is made: on the caller's stream, before the lanes exist): loaded from `load`, or fitted on the first `fit`
+    batches of this run's batch order (None: a quarter of them, at least 1), which are kept on the device meanwhile
+    (fit x B x T x 4 bytes); `save` writes it.  The loop then runs over ALL batches with the frozen perturbation, one launch per
+    batch.  More than one rank needs `load`; no communication either way.  Adds the `universal/*` keys of
+    `metrics.universal_summary` (fitted against held-out utterances) and `scores["universal_delta"]`."""
+
+    line = staticmethod(format_universal)
+
+    def __init__(self, atk, loader, device, n_batches: int, fit, load, save):
+        self.atk = atk
+        self.fitted_rows = prepare_universal(atk, loader, device, n_batches, fit, load, save)
+
+    def finish(self, ctx):
+        self.delta = self.atk.delta.detach().cpu().numpy()
+        # rank order = utterance order for the one process that fits; a loaded perturbation was fitted on none of them
+        return metrics.universal_summary(ctx.all_y, ctx.all_label, np.arange(len(ctx.all_y)) < self.fitted_rows, self.delta,
+                                         self.atk.source_label)
+
+    def scores(self):
+        return {"universal_delta": self.delta}
 
 
-class _ChannelScorer:
-    """What survives a simulated channel (torchattacks.Channel), counted on the device.  Per batch: N draws of the channel, the
+class _MultiAttackReport(_Report):
+    """A MultiAttack reports the utterances left after every member as well (multiattack.py's `save` mechanism: accumulate the
+    records of every call): `multi_attack/remaining`, summed over the ranks by one all-reduce of (n_members + 1) int64, and the
+    MultiAttack's own record line, ahead of the reference's."""
+
+    leads = True
+
+    def __init__(self, atk):
+        self.atk = atk
+        atk._start_multi_atk_records()
+
+    def finish(self, ctx):
+        remaining = torch.tensor([int(r) for r in self.atk._multi_atk_records], dtype=torch.int64, device=ctx.device)
+        self.atk._clear_multi_atk_records()
+        self.atk._accumulate_multi_atk_records = False
+        if ctx.world > 1:
+            dist.all_reduce(remaining, op=dist.ReduceOp.SUM)
+        return {"multi_attack/remaining": remaining.tolist()}
+
+    def line(self, report):
+        return self.atk._return_sr_record(report["multi_attack/remaining"])
+
+
+class _ChannelScorer(_Report):
+    """`channel=` (a torchattacks.Channel or the name of a preset in torchattacks.CHANNELS): what is left of the attack — any
+    attack, or none — after a simulated audio channel, counted on the device.  Per batch: N draws of the channel, the
     SAME draws and noise for the attacked and the clean waveform (a paired comparison), in the waveform's domain (centre 0); the
     detector scores each draw's B rows under no_grad, like every other forward of the loop.  Five counters: (utterance, draw)
     pairs, attacked pairs judged right, clean pairs judged right, pairs of utterances the attack flipped without the channel
     (clean judged right, attacked judged wrong, both unchannelled), and those of them still judged wrong through it.
     The draws and the noise seeds come from generators of the scorer's own (seeded with `seed`), so the attack sees the random
-    numbers it would see in a run without `channel=`."""
+    numbers it would see in a run without `channel=`.  Adds `channel/accuracy` (per cent, over all pairs, like
+    adv_eval/accuracy), `channel/clean_accuracy`, `channel/survival` (the share of pairs still misclassified among the utterances
+    the attack flipped without the channel; 0 when it flipped none: `channel/flipped` says how many) and, over several ranks,
+    one all-reduce of the five counters.  `adv_eval/*` and every other key are computed exactly as without it, from the
+    unchannelled waveform."""
+
+    line = staticmethod(format_channel)
 
     def __init__(self, channel, draws: int, device, seed: int = 0):
         from . import hip_ops
@@ -220,7 +299,7 @@ class _ChannelScorer:
         self.pairs = 0                                  # counted on the host: B per draw
         self.counters: Dict[int, torch.Tensor] = {}     # lane -> the other four, int64 on the device
 
-    def batch(self, lane: int, model, clean, attacked, labels, attacked_label, post=None) -> None:
+    def scored(self, lane, model, clean, attacked, labels, attacked_label, post):
         """`post`: the loop's preprocessing between the waveform and the detector (raw_sample_from_dataset), or None."""
         ops, N = self.ops, self.draws
         c = self.counters.setdefault(lane, torch.zeros(4, dtype=torch.int64, device=self.device))
@@ -236,18 +315,70 @@ class _ChannelScorer:
             adv_right, clean_right = score(through_adv[j]) == y, score(through_clean[j]) == y
             c += torch.stack([adv_right.sum(), clean_right.sum(), flipped.sum(), (flipped & ~adv_right).sum()])
         self.pairs += N * y.numel()
+        return ()                                       # the counters live as long as the scorer
 
-    def report(self) -> Dict[str, float]:
-        """After the lanes have joined.  Accuracies in per cent, like adv_eval/accuracy; survival is a share."""
+    def finish(self, ctx):
         total = torch.stack(list(self.counters.values())).sum(dim=0)
         total = torch.cat([torch.tensor([self.pairs], dtype=torch.int64, device=total.device), total])
-        if rank_and_world()[1] > 1:
+        if ctx.world > 1:
             dist.all_reduce(total, op=dist.ReduceOp.SUM)
         pairs, adv_right, clean_right, flipped, still = (int(v) for v in total.cpu().tolist())
         return {"channel/accuracy": (adv_right / pairs) * 100, "channel/clean_accuracy": (clean_right / pairs) * 100,
                 "channel/survival": still / flipped if flipped else 0.0, "channel/flipped": flipped // self.draws,
                 "channel/draws": self.draws}
 
+
+def _active_reports(atk, device, seed: int, loader, n_batches: int, perturbation_stats: bool, masking_stats: bool, channel,
+                    channel_draws: int, universal_fit, universal_load, universal_save) -> List[_Report]:
+    """The optional reports of a run, in the order of their keys and log lines; the one place that names them.  An attack-borne
+    report is active when the attack HAS the attribute before its first call (None until then).  A run with every keyword off
+    and an attack that carries nothing gets an empty list: the loop does nothing for them."""
+    from .torchattacks import MaskingModel, MultiAttack
+
+    def carries(name):
+        return atk is not None and hasattr(atk, name)
+
+    reports: List[_Report] = []
+    if perturbation_stats:
+        # one more row pass per batch over the batch and what the detector is given after `revert_minmax`, so the min-max round
+        # trip's rounding of samples the attack did not move is part of the figure; six (B,) planes
+        from . import hip_ops
+        reports.append(_RowReport("perturbation", lambda atk, clean, attacked: hip_ops.perturbation_stats(clean, attacked).t(),
+                                  np.float32, lambda planes, ctx: metrics.perturbation_summary(planes, ctx.all_label != ctx.all_y),
+                                  format_perturbation, width=len(metrics.PERTURBATION_PLANES), names=metrics.PERTURBATION_PLANES))
+    if carries("last_radius"):      # MinRadiusPGD: each utterance's minimal radius; HopSkipJump: the one a label-only attacker reached
+        reports.append(_RowReport("min_radius", lambda atk, clean, attacked: atk.last_radius, np.float32,
+                                  lambda rows, ctx: metrics.radius_summary(rows, getattr(atk, "report_at", ())), format_min_radius))
+    if carries("last_queries"):     # SPSA, HopSkipJump: the model queries each utterance spent, against the attack's budget
+        reports.append(_RowReport("queries", lambda atk, clean, attacked: atk.last_queries, np.int32,
+                                  lambda rows, ctx: metrics.query_summary(rows, atk.budget), format_blackbox))
+    if carries("last_changed"):     # PGDL0: the samples of each utterance it changed, against the attack's k
+        reports.append(_RowReport("changed", lambda atk, clean, attacked: atk.last_changed, np.int64,
+                                  lambda rows, ctx: metrics.sparsity_summary(rows, atk.k), format_sparse))
+    if masking_stats or carries("last_masking"):
+        # PsyPGD: the (B, 3) masking statistics of the rows it returned.  `masking_stats`: those of ANY attack, or none, and in
+        # place of the attack's own: `masking_pass` rates the batch against the clean utterance's masking threshold (hop 128 or
+        # the attack's own) in the attack's domain, one threshold and one launch per batch.  257 cells per frame
+        masking = getattr(atk, "masking", None) or MaskingModel()
+        reports.append(_RowReport("masking", (lambda atk, clean, attacked: masking_pass(masking, clean, attacked)) if masking_stats
+                                  else (lambda atk, clean, attacked: atk.last_masking), np.float32,
+                                  lambda rows, ctx: metrics.masking_summary(rows, masking.frames(ctx.samples) * 257),
+                                  format_masking, width=3))
+    if getattr(atk, "is_universal", False):
+        reports.append(_UniversalReport(atk, loader, device, n_batches, universal_fit, universal_load, universal_save))
+    elif universal_fit is not None or universal_load is not None or universal_save is not None:
+        raise ValueError("universal_fit / universal_load / universal_save need a universal attack (AttackEnum UAP*)")
+    if isinstance(atk, MultiAttack):
+        reports.append(_MultiAttackReport(atk))
+    if channel is not None:
+        reports.append(_ChannelScorer(channel, channel_draws, device, seed))
+    return reports
+
+
+def _log_report(report: Dict[str, float], reports: List[_Report]) -> None:
+    for line in ([r.line(report) for r in reports if r.leads] + [format_report(report)]
+                 + [r.line(report) for r in reports if not r.leads]):
+        LOGGER.info(line)
 
 # ---------------------------------------------------------------------------------------------------------
 # the loop
@@ -476,45 +607,18 @@ def generate_attacks(
     so collation belongs in worker processes),
     `device_pad` (real corpora: ship undecoded payloads and pad on the device) and `wave_fake_trim` (None = the
     reference's default, the SoX silence trim, which needs a registered backend) and `return_scores` (adds the whole job's
-    per-utterance `y_pred`, `y_pred_label`, `y` arrays, in rank order, to the returned report under "scores") and
+    per-utterance `y_pred`, `y_pred_label`, `y` arrays, in rank order, and every optional report's own rows to the returned
+    report under "scores") and
     `on_batch_queued(i)` (called when batch i's kernels have been queued, under the stream they were queued on — no
     synchronisation, no extra work: measurements) and `in_flight` (batches processed concurrently on streams of their own,
-    `_Lanes`; None = `default_in_flight`: 2 for the graph-replayed attacks, else 1; same scores either way) and
-    `perturbation_stats` (one more row pass per batch, `hip_ops.perturbation_stats`, over the loop's own waveform-domain
-    tensors — the batch and what the detector is given after `revert_minmax`, so the min-max round trip's rounding of samples
-    the attack did not move is part of the figure; adds the `perturbation/*` keys of `metrics.perturbation_summary`, a
-    second log line and, with `return_scores`, the per-utterance planes under `scores["perturbation"]`; off: the report, the
-    launches of a batch and the log are exactly those of a run without the keyword).
-    An attack that carries `last_radius` (torchattacks.MinRadiusPGD: each utterance's minimal radius, on the device;
-    torchattacks.HopSkipJump: the radius a label-only attacker reached, which also carries `last_queries`) adds the
-    `min_radius/*` keys of `metrics.radius_summary` at the attack's `report_at`, one more log line and, with `return_scores`,
-    the per-utterance radii under `scores["min_radius"]` (utterance order, like `y_pred`); any other attack: nothing.
-    An attack that carries `last_queries` (torchattacks.SPSA: the model queries each utterance spent, on the device) adds the
-    `blackbox/*` keys of `metrics.query_summary` against the attack's `budget`, one more log line and, with `return_scores`,
-    the per-utterance counts under `scores["queries"]`; any other attack: nothing.
-    An attack that carries `last_changed` (torchattacks.PGDL0: the samples of each utterance it changed, on the device) adds the
-    `sparse/*` keys of `metrics.sparsity_summary` against the attack's `k`, one more log line and, with `return_scores`, the
-    per-utterance counts under `scores["changed"]`; any other attack: nothing.
-    A universal attack (`is_universal`: torchattacks.UniversalPGD) gets its perturbation BEFORE the loop (`prepare_universal`):
-    loaded from `universal_load`, or fitted on the first `universal_fit` batches of this run's batch order (None: a quarter of
-    them, at least 1), which are kept on the device meanwhile (universal_fit x B x T x 4 bytes); `universal_save` writes it.  The
-    loop then runs over ALL batches with the frozen perturbation, one launch per batch.  More than one rank needs
-    `universal_load`.  Adds the `universal/*` keys of `metrics.universal_summary` (fitted against held-out utterances), one
-    more log line and, with `return_scores`, `scores["universal_delta"]`; any other attack: nothing, and the three keywords
-    must be left at None.
-    `channel` (a torchattacks.Channel or the name of a preset in torchattacks.CHANNELS) measures what is left of the attack —
-    any attack, or none — after a simulated audio channel: after the attack, the attacked and the clean waveform each go through
-    `channel_draws` draws of it (`_ChannelScorer`: the same draws for both, centre 0) and the detector scores them.  Adds
-    `channel/accuracy` (per cent, over all (utterance, draw) pairs), `channel/clean_accuracy`, `channel/survival` (the share of
-    pairs still misclassified among the utterances the attack flipped without the channel; 0 when it flipped none:
-    `channel/flipped` says how many), one log line and, over several ranks, one all-reduce of five counters.  `adv_eval/*` and
-    every other key are computed exactly as without it, from the unchannelled waveform.
-    An attack that carries `last_masking` (torchattacks.PsyPGD: the (B, 3) masking statistics of the rows it returned, on the
-    device) adds the `masking/*` keys of `metrics.masking_summary`, one more log line and, with `return_scores`, the
-    per-utterance rows under `scores["masking"]`.  `masking_stats` does the same for ANY attack, or none: after the attack,
-    `masking_pass` rates the batch against the clean utterance's masking threshold (`torchattacks.MaskingModel`, hop 128 or
-    the attack's own) in the attack's domain, one threshold and one launch per batch; it replaces the attack's own figures
-    where both exist.
+    `_Lanes`; None = `default_in_flight`: 2 for the graph-replayed attacks, else 1; same scores either way).
+    The remaining keywords, and some attacks by what they carry, add optional reports: keys behind the reference's, one more log
+    line each and rows under "scores" (`_active_reports` lists them; without any, the report, the launches of a batch and the
+    log are those of the reference's loop).  `perturbation_stats`: the per-utterance L-inf, L2, SNR and segmental SNR of what
+    the attack did.  `universal_fit` / `universal_load` / `universal_save`: where a universal attack's perturbation comes from
+    and goes (`_UniversalReport`); any other attack: they must be left at None.  `channel`, `channel_draws`: what is left of the
+    attack after that many draws of a simulated audio channel (`_ChannelScorer`).  `masking_stats`: every attack's perturbation
+    rated against the clean utterance's psychoacoustic masking threshold (`masking_pass`).
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -556,37 +660,18 @@ def generate_attacks(
         # decorrelate the random starts of different ranks (all ranks were seeded alike to build equal replicas)
         torch.manual_seed(seed + rank)
 
-    # a MultiAttack reports the utterances left after every member as well (multiattack.py's `save` mechanism: accumulate the
-    # records of every call)
-    from .torchattacks import MultiAttack
-    multi = atk if isinstance(atk, MultiAttack) else None
-    if multi is not None:
-        multi._start_multi_atk_records()
-
-    universal = atk if getattr(atk, "is_universal", False) else None
-    if universal is not None:
-        # on the caller's stream, BEFORE the lanes exist: their constructor orders every lane behind this stream
-        fitted_rows = prepare_universal(universal, test_loader, device, len(sampler), universal_fit, universal_load,
-                                        universal_save)
-    elif universal_fit is not None or universal_load is not None or universal_save is not None:
-        raise ValueError("universal_fit / universal_load / universal_save need a universal attack (AttackEnum UAP*)")
-
+    # BEFORE the lanes exist: a universal fit runs on the caller's stream, and the lanes' constructor orders every lane behind it
+    reports = _active_reports(atk, device, seed + rank, test_loader, len(sampler), perturbation_stats, masking_stats, channel,
+                              channel_draws, universal_fit, universal_load, universal_save)
     lanes = _Lanes(device, in_flight if in_flight is not None
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]
     seen_total = 0
-    y_pred, y_pred_label, y, perturbation, radii, queries, changed, masked = [], [], [], [], [], [], [], []
-    has_radius = atk is not None and hasattr(atk, "last_radius")
-    has_queries = atk is not None and hasattr(atk, "last_queries")
-    has_changed = atk is not None and hasattr(atk, "last_changed")
-    has_masking = masking_stats or (atk is not None and hasattr(atk, "last_masking"))
-    if has_masking:
-        from .torchattacks import MaskingModel
-        masking = getattr(atk, "masking", None) or MaskingModel()
-        masking_cells = None
-    if perturbation_stats:
-        from . import hip_ops
-    through = _ChannelScorer(channel, channel_draws, device, seed + rank) if channel is not None else None
+    y_pred, y_pred_label, y = [], [], []
+
+    def preprocessed(x):  # :229-234 — the dataset's default preprocessing, at the CURRENT batch's sampling rates
+        return SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(x, batch_sr, wave_fake_trim=wave_fake_trim)[0]
+    post = preprocessed if raw_sample_from_dataset else None
 
     for i, (batch_x, batch_sr, batch_y, batch_metadata, ready) in enumerate(_device_batches(test_loader, device)):
       with lanes.batch(i, tuple(batch_x.shape), ready, (batch_x, batch_y)) as lane:
@@ -595,43 +680,21 @@ def generate_attacks(
 
         if attack_model is not None:
             batch_x_attacked = attack_batch(atk, batch_x, batch_y)
-            if has_radius:
-                radii.append(atk.last_radius)                      # (B,), on this lane's stream; read after join()
-                lanes.keep(radii[-1])
-            if has_queries:
-                queries.append(atk.last_queries)                   # (B,) int32, on this lane's stream; read after join()
-                lanes.keep(queries[-1])
-            if has_changed:
-                changed.append(atk.last_changed)                   # (B,) int64, on this lane's stream; read after join()
-                lanes.keep(changed[-1])
-            if has_masking and not masking_stats:
-                masked.append(atk.last_masking)                    # (B, 3), on this lane's stream; read after join()
-                lanes.keep(masked[-1])
         else:
             batch_x_attacked = torch.clone(batch_x)
         batch_x_noproc, batch_x_attacked_noproc = batch_x, batch_x_attacked  # :223-224 (nothing below writes in place)
-        if perturbation_stats:
-            perturbation.append(hip_ops.perturbation_stats(batch_x, batch_x_attacked))       # (6, B), on this lane's stream
-            lanes.keep(perturbation[-1])
-        if has_masking:
-            masking_cells = masking.frames(batch_x[0].numel()) * 257
-            if masking_stats:
-                masked.append(masking_pass(masking, batch_x, batch_x_attacked))                  # (B, 3), on this lane's stream
-                lanes.keep(masked[-1])
+        for r in reports:
+            lanes.keep(*r.batch(atk, batch_x, batch_x_attacked))
 
-        if raw_sample_from_dataset:  # :229-234 — the dataset's default preprocessing, after the attack
-            batch_x_attacked, _ = SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(
-                batch_x_attacked, batch_sr, wave_fake_trim=wave_fake_trim)
+        if raw_sample_from_dataset:  # after the attack
+            batch_x_attacked = preprocessed(batch_x_attacked)
         batch_preds, batch_preds_label = score_batch(model, batch_x_attacked)
-        if through is not None:
-            post = ((lambda x: SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(x, batch_sr, wave_fake_trim=wave_fake_trim)[0])
-                    if raw_sample_from_dataset else None)
-            through.batch(lane, model, batch_x_noproc, batch_x_attacked_noproc, batch_y, batch_preds_label, post)
+        for r in reports:
+            lanes.keep(*r.scored(lane, model, batch_x_noproc, batch_x_attacked_noproc, batch_y, batch_preds_label, post))
 
         if on_attack_end_callback is not None:  # :240-259
             if raw_sample_from_dataset:
-                batch_x, _ = SimpleAudioFakeDataset.wavefake_preprocessing_on_batch(
-                    batch_x, batch_sr, wave_fake_trim=wave_fake_trim)
+                batch_x = preprocessed(batch_x)
             batch_preds_noattack, batch_preds_noattack_label = score_batch(model, batch_x)
             on_attack_end_callback(batch_x=batch_x_noproc, batch_x_attacked=batch_x_attacked_noproc, batch_y=batch_y,
                                    batch_preds_label=batch_preds_label, batch_preds=batch_preds,
@@ -655,82 +718,16 @@ def generate_attacks(
     all_pred, all_label, all_y, n_correct, n_total = aggregate_across_ranks(
         torch.cat(y_pred), torch.cat(y_pred_label), torch.cat(y), num_correct, num_total)
 
-    if multi is not None:
-        remaining = torch.tensor([int(r) for r in multi._multi_atk_records], dtype=torch.int64, device=device)
-        multi._clear_multi_atk_records()
-        multi._accumulate_multi_atk_records = False
-        if world > 1:
-            dist.all_reduce(remaining, op=dist.ReduceOp.SUM)     # next to the counters' all-reduce: (n_members + 1) int64
-        remaining = remaining.tolist()
-
-    if perturbation_stats:
-        planes = gather_rows_across_ranks(torch.cat(perturbation, dim=1).t()).T                    # (6, N), rank order
-        planes = {name: np.ascontiguousarray(planes[k], dtype=np.float32) for k, name in enumerate(metrics.PERTURBATION_PLANES)}
-
-    if has_radius:
-        all_radii = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(radii).reshape(-1, 1))[:, 0], dtype=np.float32)
-
-    if has_queries:
-        all_queries = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(queries).reshape(-1, 1))[:, 0], dtype=np.int32)
-
-    if has_changed:
-        all_changed = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(changed).reshape(-1, 1))[:, 0], dtype=np.int64)
-
-    if has_masking:
-        all_masked = np.ascontiguousarray(gather_rows_across_ranks(torch.cat(masked).reshape(-1, 3)), dtype=np.float32)
-
     report = metrics.adversarial_report(all_y, all_pred, all_label)
     report["adv_eval/accuracy"] = (n_correct / n_total) * 100  # :267 (from the all-reduced counters)
     report["num_total"] = n_total
     if return_scores:
         report["scores"] = {"y_pred": all_pred, "y_pred_label": all_label, "y": all_y}
-    if perturbation_stats:
-        report.update(metrics.perturbation_summary(planes, all_label != all_y))
+    ctx = SimpleNamespace(all_y=all_y, all_label=all_label, samples=batch_x_noproc[0].numel(), rank=rank, world=world, device=device)
+    for r in reports:
+        report.update(r.finish(ctx))
         if return_scores:
-            report["scores"]["perturbation"] = planes
-    if has_radius:
-        report.update(metrics.radius_summary(all_radii, getattr(atk, "report_at", ())))
-        if return_scores:
-            report["scores"]["min_radius"] = all_radii
-    if has_queries:
-        report.update(metrics.query_summary(all_queries, atk.budget))
-        if return_scores:
-            report["scores"]["queries"] = all_queries
-    if has_changed:
-        report.update(metrics.sparsity_summary(all_changed, atk.k))
-        if return_scores:
-            report["scores"]["changed"] = all_changed
-    if has_masking:
-        report.update(metrics.masking_summary(all_masked, masking_cells))
-        if return_scores:
-            report["scores"]["masking"] = all_masked
-    if universal is not None:
-        delta = universal.delta.detach().cpu().numpy()
-        # rank order = utterance order for the one process that fits; a loaded perturbation was fitted on none of them
-        report.update(metrics.universal_summary(all_y, all_label, np.arange(len(all_y)) < fitted_rows, delta,
-                                                universal.source_label))
-        if return_scores:
-            report["scores"]["universal_delta"] = delta
-    if multi is not None:
-        report["multi_attack/remaining"] = remaining
-    if through is not None:
-        report.update(through.report())
+            report["scores"].update(r.scores())
     if rank == 0:
-        if multi is not None:
-            LOGGER.info(multi._return_sr_record(remaining))
-        LOGGER.info(format_report(report))
-        if perturbation_stats:
-            LOGGER.info(format_perturbation(report))
-        if has_radius:
-            LOGGER.info(format_min_radius(report))
-        if has_queries:
-            LOGGER.info(format_blackbox(report))
-        if has_changed:
-            LOGGER.info(format_sparse(report))
-        if has_masking:
-            LOGGER.info(format_masking(report))
-        if universal is not None:
-            LOGGER.info(format_universal(report))
-        if through is not None:
-            LOGGER.info(format_channel(report))
+        _log_report(report, reports)
     return report
