@@ -1,5 +1,5 @@
 // row_tiles.h — the (tile, row) geometry of the 256-thread row kernels (advstep.hip, apgd.hip, momentum.hip, radius.hip, perturb.hip,
-// multiattack.hip, snr.hip, universal.hip, spsa.hip, hsj.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2
+// multiattack.hip, snr.hip, universal.hip, spsa.hip, hsj.hip, smooth.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2
 // arithmetic that several kernels must agree on bit for bit, and the launch on the (tile, row) grid (internal, like
 // advstep_common.h, which has the rules that do not depend on this tile: scalar semantics, reductions, rows_vec, ROW_KERNEL_PAIR,
 // overlaps).

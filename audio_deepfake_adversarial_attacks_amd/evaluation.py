@@ -15,7 +15,8 @@ log line.  What is different is how the work is placed on the machine:
     the packed (score, predicted label, label) rows over RCCL/xGMI (`backend="nccl"`), or gloo on CPU tests
     Every optional report of the run (`_active_reports`) adds at most one exchange of its own behind them, in the reports'
     order: a per-utterance report (`_RowReport`) one all-gather of its rows, a MultiAttack one all-reduce of its survivor
-    counts, `channel=` one all-reduce of its five counters, a universal attack none.
+    counts, `channel=` one all-reduce of its five counters, `certify=` one all-gather per dtype of its rows (two), a universal
+    attack none.
 """
 from __future__ import annotations
 
@@ -156,6 +157,7 @@ format_blackbox = functools.partial(format_keys, prefix="blackbox", integer_suff
 format_sparse = functools.partial(format_keys, prefix="sparse", integer_suffixes=("_max", "/k"))
 format_masking = functools.partial(format_keys, prefix="masking")
 format_channel = functools.partial(format_keys, prefix="channel", integer_suffixes=("draws", "flipped"), float_spec=".4f")
+format_certified = functools.partial(format_keys, prefix="certified", integer_suffixes=("/n", "violations"))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -328,8 +330,81 @@ class _ChannelScorer(_Report):
                 "channel/draws": self.draws}
 
 
+class _CertifyScorer(_Report):
+    """`certify=sigma`: randomized smoothing's certificate (Cohen, Rosenfeld and Kolter, ICML 2019) of the detector on the CLEAN
+    waveform of every batch — Cohen's protocol, whatever the attack, or none — through `torchattacks.Smoothing`: `n0` noisy
+    copies pick a class, `n` fresh ones give its count kA, and at the end of the run `metrics.certified_summary` turns the counts
+    into radii (host-side float64) and the `certified/*` keys.  `sigma` and the radii are in the WAVEFORM's units, one noise
+    level for every utterance; the normalised figures divide by the clean utterance's max - min, the unit of every `eps` of
+    AttackEnum (exact for the loop's threat model: the attack's waveform perturbation is span * delta).
+
+    With an attack (`attacked`), PREDICT also votes on the attacked waveform with `n0` copies:
+      certified/attacked_accuracy    per cent of utterances the smoothed detector still gets right (not abstained, right class)
+      certified/attacked_abstained   per cent on which PREDICT abstains (metrics.smoothed_prediction)
+      certified/violations           utterances where the attack's waveform-domain L2 (hip_ops.perturbation_stats) is BELOW the
+                                     certified radius, neither procedure abstained and PREDICT gives the other class: 0 with
+                                     probability >= 1 - alpha per utterance when the implementation is sound
+    Every vote's noise is keyed by (seed, offset): a host counter advances by the slots a batch used, so the offsets follow the
+    loop's batch order whatever the lanes do, and rank r starts at r << 40.  Per batch the scorer keeps an int32 and a float32
+    row block on the device; `finish` makes one all-gather per dtype.  No host read before that.  The forwards are no_grad and
+    come after the batch was scored: `adv_eval/*` and every other key are computed exactly as without it.  The frontends'
+    dB floor is batch-wide, so a copy's logit depends on the rows forwarded with it: what is certified is the detector with
+    that floor as these chunks form it (SPSA and HopSkipJump query it the same way)."""
+
+    line = staticmethod(format_certified)
+
+    def __init__(self, sigma: float, samples: int, select: int, alpha: float, device, seed: int = 0, rank: int = 0,
+                 attacked: bool = False, report_at=metrics.CERTIFIED_REPORT_AT):
+        from . import hip_ops
+        from .torchattacks import Smoothing
+        self.ops, self.device, self.attacked, self.report_at = hip_ops, device, bool(attacked), tuple(report_at)
+        self.smooth = Smoothing(sigma, n=samples, n0=select, alpha=alpha, seed=seed)    # raises on a bad sigma, n, n0 or alpha
+        self.offset = int(rank) << 40
+        self.int_rows: List[torch.Tensor] = []          # per batch, in the loop's order: (B, 3) int32
+        self.float_rows: List[torch.Tensor] = []        # (B, 2) float32
+
+    def scored(self, lane, model, clean, attacked, labels, attacked_label, post):
+        sm, B = self.smooth, clean.shape[0]
+        cert = sm.certify(model, clean, self.offset, post)
+        self.offset += sm.slots_certify
+        flat = clean.reshape(B, -1)
+        span = flat.amax(dim=1) - flat.amin(dim=1)
+        if self.attacked:
+            c1 = sm.predict(model, attacked, self.offset, post)[:, 0]
+            self.offset += sm.slots_predict
+            l2 = self.ops.perturbation_stats(clean.contiguous(), attacked.contiguous())[metrics.PERTURBATION_PLANES.index("l2")]
+        else:
+            c1, l2 = torch.zeros_like(cert[:, 0]), torch.zeros_like(span)
+        self.int_rows.append(torch.cat([cert, c1.unsqueeze(1)], dim=1))
+        self.float_rows.append(torch.stack([span, l2], dim=1))
+        return self.int_rows[-1], self.float_rows[-1]
+
+    def finish(self, ctx):
+        sm = self.smooth
+        ints = gather_rows_across_ranks(torch.cat(self.int_rows)).astype(np.int64)
+        floats = gather_rows_across_ranks(torch.cat(self.float_rows)).astype(np.float64)
+        y = np.asarray(ctx.all_y, dtype=np.int64).ravel()
+        radius = np.asarray(metrics.certified_radius(ints[:, 1], sm.n, sm.alpha, sm.sigma), dtype=np.float64).reshape(-1)
+        self.rows = {"class": ints[:, 0].astype(np.int32), "kA": ints[:, 1].astype(np.int32), "radius": radius,
+                     "span": floats[:, 0].astype(np.float32)}
+        out = metrics.certified_summary(ints[:, :2], y, floats[:, 0], sm.sigma, sm.n, sm.n0, sm.alpha, self.report_at)
+        if self.attacked:
+            pred = np.asarray(metrics.smoothed_prediction(ints[:, 2], sm.n0, sm.alpha), dtype=np.int64).reshape(-1)
+            l2 = floats[:, 1]
+            out["certified/attacked_accuracy"] = 100.0 * float(np.mean(pred == y)) if y.size else float("nan")
+            out["certified/attacked_abstained"] = 100.0 * float(np.mean(pred < 0)) if y.size else float("nan")
+            out["certified/violations"] = int(np.sum((radius >= 0.0) & (l2 < radius) & (pred >= 0) & (pred != ints[:, 0])))
+            self.rows.update({"attacked_c1": ints[:, 2].astype(np.int32), "attacked_class": pred.astype(np.int32),
+                              "l2": l2.astype(np.float32)})
+        return out
+
+    def scores(self):
+        return {"certified": self.rows}
+
+
 def _active_reports(atk, device, seed: int, loader, n_batches: int, perturbation_stats: bool, masking_stats: bool, channel,
-                    channel_draws: int, universal_fit, universal_load, universal_save) -> List[_Report]:
+                    channel_draws: int, universal_fit, universal_load, universal_save, certify=None, certify_samples: int = 1000,
+                    certify_select: int = 100, certify_alpha: float = 0.001) -> List[_Report]:
     """The optional reports of a run, in the order of their keys and log lines; the one place that names them.  An attack-borne
     report is active when the attack HAS the attribute before its first call (None until then).  A run with every keyword off
     and an attack that carries nothing gets an empty list: the loop does nothing for them."""
@@ -372,6 +447,9 @@ def _active_reports(atk, device, seed: int, loader, n_batches: int, perturbation
         reports.append(_MultiAttackReport(atk))
     if channel is not None:
         reports.append(_ChannelScorer(channel, channel_draws, device, seed))
+    if certify is not None:
+        reports.append(_CertifyScorer(certify, certify_samples, certify_select, certify_alpha, device, seed, rank_and_world()[0],
+                                      attacked=atk is not None))
     return reports
 
 
@@ -599,6 +677,10 @@ def generate_attacks(
     channel: Optional[Any] = None,
     channel_draws: int = 1,
     masking_stats: bool = False,
+    certify: Optional[float] = None,
+    certify_samples: int = 1000,
+    certify_select: int = 100,
+    certify_alpha: float = 0.001,
 ) -> Dict[str, float]:
     """Reference signature (:146-157) plus additive keywords: `dataset` (a ready Dataset yielding the reference's
     4-tuple; without it the `DetectionDataset` over `datasets_paths` is built as in the reference's `get_dataset`,
@@ -618,7 +700,9 @@ def generate_attacks(
     the attack did.  `universal_fit` / `universal_load` / `universal_save`: where a universal attack's perturbation comes from
     and goes (`_UniversalReport`); any other attack: they must be left at None.  `channel`, `channel_draws`: what is left of the
     attack after that many draws of a simulated audio channel (`_ChannelScorer`).  `masking_stats`: every attack's perturbation
-    rated against the clean utterance's psychoacoustic masking threshold (`masking_pass`).
+    rated against the clean utterance's psychoacoustic masking threshold (`masking_pass`).  `certify` (a noise level sigma > 0, in
+    the waveform's units), `certify_samples` (n), `certify_select` (n0), `certify_alpha`: randomized smoothing's certified L2
+    radius of every clean utterance and, with an attack, the smoothed detector's answer to it (`_CertifyScorer`).
     `batch_size` is the GLOBAL batch."""
     rank, world = rank_and_world()
     LOGGER.info("Loading data...")
@@ -662,7 +746,8 @@ def generate_attacks(
 
     # BEFORE the lanes exist: a universal fit runs on the caller's stream, and the lanes' constructor orders every lane behind it
     reports = _active_reports(atk, device, seed + rank, test_loader, len(sampler), perturbation_stats, masking_stats, channel,
-                              channel_draws, universal_fit, universal_load, universal_save)
+                              channel_draws, universal_fit, universal_load, universal_save, certify, certify_samples,
+                              certify_select, certify_alpha)
     lanes = _Lanes(device, in_flight if in_flight is not None
                    else default_in_flight(atk, device, on_attack_end_callback is not None))
     num_correct = [torch.zeros((), dtype=torch.int64, device=device) for _ in range(lanes.n)]

@@ -25,6 +25,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   hsj_search_* / hsj_probe / hsj_candidates / hsj_take  no counterpart: the label-only black-box attack, torchattacks.HopSkipJump
   channel_apply / _adjoint / _eot_step  no counterpart: the simulated audio channel of torchattacks.Channel / EOTPGD
   stft_power / masking_hinge_grad / psy_step  no counterpart: the psychoacoustic masking hinge of torchattacks.PsyPGD
+  smooth_noise / smooth_tally        no counterpart: the noisy copies and the votes of torchattacks.Smoothing
 """
 from __future__ import annotations
 
@@ -1078,6 +1079,40 @@ def spsa_step(adv, orig, z, labels, queries, alpha: float, eps: float, seed: int
     _call("advstep_spsa_step_f32", adv.device, adv, orig, z, labels, queries, out, B, T, n, alpha, eps, lo, hi, seed, offset,
           bracket="spsa_step", tensors=(adv, orig, out, z))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# randomized smoothing (include/advstep_smooth.h): the Gaussian-noised copies of a batch and the vote count over their logits
+# ---------------------------------------------------------------------------------------------------------
+
+def smooth_noise(x, sigma: float, seed: int, offset: int = 0, s0: int = 0, ns: int = 1, out=None):
+    """(ns, *x.shape) float32: copies s0 .. s0 + ns - 1 of `x` (B, T) under Gaussian noise, x + sigma * z with z the standard
+    normals the kernel regenerates from Philox at counter offset + s (seed; include/advstep_smooth.h has the mapping).  No clamp;
+    a NaN in x propagates.  A fill in chunks gives the bytes of a whole one.  One launch, 4 B read and 4 * ns B written per
+    sample, no host read."""
+    _require(x, "x")
+    B, T = _rows(x, "x")
+    s0, ns, sigma = int(s0), int(ns), float(sigma)
+    if s0 < 0 or ns < 0:
+        raise ValueError(f"s0 and ns must not be negative, got {s0} and {ns}")
+    if not 0.0 <= sigma < float("inf"):                             # (a NaN sigma fails the comparison)
+        raise ValueError(f"sigma must be a finite noise level >= 0, got {sigma}")
+    out = _stacked_out(out, ns, x)
+    _call("advstep_smooth_noise_f32", x.device, x, out, B, T, s0, ns, sigma, seed, offset,
+          bracket="smooth_noise", tensors=(x, out))
+    return out
+
+
+def smooth_tally(z, counts):
+    """counts[b] += #{s : z[s, b] > 0} for the logits `z` (ns, B) of ns noisy copies; `counts` (B,) int32, read and written.
+    A NaN logit is class 0.  One launch, no host read."""
+    _require(z, "z")
+    if z.dim() != 2:
+        raise ValueError(f"z must be (ns, B), got {tuple(z.shape)}")
+    ns, B = z.shape
+    _per_row(counts, "counts", B, torch.int32, z.device)
+    _call("advstep_smooth_tally_i32", z.device, z, counts, B, ns, bracket="smooth_tally", tensors=(z, counts))
+    return counts
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -5,8 +5,9 @@ reference's own calls produced (tests/golden/metrics.npz).  `perturbation_summar
 digest of the per-utterance perturbation report (include/advstep_perturb.h); so is `radius_summary`, the digest of the
 per-utterance minimal radii of torchattacks.MinRadiusPGD, `universal_summary`, the fitted / held-out split of a run with one
 universal perturbation (torchattacks.UniversalPGD), `query_summary`, the digest of the per-utterance model queries of a
-score-based attack (torchattacks.SPSA), and `sparsity_summary`, the digest of the per-utterance changed-sample counts of a
-sparse attack (torchattacks.PGDL0)."""
+score-based attack (torchattacks.SPSA), `sparsity_summary`, the digest of the per-utterance changed-sample counts of a
+sparse attack (torchattacks.PGDL0), and the statistics of randomized smoothing (torchattacks.Smoothing): `clopper_pearson_lower`,
+`certified_radius`, `smoothed_prediction` and `certified_summary` — these four import scipy where they run."""
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -318,3 +319,93 @@ def masking_summary(stats, cells: int) -> Dict[str, float]:
     return {"masking/over_share_mean": float(np.mean(share)), "masking/over_share_median": float(np.median(share)),
             "masking/worst_db_median": float(np.median(db)), "masking/worst_db_p90": float(np.percentile(db, 90)),
             "masking/loss_mean": float(np.mean(s[:, 0]))}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# randomized-smoothing certificate (torchattacks.Smoothing; Cohen, Rosenfeld and Kolter, ICML 2019)
+# ---------------------------------------------------------------------------------------------------------
+# Host-side float64, once at the end of a run.  scipy is imported where it is used: the rest of this module needs numpy alone.
+
+CERTIFIED_REPORT_AT = (0.1, 0.15, 0.2)           # the PGDL2 triplet of AttackEnum, in the normalised unit (radius / span)
+
+
+def clopper_pearson_lower(k, n: int, alpha: float):
+    """The one-sided Clopper-Pearson lower confidence bound of a binomial proportion from k successes in n trials, at level
+    1 - alpha: the p with P(Binomial(n, p) >= k) = alpha, i.e. scipy.stats.beta.ppf(alpha, k, n - k + 1); 0 for k == 0 and
+    alpha ** (1 / n) for k == n (the same value in closed form).  `k` may be an array; float64."""
+    from scipy.stats import beta
+    k = np.asarray(k, dtype=np.float64)
+    n = int(n)
+    if n < 1 or not 0.0 < float(alpha) < 1.0:
+        raise ValueError(f"need n >= 1 and 0 < alpha < 1, got n = {n} and alpha = {alpha}")
+    if ((k < 0) | (k > n)).any():
+        raise ValueError(f"k must lie in 0 .. {n}")
+    inner = (k > 0) & (k < n)
+    p = np.where(k >= n, float(alpha) ** (1.0 / n), 0.0)
+    if inner.any():
+        p = np.where(inner, beta.ppf(float(alpha), np.where(inner, k, 1.0), np.where(inner, n - k + 1.0, 1.0)), p)
+    return p if p.ndim else float(p)
+
+
+def certified_radius(k, n: int, alpha: float, sigma: float):
+    """Cohen's certified L2 radius of the class that got k of n noisy votes: sigma * Phi^-1(p_lower) where p_lower =
+    clopper_pearson_lower(k, n, alpha) > 0.5, in sigma's unit; otherwise the procedure ABSTAINS, coded -1.  k <= n / 2 always
+    abstains.  `k` may be an array; float64."""
+    from scipy.stats import norm
+    p = np.asarray(clopper_pearson_lower(k, n, alpha), dtype=np.float64)
+    ok = p > 0.5
+    r = np.where(ok, float(sigma) * norm.ppf(np.where(ok, p, 0.75)), -1.0)
+    return r if r.ndim else float(r)
+
+
+def smoothed_prediction(c1, n0: int, alpha: float):
+    """Cohen's PREDICT from c1 class-1 votes among n0: the majority class (a tie goes to class 0), or -1 (abstain) when the
+    two-sided test scipy.stats.binomtest(max(c1, n0 - c1), n0, 0.5).pvalue > alpha.  `c1` may be an array; int64."""
+    from scipy.stats import binomtest
+    c = np.asarray(c1, dtype=np.int64)
+    top = np.maximum(c, int(n0) - c)
+    pvalue = {int(m): binomtest(int(m), int(n0), 0.5).pvalue for m in np.unique(top)}
+    keep = np.array([pvalue[int(m)] <= alpha for m in top.ravel()], dtype=bool).reshape(top.shape)
+    out = np.where(keep, (2 * c > int(n0)).astype(np.int64), -1)
+    return out if out.ndim else int(out)
+
+
+def certified_summary(rows, labels, spans, sigma: float, n: int, n0: int, alpha: float,
+                      report_at: Sequence[float] = CERTIFIED_REPORT_AT) -> Dict[str, float]:
+    """Run-level digest of Cohen's CERTIFY per utterance.  `rows` (N, 2) = (the class the n0 selection votes picked, kA = that
+    class's count among the n estimation votes); `labels` (N,); `spans` (N,) = each clean utterance's max - min, the unit of every
+    `eps` of AttackEnum; `sigma` and the radii in the waveform's units.
+
+    certified/accuracy               per cent of utterances not abstained and of the right class
+    certified/abstained              per cent abstained
+    certified/radius_median          the median radius over the certified-and-right rows (NaN without any)
+    certified/radius_norm_median     the same of radius / span
+    certified/accuracy_at_<r>        per cent certified, right and with radius / span >= r, for every r of report_at
+    certified/radius_max             sigma * Phi^-1(alpha ** (1 / n)): the ceiling this n can certify
+    certified/sigma, n, alpha        the run's parameters (n0 does not enter the radius)
+    An empty run gives NaN for the shares and medians."""
+    from scipy.stats import norm
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+    y = np.asarray(labels, dtype=np.int64).ravel()
+    span = np.asarray(spans, dtype=np.float64).ravel()
+    if not (rows.shape[0] == y.size == span.size):
+        raise ValueError(f"rows, labels and spans must hold one entry per utterance, got {rows.shape[0]}, {y.size}, {span.size}")
+    N = y.size
+    radius = np.asarray(certified_radius(rows[:, 1], n, alpha, sigma), dtype=np.float64).reshape(-1)
+    abstained = radius < 0.0
+    right = ~abstained & (rows[:, 0] == y)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rnorm = radius / span
+    nan = float("nan")
+
+    def pct(mask):
+        return 100.0 * float(np.mean(mask)) if N else nan
+
+    out: Dict[str, float] = {"certified/accuracy": pct(right), "certified/abstained": pct(abstained),
+                             "certified/radius_median": float(np.median(radius[right])) if right.any() else nan,
+                             "certified/radius_norm_median": float(np.median(rnorm[right])) if right.any() else nan}
+    for r in report_at:
+        out[f"certified/accuracy_at_{r:g}"] = pct(right & (rnorm >= float(r)))
+    out["certified/radius_max"] = float(sigma) * float(norm.ppf(float(alpha) ** (1.0 / int(n))))
+    out["certified/sigma"], out["certified/n"], out["certified/alpha"] = float(sigma), int(n), float(alpha)
+    return out

@@ -8,7 +8,8 @@ SNR or segmental SNR), UniversalPGD (one perturbation fitted once and added to e
 black-box counterpart of PGD: queries instead of gradients) and EOTPGD (PGD on a gradient summed over passes, here over draws of a
 simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat model: at most k samples of an utterance change) and HopSkipJump (the label-only
 black-box attack: decisions instead of scores) and PsyPGD (PGD pulled under the psychoacoustic masking threshold of the clean
-utterance: `MaskingModel`), with the reference's constructor
+utterance: `MaskingModel`), and beside them `Smoothing`, which is no attack: randomized smoothing's votes over noisy copies, for a
+certified lower bound on the radius the attacks bound from above, with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -33,8 +34,9 @@ from .attacks.vmifgsm import VMIFGSM
 from .attacks.vnifgsm import VNIFGSM
 from .channel import CHANNELS, Channel
 from .masking import MaskingModel
+from .smoothing import Smoothing
 
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
-           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel"]
+           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing"]

@@ -95,6 +95,16 @@ def parse_arguments(argv=None):
                         help="rate the perturbation against the clean utterance's psychoacoustic masking threshold (the share of "
                              "time-frequency cells over it, the worst excess in dB, the hinge loss): masking/* keys and one more "
                              "log line; works with every attack and with NO_ATTACK")
+    parser.add_argument("--certify", type=float, default=None, metavar="SIGMA",
+                        help="randomized smoothing at noise level SIGMA (> 0, in the waveform's units): a certified L2 radius of "
+                             "every clean utterance and, with an attack, the smoothed detector's answer to it: certified/* keys "
+                             "and one more log line; works with every attack and with NO_ATTACK")
+    parser.add_argument("--certify_samples", type=int, default=1000, metavar="N",
+                        help="noisy copies per utterance that estimate the certified class's probability (default 1000)")
+    parser.add_argument("--certify_select", type=int, default=100, metavar="N0",
+                        help="noisy copies per utterance that pick the class, and that vote on the attacked waveform (default 100)")
+    parser.add_argument("--certify_alpha", type=float, default=0.001, metavar="A",
+                        help="failure probability of a certificate (default 0.001)")
     return parser.parse_args(argv)
 
 
@@ -158,6 +168,10 @@ def main(args):
         channel=args.channel,
         channel_draws=args.channel_draws,
         masking_stats=args.masking_stats,
+        certify=args.certify,
+        certify_samples=args.certify_samples,
+        certify_select=args.certify_select,
+        certify_alpha=args.certify_alpha,
     )
     if world > 1:
         dist.destroy_process_group()
