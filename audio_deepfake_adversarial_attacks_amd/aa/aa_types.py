@@ -168,4 +168,13 @@ class AttackEnum(Enum):
     PSYPGD40_eps003 = (torchattacks.PsyPGD, {"eps": 0.003, "alpha": 2.5 * 0.003 / 40, "steps": 40, "mask_steps": 40,
                                              "mask_weight": 1.0})    # budget unmeasured, as above
 
+    # --- additive members: PGD on the SMOOTHED detector (torchattacks.SmoothAdvPGD: SmoothAdv of Salman et al., NeurIPS 2019 — the
+    # soft vote over noisy copies of the iterate is differentiated, not the detector at one point), at the radii of the PGDL2
+    # triplet above; alpha = 2 eps / steps.  sigma 0.05 in the waveform's units (with --certify the run's sigma replaces it), 8 noise
+    # draws and 10 steps are 80 gradient passes per utterance.  sigma, the draws and the radii are choices of scale: nobody has
+    # measured what they achieve against a detector trained under noise ---
+    SMOOTHADV = (torchattacks.SmoothAdvPGD, {"eps": 0.1, "steps": 10, "sigma": 0.05, "samples": 8})
+    SMOOTHADV_eps15 = (torchattacks.SmoothAdvPGD, {"eps": 0.15, "steps": 10, "sigma": 0.05, "samples": 8})
+    SMOOTHADV_eps20 = (torchattacks.SmoothAdvPGD, {"eps": 0.20, "steps": 10, "sigma": 0.05, "samples": 8})
+
     NO_ATTACK = (None, {})

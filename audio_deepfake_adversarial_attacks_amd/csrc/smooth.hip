@@ -16,6 +16,7 @@
 #include "advstep_smooth.h"
 #include "advstep_common.h"
 #include "row_tiles.h"
+#include "smooth_fill.h"
 
 namespace {
 
@@ -25,21 +26,7 @@ template <bool VEC>
 __global__ __launch_bounds__(kWgThreads) void smooth_noise_kernel(const float *__restrict__ x, float *__restrict__ out, int64_t B,
                                                                   int64_t T, int64_t ns, float sigma, uint64_t seed,
                                                                   uint64_t offset0) {
-    const int tile = blockIdx.x;
-    const int64_t b = blockIdx.y;
-    float4 a[kVecs];
-    load_tile<VEC>(x + b * T, T, tile, 0.0f, a);
-    for (int64_t i = 0; i < ns; ++i) {
-        const uint64_t O = offset0 + (uint64_t)i;  // offset + s, carried into the high counter word
-        float *slot = out + (i * B + b) * T;
-#pragma unroll
-        for (int v = 0; v < kVecs; ++v) {
-            const int64_t q = quad_of(tile, v);
-            if (!in_row(T, q, 0)) continue;  // no barrier in this kernel
-            const float4 z = philox_normal4((uint32_t)q, (uint32_t)b, seed, O);
-            store4<VEC>(slot, T, q, make_float4(a[v].x + sigma * z.x, a[v].y + sigma * z.y, a[v].z + sigma * z.z, a[v].w + sigma * z.w));
-        }
-    }
+    noised_slots<VEC, false>(x, nullptr, nullptr, out, B, T, ns, sigma, seed, offset0);  // smooth_fill.h: smoothadv.hip's fill too
 }
 
 // ---- b. the votes -----------------------------------------------------------------------------------------------------------------

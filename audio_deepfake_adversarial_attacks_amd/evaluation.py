@@ -453,6 +453,17 @@ def _active_reports(atk, device, seed: int, loader, n_batches: int, perturbation
     return reports
 
 
+def adopt_certify_sigma(atk, certify: Optional[float]) -> bool:
+    """There is one smoothed detector per run: with `certify=sigma`, an attack on the smoothed detector
+    (torchattacks.SmoothAdvPGD) attacks the one being certified, whatever sigma it was constructed with.  True when it applied."""
+    from .torchattacks import SmoothAdvPGD
+    if certify is None or not isinstance(atk, SmoothAdvPGD):
+        return False
+    LOGGER.info(f"SmoothAdvPGD: sigma {atk.sigma:g} -> {float(certify):g}, the smoothed detector this run certifies")
+    atk.sigma = float(certify)
+    return True
+
+
 def _log_report(report: Dict[str, float], reports: List[_Report]) -> None:
     for line in ([r.line(report) for r in reports if r.leads] + [format_report(report)]
                  + [r.line(report) for r in reports if not r.leads]):
@@ -714,6 +725,7 @@ def generate_attacks(
             attack_model.load_state_dict(model.state_dict())
         atk = attack_method(attack_model, **attack_params)         # :169
         atk.set_training_mode(model_training=True, batchnorm_training=False)  # :170
+        adopt_certify_sigma(atk, certify)
     else:
         attack_model, atk = None, None
 

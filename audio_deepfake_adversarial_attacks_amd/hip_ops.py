@@ -26,6 +26,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   channel_apply / _adjoint / _eot_step  no counterpart: the simulated audio channel of torchattacks.Channel / EOTPGD
   stft_power / masking_hinge_grad / psy_step  no counterpart: the psychoacoustic masking hinge of torchattacks.PsyPGD
   smooth_noise / smooth_tally        no counterpart: the noisy copies and the votes of torchattacks.Smoothing
+  smoothadv_fill / _loss_grad / _step  no counterpart: PGD on the smoothed detector's soft vote, torchattacks.SmoothAdvPGD
 """
 from __future__ import annotations
 
@@ -1113,6 +1114,73 @@ def smooth_tally(z, counts):
     _per_row(counts, "counts", B, torch.int32, z.device)
     _call("advstep_smooth_tally_i32", z.device, z, counts, B, ns, bracket="smooth_tally", tensors=(z, counts))
     return counts
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the attack on the smoothed detector (include/advstep_smoothadv.h): the noised copies of the iterate in the detector's domain,
+# the soft vote over their logits with its gradient, and the sum over the slot gradients fused with PGD's step
+# ---------------------------------------------------------------------------------------------------------
+
+SMOOTHADV_NORMS = {"Linf": 0, "L2": 1}          # ADVSTEP_SMOOTHADV_LINF / _L2
+
+
+def smoothadv_fill(adv, sigma: float, seed: int, offset: int = 0, s0: int = 0, ns: int = 1, scale=None, shift=None, out=None):
+    """(ns, *adv.shape) float32: copies s0 .. s0 + ns - 1 of (shift_b + scale_b * adv) + sigma * z, `scale` / `shift` one float32 per
+    row or both None (then the bytes are `smooth_noise`'s), z as in `smooth_noise` at counter offset + s.  With scale = mx - mn
+    and shift = mn the copies are those of the reverted iterate, which is never stored.  One launch, 4 B read and 4 * ns B written
+    per sample, no host read."""
+    _require(adv, "adv")
+    B, T = _rows(adv, "adv")
+    s0, ns, sigma = int(s0), int(ns), float(sigma)
+    if s0 < 0 or ns < 0:
+        raise ValueError(f"s0 and ns must not be negative, got {s0} and {ns}")
+    if not 0.0 <= sigma < float("inf"):                             # (a NaN sigma fails the comparison)
+        raise ValueError(f"sigma must be a finite noise level >= 0, got {sigma}")
+    if (scale is None) != (shift is None):
+        raise ValueError("scale and shift are given together or not at all")
+    scale, shift = _optional_rows(scale, "scale", B, adv.device), _optional_rows(shift, "shift", B, adv.device)
+    out = _stacked_out(out, ns, adv)
+    _call("advstep_smoothadv_fill_f32", adv.device, adv, scale, shift, out, B, T, s0, ns, sigma, seed, offset,
+          bracket="smoothadv_fill", tensors=(adv, out))
+    return out
+
+
+def smoothadv_loss_grad(z, labels, scale: float = 1.0):
+    """The soft vote of m noised copies: for logits `z` (m, B) and labels (B) int64 returns (dz (m, B), cost (B)) with cost_b =
+    -log(mean_i sigmoid(s z_ib)), s = 2 y_b - 1, and dz = scale * d cost_b / d z_ib (scale = -1: targeted).  The cost is per row,
+    not a batch mean.  One launch, no host read."""
+    _require(z, "z")
+    if z.dim() != 2:
+        raise ValueError(f"z must be (m, B), got {tuple(z.shape)}")
+    m, B = z.shape
+    _per_row(labels, "labels", B, torch.int64, z.device)
+    dz = torch.empty_like(z)
+    cost = torch.empty(B, dtype=torch.float32, device=z.device)
+    _call("advstep_smoothadv_loss_grad_f32", z.device, z, labels, dz, cost, B, m, float(scale), bracket="smoothadv_loss_grad",
+          tensors=(z, dz, cost))
+    return dz, cost
+
+
+def smoothadv_step(adv, orig, grads, alpha: float, eps: float, norm: str = "L2", eps_div: float = 1e-10, lo: float = 0.0,
+                   hi: float = 1.0, out=None, gsum=None):
+    """PGD's step along the slot-order float32 sum of `grads` (m, *adv.shape): `out` has the bits of `pgd_l2_step` / `pgd_linf_step`
+    on (adv, sum, orig).  The sum is written to `gsum` and returned as (out, gsum) when `gsum` is given.  L-inf: one launch,
+    (m + 2) * 4 B read per sample; L2: three, the first of which also leaves the sum's row norms.  `out` may be `adv`."""
+    _require(adv, "adv"), _require(orig, "orig"), _require(grads, "grads")
+    _same_shape(("adv", adv), ("orig", orig))
+    B, T = _rows(adv, "adv")
+    if norm not in SMOOTHADV_NORMS:
+        raise ValueError(f"norm must be one of {sorted(SMOOTHADV_NORMS)}, got {norm!r}")
+    if grads.dim() < 1 or grads.shape[0] < 1 or grads.numel() != grads.shape[0] * adv.numel() or grads.device != adv.device:
+        raise ValueError(f"grads must hold (m, {B}, {T}) values with m >= 1 on {adv.device}, got {tuple(grads.shape)}@{grads.device}")
+    m = grads.shape[0]
+    out = _out_like(adv, out)
+    sums = _out_like(adv, gsum, "gsum")
+    with _Launch("smoothadv_step", adv.device, tensors=(adv, orig, grads, sums, out)):
+        ws, ws_bytes = _workspace(adv.device, B, T) if norm == "L2" else (None, 0)
+        _call("advstep_smoothadv_step_f32", adv.device, adv, orig, grads, sums, out, B, T, m, SMOOTHADV_NORMS[norm], alpha, eps, eps_div,
+              lo, hi, ws, ws_bytes)
+    return out if gsum is None else (out, gsum)
 
 
 # ---------------------------------------------------------------------------------------------------------

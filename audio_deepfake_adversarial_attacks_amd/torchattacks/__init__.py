@@ -9,7 +9,8 @@ black-box counterpart of PGD: queries instead of gradients) and EOTPGD (PGD on a
 simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat model: at most k samples of an utterance change) and HopSkipJump (the label-only
 black-box attack: decisions instead of scores) and PsyPGD (PGD pulled under the psychoacoustic masking threshold of the clean
 utterance: `MaskingModel`), and beside them `Smoothing`, which is no attack: randomized smoothing's votes over noisy copies, for a
-certified lower bound on the radius the attacks bound from above, with the reference's constructor
+certified lower bound on the radius the attacks bound from above, and SmoothAdvPGD (PGD on that smoothed detector's soft vote: the
+adversary the certificate has to withstand), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -28,6 +29,7 @@ from .attacks.pgdl0 import PGDL0
 from .attacks.pgdl2 import PGDL2
 from .attacks.pgdsnr import PGDSNR
 from .attacks.psypgd import PsyPGD
+from .attacks.smoothadv import SmoothAdvPGD
 from .attacks.spsa import SPSA
 from .attacks.universal import UniversalPGD
 from .attacks.vmifgsm import VMIFGSM
@@ -39,4 +41,4 @@ from .smoothing import Smoothing
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
-           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing"]
+           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing", "SmoothAdvPGD"]

@@ -67,6 +67,8 @@ class Trainer:
     loader_workers = 0      # the reference forks 6 DataLoader workers to decode audio; tensors already in memory need none
     corpus_loader_workers = 6   # ... audio files on disk do (src/trainer.py:154,162)
     attack_ops = None       # test seam: op table handed to every attack (None = the HIP kernels)
+    noise_sigma = None      # Gaussian-noise training (Cohen et al., ICML 2019): every TRAINING batch becomes x + N(0, sigma^2 I), in the
+                            # waveform's units, after any attack; None = off, and nothing below touches the batch or a generator
 
     def __init__(self, epochs: int = 20, batch_size: int = 32, device: str = "cpu",
                  optimizer_fn: Callable = torch.optim.Adam, optimizer_kwargs: dict = {"lr": 1e-3},
@@ -149,6 +151,7 @@ class GDTrainer(Trainer):
         trainer = AdversarialGDTrainer(self.epochs, self.batch_size, self.device, self.optimizer_fn, self.optimizer_kwargs,
                                        self.use_scheduler)
         trainer.loader_workers = self.loader_workers
+        trainer.noise_sigma, trainer.attack_ops = self.noise_sigma, self.attack_ops
         # src/trainer.py:118 restarts the cosine schedule every second epoch for clean training
         return trainer._fit(dataset, model, None, [], test_len, test_dataset, None, None, scheduler_period=2,
                             banner=f"Starting training for {self.epochs} epochs!")
@@ -209,6 +212,16 @@ class AdversarialGDTrainer(Trainer):
             if torch.cuda.is_available():
                 torch.cuda.manual_seed(base + rank)
 
+        noise_ops, noise_seed, noise_step = None, 0, 0
+        if self.noise_sigma is not None:
+            # what randomized smoothing certifies is the detector under noise, so it is trained under that noise: one Philox key
+            # per fit from torch's CPU generator, one offset per step ((rank << 40) + step: no two steps share (seed, offset))
+            if not 0.0 < float(self.noise_sigma) < float("inf"):     # (a NaN sigma fails the comparison)
+                raise ValueError(f"noise_sigma must be a finite noise level > 0 or None, got {self.noise_sigma}")
+            noise_ops = self._noise_ops()
+            noise_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+            LOGGER.info(f"Training under Gaussian noise, sigma = {float(self.noise_sigma):g} in the waveform's units")
+
         for epoch in range(self.epochs):
             LOGGER.info(f"Epoch num: {epoch}")
             running_loss, num_correct, num_total = 0.0, 0.0, 0.0
@@ -222,6 +235,10 @@ class AdversarialGDTrainer(Trainer):
                 batch_x = self._upload(batch_x)
                 if adversarial:
                     batch_x = self.apply_adv_attack(batch_x, batch_y).detach()
+                if noise_ops is not None:                            # validation stays clean
+                    batch_x = noise_ops.smooth_noise(batch_x.contiguous(), float(self.noise_sigma), noise_seed,
+                                                     offset=(rank << 40) + noise_step, ns=1)[0]
+                    noise_step += 1
                 batch_y = batch_y.unsqueeze(1).type(torch.float32).to(self.device)
 
                 batch_out, batch_loss = forward_and_loss(model=model, criterion=criterion, batch_x=batch_x, batch_y=batch_y)
@@ -311,6 +328,14 @@ class AdversarialGDTrainer(Trainer):
         return test_running_loss / num_total, 100 * (num_correct / num_total), eer_val
 
     # ---- attacks -------------------------------------------------------------------------------------------------------
+
+    def _noise_ops(self):
+        """The op table of the training noise: the test seam's, else the HIP kernels (loaded here: a missing library is an error)."""
+        if self.attack_ops is not None:
+            return self.attack_ops
+        from . import hip_ops
+        hip_ops._lib.load()
+        return hip_ops
 
     @staticmethod
     def _attack_batch(attack, batch_x, batch_y):

@@ -56,8 +56,9 @@ def train_nn(batch_size: int, epochs: int, device: str, config: Dict, attack_con
              amount_to_use: Tuple[int, int] = (None, None), config_save_path: str = "configs",
              adv_training_strategy: str = AdversarialGDTrainerEnum.RANDOM.name, is_finetune: bool = False,
              synthetic: Optional[Tuple[int, int]] = None, datasets_paths: List[Optional[str]] = (None, None, None),
-             wave_fake_trim: Optional[bool] = None):
-    """train_models_on_adversarial_attacks.py:50-160."""
+             wave_fake_trim: Optional[bool] = None, noise_sigma: Optional[float] = None):
+    """train_models_on_adversarial_attacks.py:50-160.  `noise_sigma` (additive): train under Gaussian noise of that level, in the
+    waveform's units (Trainer.noise_sigma); with SMOOTHADV among the attacks this is SmoothAdv training."""
     model_config = config["model"]
     model_name = model_config["name"]
     optimizer_config = model_config["optimizer"]
@@ -92,9 +93,11 @@ def train_nn(batch_size: int, epochs: int, device: str, config: Dict, attack_con
     LOGGER.info(f"Adversarial training strategy: {adv_training_strategy}")
     save_name = f"aad__{model_name}_{timestamp}"
 
-    current_model = AdversarialGDTrainerEnum[adv_training_strategy].value(
-        device=device, batch_size=batch_size, epochs=epochs, optimizer_kwargs=optimizer_config, use_scheduler=use_scheduler,
-    ).train(dataset=data_train, model=current_model, attack_model=attack_model, test_dataset=data_test,
+    trainer = AdversarialGDTrainerEnum[adv_training_strategy].value(
+        device=device, batch_size=batch_size, epochs=epochs, optimizer_kwargs=optimizer_config, use_scheduler=use_scheduler)
+    if noise_sigma is not None:
+        trainer.noise_sigma = noise_sigma
+    current_model = trainer.train(dataset=data_train, model=current_model, attack_model=attack_model, test_dataset=data_test,
             adversarial_attacks=adversarial_attacks, model_dir=model_dir, save_model_name=save_name)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -144,7 +147,7 @@ def main(args):
              adv_training_strategy=args.adv_training_strategy, is_finetune=args.finetune, synthetic=synthetic,
              config_save_path=args.config_save_path,
              datasets_paths=[args.asv_path, args.wavefake_path, args.celeb_path],
-             wave_fake_trim=False if args.no_trim else None)
+             wave_fake_trim=False if args.no_trim else None, noise_sigma=args.noise_sigma)
     if world > 1:
         dist.destroy_process_group()
 
@@ -172,6 +175,10 @@ def parse_args(argv=None):
     parser.add_argument("--no_trim", default=False, action="store_true",
                         help="real corpora: skip the SoX silence trim (needs a registered backend otherwise)")
     parser.add_argument("--config_save_path", type=str, default="configs", help="where the test config is written")
+    parser.add_argument("--noise_sigma", type=float, default=None, metavar="SIGMA",
+                        help="train under Gaussian noise N(0, SIGMA^2) in the waveform's units, added to every training batch after "
+                             "any attack (what --certify SIGMA of the evaluation certifies); with SMOOTHADV in the attack list: "
+                             "SmoothAdv training")
     return parser.parse_args(argv)
 
 
