@@ -177,4 +177,12 @@ class AttackEnum(Enum):
     SMOOTHADV_eps15 = (torchattacks.SmoothAdvPGD, {"eps": 0.15, "steps": 10, "sigma": 0.05, "samples": 8})
     SMOOTHADV_eps20 = (torchattacks.SmoothAdvPGD, {"eps": 0.20, "steps": 10, "sigma": 0.05, "samples": 8})
 
+    # --- additive members: the minimal-norm attack (torchattacks.FMN: Fast Minimum-Norm of Pintor et al., NeurIPS 2021) — the radius
+    # at which each utterance breaks as a continuous, uncapped figure: no eps_max, no outer search.  60 steps are the 60 gradient
+    # passes MINRADIUS spends; report_at = the radii of the PGD / PGDL2 triplets above.  The schedules are the paper's defaults, a
+    # choice of scale: nobody has measured what they achieve against a trained detector ---
+    FMN = (torchattacks.FMN, {"norm": "Linf", "steps": 60, "report_at": (0.0005, 0.00075, 0.001)})
+    FMN_L2 = (torchattacks.FMN, {"norm": "L2", "steps": 60, "report_at": (0.1, 0.15, 0.2)})
+    FMN200 = (torchattacks.FMN, {"norm": "Linf", "steps": 200})
+
     NO_ATTACK = (None, {})

@@ -17,7 +17,7 @@ SOURCES = [PKG / "csrc" / "advstep.hip", PKG / "csrc" / "lcnn_mfm.hip", PKG / "c
            PKG / "csrc" / "apgdl1.hip", PKG / "csrc" / "snr.hip", PKG / "csrc" / "universal.hip",
            PKG / "csrc" / "spsa.hip", PKG / "csrc" / "channel.hip", PKG / "csrc" / "l0.hip",
            PKG / "csrc" / "hsj.hip", PKG / "csrc" / "masking.hip", PKG / "csrc" / "smooth.hip",
-           PKG / "csrc" / "smoothadv.hip"]
+           PKG / "csrc" / "smoothadv.hip", PKG / "csrc" / "fmn.hip"]
 HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants (tools/gen_stft_tables.py), #included by stft_reg.h
            PKG / "csrc" / "stft_reg.h",            # the register-resident 512-point transform and overlap-add of lfcc_stft.hip and masking.hip
            PKG / "csrc" / "advstep_common.h",      # internal helpers #included by every source
@@ -34,7 +34,8 @@ HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants
            ROOT / "include" / "advstep_snr.h", ROOT / "include" / "advstep_universal.h",
            ROOT / "include" / "advstep_spsa.h", ROOT / "include" / "advstep_channel.h",
            ROOT / "include" / "advstep_l0.h", ROOT / "include" / "advstep_hsj.h", ROOT / "include" / "advstep_masking.h",
-           ROOT / "include" / "advstep_smooth.h", ROOT / "include" / "advstep_smoothadv.h"]
+           ROOT / "include" / "advstep_smooth.h", ROOT / "include" / "advstep_smoothadv.h",
+           ROOT / "include" / "advstep_fmn.h"]
 LIB = PKG / "libadvstep.so"
 STAMP = PKG / "libadvstep.so.buildkey"   # git-ignored like the library; travels with it to the GPU box
 

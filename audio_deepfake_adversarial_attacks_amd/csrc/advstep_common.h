@@ -5,7 +5,7 @@
 // the forward kernels (lcnn_conv0.hip, lcnn_wino.hip, lcnn_mfm.hip) and read back by the backward ones (lcnn_mfm.hip),
 // and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The attack files (advstep.hip, apgd.hip,
 // momentum.hip, radius.hip, perturb.hip, multiattack.hip, fab.hip, apgdl1.hip, snr.hip, universal.hip, spsa.hip, channel.hip,
-// l0.hip, hsj.hip, smooth.hip, smoothadv.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the host's rows_vec /
+// l0.hip, hsj.hip, smooth.hip, smoothadv.hip, fmn.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the host's rows_vec /
 // ROW_KERNEL_PAIR / overlaps; what depends on the 256-thread (tile, row) geometry is in row_tiles.h; fab.hip, apgdl1.hip and
 // l0.hip give a row to one 1024-thread workgroup instead: row_workgroup.h, which also holds their sort-free threshold search.
 
@@ -130,6 +130,10 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) {
     v = (v < lo) ? lo : v;
     return (v > hi) ? hi : v;
 }
+
+// Is a one-logit row misclassified?  multi_select_kernel's rule (multiattack.hip): torch.max(cat([-z, z], 1), 1) takes the first
+// maximal index, so +-0 and NaN give class 0.  radius.hip's search round and fmn.hip's row decision.
+__device__ __forceinline__ bool judged_wrong(float z, int64_t y) { return (int64_t)(z > 0.0f) != y; }
 
 // The PGD L-inf move and projection of one sample (pgd.py:74-76): advstep.hip's advstep_pgd_linf_step_f32 and spsa.hip's step,
 // which promises that entry point's bits for its estimated gradient.

@@ -86,9 +86,7 @@ __global__ __launch_bounds__(kWgThreads) void row_l2_project_kernel(const float 
 
 // ---- c. search bookkeeping ----------------------------------------------------------------------------------------------------
 
-// multi_select_kernel's rule (multiattack.hip): torch.max(cat([-z, z], 1), 1) takes the first maximal index, so +-0 and NaN
-// give class 0.
-__device__ __forceinline__ bool judged_wrong(float z, int64_t y) { return (int64_t)(z > 0.0f) != y; }
+// the row's verdict: advstep_common.h's judged_wrong (fmn.hip takes the same)
 
 __global__ __launch_bounds__(kWgThreads) void radius_begin_kernel(const float *__restrict__ z0, const int64_t *__restrict__ labels,
                                                                   float eps_max, float *__restrict__ state, int64_t B) {

@@ -1,5 +1,5 @@
 // row_tiles.h — the (tile, row) geometry of the 256-thread row kernels (advstep.hip, apgd.hip, momentum.hip, radius.hip, perturb.hip,
-// multiattack.hip, snr.hip, universal.hip, spsa.hip, hsj.hip, smooth.hip, smoothadv.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2
+// multiattack.hip, snr.hip, universal.hip, spsa.hip, hsj.hip, smooth.hip, smoothadv.hip, fmn.hip): tile addressing, the re-reduction of a row's per-tile partials, the L2
 // arithmetic that several kernels must agree on bit for bit, and the launch on the (tile, row) grid (internal, like
 // advstep_common.h, which has the rules that do not depend on this tile: scalar semantics, reductions, rows_vec, ROW_KERNEL_PAIR,
 // overlaps).
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kWgThreads) void sumsq_partial_kernel(const float *
     if (threadIdx.x == 0) part[b * C + tile] = s;
 }
 
-// ---- the PGD-L2 step's two row passes (advstep.hip and smoothadv.hip: launch scalars alpha, eps; radius.hip: the row's a, e) ----
+// ---- the PGD-L2 step's two row passes (advstep.hip and smoothadv.hip: launch scalars alpha, eps; radius.hip: the row's a, e; fmn.hip: alpha, the row's e) ----
 // One body each, so the fixed-radius and the per-row kernels agree bit for bit by construction.  `lds` holds >= 8 floats.
 
 // pass 2: gn from the grad partials; d = l2_move4; partial sum d^2

@@ -27,6 +27,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   stft_power / masking_hinge_grad / psy_step  no counterpart: the psychoacoustic masking hinge of torchattacks.PsyPGD
   smooth_noise / smooth_tally        no counterpart: the noisy copies and the votes of torchattacks.Smoothing
   smoothadv_fill / _loss_grad / _step  no counterpart: PGD on the smoothed detector's soft vote, torchattacks.SmoothAdvPGD
+  fmn_begin / fmn_norms / fmn_step   no counterpart: Fast Minimum-Norm (Pintor et al., NeurIPS 2021), torchattacks.FMN
 """
 from __future__ import annotations
 
@@ -947,6 +948,100 @@ def radius_round(adv, z, labels, first: bool, state, best_adv, out=None):
     _call("advstep_radius_round_f32", adv.device, adv, z, labels, 1 if first else 0, state, out, best_adv, B, T,
           bracket="radius_round", tensors=(adv, best_adv))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# minimal-norm attack (include/advstep_fmn.h): the iterate's row norms and the step of torchattacks.FMN
+# ---------------------------------------------------------------------------------------------------------
+
+FMN_PLANES = ("eps", "best", "found", "dnorm")  # the rows of an attack state, in the order of include/advstep_fmn.h
+FMN_NORMS = ("dsq", "dmax", "gsq", "gabs")      # the partial planes fmn_norms writes; the workspace's fifth is the L2 move's
+FMN_TILE = 4096                                 # samples per partial
+
+
+def fmn_workspace(B: int, T: int, device) -> torch.Tensor:
+    """A fresh workspace of the FMN entry points for a (B, T) batch: flat float32, five planes of one partial per (row, tile).
+    No zero-fill is needed (include/advstep_fmn.h); one stream at a time."""
+    return torch.empty(max(_lib.load().advstep_fmn_workspace_bytes(B, T), 16) // 4, dtype=torch.float32, device=device)
+
+
+def fmn_partials(ws: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    """The (4, B, C) view of the partials `fmn_norms` left in `ws` (FMN_NORMS; C = ceil(T / 4096) tiles)."""
+    C = -(-T // FMN_TILE)
+    plane = ws.numel() // 5
+    return ws[:4 * plane].view(4, plane)[:, :B * C].view(4, B, C)
+
+
+def _fmn_ws(ws: Optional[torch.Tensor], B: int, T: int, device) -> torch.Tensor:
+    if ws is None:
+        return fmn_workspace(B, T, device)
+    _require(ws, "ws")
+    if ws.device != device or ws.numel() * 4 < _lib.load().advstep_fmn_workspace_bytes(B, T):
+        raise ValueError(f"ws must be fmn_workspace({B}, {T}) on {device}, got {ws.numel()} floats on {ws.device}")
+    return ws
+
+
+def fmn_begin(state=None, B: Optional[int] = None, device=None):
+    """The attack state (4, B) = eps, best, found, dnorm (FMN_PLANES) before the first step: eps = best = +inf, found = 0."""
+    if state is None:
+        state = torch.empty((len(FMN_PLANES), int(B)), dtype=torch.float32, device=device)
+    _require(state, "state")
+    if state.dim() != 2 or state.shape[0] != len(FMN_PLANES):
+        raise ValueError(f"state must be ({len(FMN_PLANES)}, B), got {tuple(state.shape)}")
+    _call("advstep_fmn_begin_f32", state.device, state, state.shape[1], bracket="fmn_begin")
+    return state
+
+
+def fmn_norms(adv, grad, orig, ws=None):
+    """Per-(row, tile) partials of sum d^2, max |d|, sum g^2 and sum |g| (d = adv - orig, g = grad; grad None: the g planes get
+    0), left in the workspace `ws` (a fresh `fmn_workspace` when None), which is returned for `fmn_step`; `fmn_partials` views
+    them.  One launch, 12 B per sample, no host read."""
+    _require(adv, "adv"), _require(orig, "orig")
+    _same_shape(("adv", adv), ("orig", orig))
+    if grad is not None:
+        _require(grad, "grad")
+        _same_shape(("adv", adv), ("grad", grad))
+    B, T = _rows(adv, "adv")
+    ws = _fmn_ws(ws, B, T, adv.device)
+    _call("advstep_fmn_norms_f32", adv.device, adv, grad, orig, B, T, ws, ws.numel() * 4, bracket="fmn_norms",
+          tensors=(adv, grad, orig))
+    return ws
+
+
+def fmn_step(adv, grad, orig, z, labels, state, best_adv, ws, alpha: float, gamma: float, norm: str = "Linf", move: bool = True,
+             eps_div: float = 1e-10, lo: float = 0.0, hi: float = 1.0, state_out=None, out=None, row_norms=None):
+    """One step of the FMN recurrence after `fmn_norms` of the same adv, grad, orig left its partials in `ws` (z = the logit of
+    model(adv), grad = dz / d adv turned towards the other class): the row's decision from `state` into `state_out` (another
+    (4, B) buffer: the launch only reads `state`), the row's iterate into `best_adv` iff it is adversarial and smaller than
+    every earlier one, then the move and the projection into the row's new radius (include/advstep_fmn.h has the expressions).
+    move=False is the last call: decision and copy only, grad may be None.  Returns (state_out, out) — out is None when
+    move=False.  row_norms: an optional (5, B) tensor that receives the row norms the decision used.  No host read."""
+    _require(adv, "adv"), _require(orig, "orig"), _require(best_adv, "best_adv"), _require(z, "z")
+    _same_shape(("adv", adv), ("orig", orig), ("best_adv", best_adv))
+    if grad is not None:
+        _require(grad, "grad")
+        _same_shape(("adv", adv), ("grad", grad))
+    elif move:
+        raise ValueError("fmn_step needs the gradient to move (grad=None only with move=False)")
+    B, T = _rows(adv, "adv")
+    if z.numel() != B or z.device != adv.device:
+        raise ValueError(f"z must hold one logit per row of adv ({B}) on {adv.device}, got {tuple(z.shape)}@{z.device}")
+    _per_row(labels, "labels", B, torch.int64)
+    kind = _apgd_norm(norm)
+    if not 0.0 < float(gamma) < 1.0:
+        raise ValueError(f"gamma must lie in (0, 1), got {gamma}")
+    _shaped(_require(state, "state"), "state", (len(FMN_PLANES), B), adv.device)
+    state_out = _shaped(state_out, "state_out", (len(FMN_PLANES), B), adv.device)
+    if row_norms is not None:
+        _shaped(_require(row_norms, "row_norms"), "row_norms", (5, B), adv.device)
+    ws = _fmn_ws(_require(ws, "ws"), B, T, adv.device)
+    out = _out_like(adv, out) if move else None
+    # compulsory traffic: adv, grad, orig and out once (the L2 form reads the three inputs twice); improved rows move once more
+    traffic = (adv, grad, orig, out) + ((adv, grad, orig) if kind == 1 else ()) if move else ()
+    _call("advstep_fmn_step_f32", adv.device, adv, grad, orig, z, labels, state, state_out, best_adv, out, row_norms, float(alpha),
+          float(gamma), kind, 1 if move else 0, float(eps_div), lo, hi, B, T, ws, ws.numel() * 4, bracket="fmn_step",
+          tensors=traffic)
+    return state_out, out
 
 
 # ---------------------------------------------------------------------------------------------------------

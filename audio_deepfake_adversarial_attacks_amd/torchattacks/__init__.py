@@ -10,7 +10,8 @@ simulated audio channel: `Channel`, `CHANNELS`) and PGDL0 (the sparse threat mod
 black-box attack: decisions instead of scores) and PsyPGD (PGD pulled under the psychoacoustic masking threshold of the clean
 utterance: `MaskingModel`), and beside them `Smoothing`, which is no attack: randomized smoothing's votes over noisy copies, for a
 certified lower bound on the radius the attacks bound from above, and SmoothAdvPGD (PGD on that smoothed detector's soft vote: the
-adversary the certificate has to withstand), with the reference's constructor
+adversary the certificate has to withstand) and FMN (the minimal-norm attack: every utterance's radius in one run, without a
+largest radius and without an outer search), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -19,6 +20,7 @@ from .attacks.cw import CW
 from .attacks.eotpgd import EOTPGD
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
+from .attacks.fmn import FMN
 from .attacks.hopskipjump import HopSkipJump
 from .attacks.mifgsm import MIFGSM
 from .attacks.minradius import MinRadiusPGD
@@ -41,4 +43,4 @@ from .smoothing import Smoothing
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
-           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing", "SmoothAdvPGD"]
+           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing", "SmoothAdvPGD", "FMN"]
