@@ -185,4 +185,13 @@ class AttackEnum(Enum):
     FMN_L2 = (torchattacks.FMN, {"norm": "L2", "steps": 60, "report_at": (0.1, 0.15, 0.2)})
     FMN200 = (torchattacks.FMN, {"norm": "Linf", "steps": 200})
 
+    # --- additive members: the sparse forms of the minimal-norm attack (torchattacks.FMNSparse) — the L1 norm and the number of changed
+    # samples at which each utterance breaks, where APGDL1 and PGDL0 above only answer at fixed budgets; report_at = the radii of
+    # the APGDL1 triplet and the budgets of the PGDL0 triplet.  The L0 member sets gamma_init itself: the paper's 0.05 grows an
+    # integer radius by +1 per step (floor(1.05 eps) <= eps + 1 below eps = 20, and gamma is annealed while eps grows), so 100 steps
+    # first meet 64 samples at step 63 and end at 101, short of 256 and 1024.  Steps, schedules and gamma_init = 0.3 are
+    # choices of scale: nobody has measured what they achieve against a trained detector ---
+    FMN_L1 = (torchattacks.FMNSparse, {"norm": "L1", "steps": 100, "report_at": (20.0, 30.0, 40.0)})
+    FMN_L0 = (torchattacks.FMNSparse, {"norm": "L0", "steps": 100, "gamma_init": 0.3, "report_at": (64, 256, 1024)})
+
     NO_ATTACK = (None, {})

@@ -17,12 +17,14 @@ SOURCES = [PKG / "csrc" / "advstep.hip", PKG / "csrc" / "lcnn_mfm.hip", PKG / "c
            PKG / "csrc" / "apgdl1.hip", PKG / "csrc" / "snr.hip", PKG / "csrc" / "universal.hip",
            PKG / "csrc" / "spsa.hip", PKG / "csrc" / "channel.hip", PKG / "csrc" / "l0.hip",
            PKG / "csrc" / "hsj.hip", PKG / "csrc" / "masking.hip", PKG / "csrc" / "smooth.hip",
-           PKG / "csrc" / "smoothadv.hip", PKG / "csrc" / "fmn.hip"]
+           PKG / "csrc" / "smoothadv.hip", PKG / "csrc" / "fmn.hip",
+           PKG / "csrc" / "fmn_sparse.hip"]
 HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants (tools/gen_stft_tables.py), #included by stft_reg.h
            PKG / "csrc" / "stft_reg.h",            # the register-resident 512-point transform and overlap-add of lfcc_stft.hip and masking.hip
            PKG / "csrc" / "advstep_common.h",      # internal helpers #included by every source
            PKG / "csrc" / "row_tiles.h",           # (tile, row) addressing, partial re-reductions, shared L2 arithmetic and launch of every row kernel
-           PKG / "csrc" / "row_workgroup.h",       # one 1024-thread workgroup per row: fab.hip's, apgdl1.hip's and l0.hip's reduction, traversal, digit-walk search, launch
+           PKG / "csrc" / "row_workgroup.h",       # one 1024-thread workgroup per row: fab.hip's, apgdl1.hip's, l0.hip's and fmn_sparse.hip's reduction, traversal, digit-walk search, launch
+           PKG / "csrc" / "row_project.h",         # the L1 and L0 row projections that apgdl1.hip, l0.hip and fmn_sparse.hip all instantiate
            PKG / "csrc" / "direction_bits.h",      # the Philox direction bits spsa.hip and hsj.hip both regenerate
            PKG / "csrc" / "smooth_fill.h",         # the noised-slot fill that smooth.hip and smoothadv.hip both instantiate
            PKG / "csrc" / "lcnn_wino_plan.h",      # lcnn_wino.hip's enumerators, predicates and launch plan (host side)
@@ -35,7 +37,7 @@ HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants
            ROOT / "include" / "advstep_spsa.h", ROOT / "include" / "advstep_channel.h",
            ROOT / "include" / "advstep_l0.h", ROOT / "include" / "advstep_hsj.h", ROOT / "include" / "advstep_masking.h",
            ROOT / "include" / "advstep_smooth.h", ROOT / "include" / "advstep_smoothadv.h",
-           ROOT / "include" / "advstep_fmn.h"]
+           ROOT / "include" / "advstep_fmn.h", ROOT / "include" / "advstep_fmn_sparse.h"]
 LIB = PKG / "libadvstep.so"
 STAMP = PKG / "libadvstep.so.buildkey"   # git-ignored like the library; travels with it to the GPU box
 

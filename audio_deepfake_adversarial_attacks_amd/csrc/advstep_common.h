@@ -5,9 +5,10 @@
 // the forward kernels (lcnn_conv0.hip, lcnn_wino.hip, lcnn_mfm.hip) and read back by the backward ones (lcnn_mfm.hip),
 // and the dB backward of the plain and the fused LFCC tails (lfcc.hip, lfcc_stft.hip).  The attack files (advstep.hip, apgd.hip,
 // momentum.hip, radius.hip, perturb.hip, multiattack.hip, fab.hip, apgdl1.hip, snr.hip, universal.hip, spsa.hip, channel.hip,
-// l0.hip, hsj.hip, smooth.hip, smoothadv.hip, fmn.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the host's rows_vec /
+// l0.hip, hsj.hip, smooth.hip, smoothadv.hip, fmn.hip, fmn_sparse.hip) share the scalar semantics, the reduction operators with the wave butterfly, and the host's rows_vec /
 // ROW_KERNEL_PAIR / overlaps; what depends on the 256-thread (tile, row) geometry is in row_tiles.h; fab.hip, apgdl1.hip and
-// l0.hip give a row to one 1024-thread workgroup instead: row_workgroup.h, which also holds their sort-free threshold search.
+// l0.hip (and fmn_sparse.hip, which shares their projections: row_project.h) give a row to one 1024-thread workgroup instead:
+// row_workgroup.h, which also holds their sort-free threshold search.
 
 #ifndef ADVSTEP_COMMON_H
 #define ADVSTEP_COMMON_H

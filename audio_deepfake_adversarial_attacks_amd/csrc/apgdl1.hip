@@ -22,6 +22,7 @@
 #include "advstep_apgdl1.h"
 #include "advstep_common.h"
 #include "row_workgroup.h"
+#include "row_project.h"
 
 namespace {
 
@@ -29,49 +30,7 @@ constexpr uint8_t kImproved = 2, kReset = 4;           // the flag bits of inclu
 
 // ---- the projection --------------------------------------------------------------------------------------------------
 
-// m_i(lam) = min(max(|d_i| - lam, 0), cap_i): how far coordinate i moves from x_i towards u_i.  The median of the three is
-// that value whenever 0 <= cap (x in [0, 1]), in one instruction instead of two; the searches' passes are VALU-bound.
-__device__ __forceinline__ float l1_move(float ad, float cap, float lam) {
-    return __builtin_amdgcn_fmed3f(ad - lam, 0.0f, cap);
-}
-__device__ __forceinline__ float l1_cap(float d, float xi) { return d > 0.0f ? 1.0f - xi : xi; }
-
-// (the search passes traverse with row_workgroup.h's visit_rows_ahead: the next element's loads before this one's arithmetic)
-
-// out row = P(u row; x row, eps), phi0 = phi(0) as the caller's pass over (x, u) summed it.  ur may be outr.
-template <bool VEC>
-__device__ __forceinline__ void l1_box_project_row(const float *xr, const float *ur, float *outr, int64_t T, float eps,
-                                                   float phi0, float *lds) {
-    float lam = 0.0f;
-    if (phi0 > eps) {                                          // workgroup-uniform: every thread holds the same phi0
-        // rho = the largest bit pattern with phi > eps (phi(0) > eps: it exists); lam* is the next float
-        float h[kCand];
-        const uint32_t rho = digit_search(
-            31, h, lds,
-            [&](uint32_t lo, int shift, float(&hh)[kCand]) {   // bin k = phi at candidate k + 1 itself: nothing to accumulate
-                float cand[kCand];
-#pragma unroll
-                for (int k = 0; k < kCand; ++k) cand[k] = __uint_as_float(lo | ((uint32_t)(k + 1) << shift));
-                visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float (&xu)[2]) {
-                    const float d = xu[1] - xu[0], ad = fabsf(d), cap = l1_cap(d, xu[0]);
-#pragma unroll
-                    for (int k = 0; k < kCand; ++k) hh[k] += l1_move(ad, cap, cand[k]);
-                });
-            },
-            [&](float phi) { return phi > eps; });             // phi is non-increasing: the first candidate that fits ends the scan
-        lam = __uint_as_float(rho + 1u);
-    }
-    map_rows<VEC>({xr, ur}, outr, T, [&](float xi, float ui) {
-        const float d = ui - xi;
-        return clampf(xi + sgn(d) * l1_move(fabsf(d), l1_cap(d, xi), lam), 0.0f, 1.0f);
-    });
-}
-
-// one term of phi(0) for the sample (x_i, u_i)
-__device__ __forceinline__ float l1_move0(float xi, float ui) {
-    const float d = ui - xi;
-    return l1_move(fabsf(d), l1_cap(d, xi), 0.0f);
-}
+// l1_move, l1_cap, l1_move0 and l1_box_project_row are row_project.h's (fmn_sparse.hip projects with them too)
 
 template <bool VEC>
 __global__ __launch_bounds__(kRow) void l1_box_project_kernel(const float *__restrict__ x, const float *u, float *out,

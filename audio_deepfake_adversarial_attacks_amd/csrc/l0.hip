@@ -20,78 +20,11 @@
 #include "advstep_common.h"
 #include "advstep_l0.h"
 #include "row_workgroup.h"
+#include "row_project.h"
 
 namespace {
 
-// c_i of include/advstep_l0.h: d clipped to what the box and the cap leave of it
-__device__ __forceinline__ float l0_clip(float d, float xi, float cap) {
-    const float lb = -xi > -cap ? -xi : -cap, ub = 1.0f - xi < cap ? 1.0f - xi : cap;
-    return clampf(d, lb, ub);
-}
-// the bit pattern of s_i (>= 0, so patterns order like scores; the mask keeps a NaN's inside the 31 searched bits)
-__device__ __forceinline__ uint32_t l0_key(float xi, float ui, float cap) {
-    const float d = ui - xi, r = d - l0_clip(d, xi, cap);
-    return __float_as_uint(d * d - r * r) & 0x7FFFFFFFu;
-}
-
-// out row = P0(u row; x row, kk = min(k, T), cap).  ur may be outr.  stats: the row's four floats or NULL; stats[0] is the caller's.
-template <bool VEC>
-__device__ __forceinline__ void l0_project_row(const float *xr, const float *ur, float *outr, int64_t T, float kk, float cap,
-                                               float *stats, float *lds) {
-    // rho = the largest pattern with #{key >= rho} >= kk, which is the kk-th largest key; `above` is that count
-    float h[kCand], above = (float)T;
-    const uint32_t rho = digit_search(
-        31, h, lds,
-        [&](uint32_t lo, int shift, float(&hh)[kCand]) {
-            visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](const float(&xu)[2]) {
-                bucket_add(hh, l0_key(xu[0], xu[1], cap), lo, shift, 1.0f);
-            });
-        },
-        [&](float hj) {                                        // #{key >= candidate j} = above - h[0..j): non-increasing in j
-            const float at = above - hj;
-            if (!(at >= kk)) return false;
-            above = at;
-            return true;
-        });
-    const float eq = (rho & 1u) ? h[1] : h[0];                 // the last pass has one bit: h[pick] = #{key == rho}
-    const float gt = above - eq;                               // #{key > rho} < kk <= above
-    // the cut: the smallest index with #{i <= cut : key_i == rho} = kk - gt, wanted only where ties exceed what is left of kk.
-    // cut = the largest c with #{i < c : key_i == rho} < need, found like rho, over the bits of an index
-    int64_t cut = T;
-    if (above > kk) {                                          // workgroup-uniform: every thread holds the same counts
-        const float need = kk - gt;
-        float below = 0.0f;
-        cut = (int64_t)digit_search(
-            32 - __clz((int)(T - 1)), h, lds,                  // T - 1 >= 1 here (above > kk >= 1)
-            [&](uint32_t c, int shift, float(&hh)[kCand]) {
-                visit_rows_ahead<VEC, 2>({xr, ur}, T, [&](int64_t i, const float(&xu)[2]) {
-                    if (l0_key(xu[0], xu[1], cap) == rho) bucket_add(hh, (uint32_t)i, c, shift, 1.0f);
-                });
-            },
-            [&](float hj) {                                    // #{i < candidate j : tie} = below + h[0..j)
-                const float at = below + hj;
-                if (!(at < need)) return false;
-                below = at;
-                return true;
-            });
-    }
-    float last[1] = {-1.0f};                                   // the last kept tie (a thread's indices ascend)
-    map_rows<VEC>({xr, ur}, outr, T, [&](int64_t i, float xi, float ui) {
-        const float d = ui - xi, ci = l0_clip(d, xi, cap), r = d - ci;
-        const uint32_t key = __float_as_uint(d * d - r * r) & 0x7FFFFFFFu;
-        const bool tie = key == rho && i <= cut;
-        if (tie) last[0] = (float)i;
-        return (key > rho || tie) ? clampf(xi + ci, 0.0f, 1.0f) : xi;
-    });
-    if (stats) {                                               // a kernel argument: uniform
-        row_reduce<1>(last, MaxNanOp(), lds);
-        if (threadIdx.x == 0) {
-            stats[1] = __uint_as_float(rho);
-            stats[2] = gt;
-            stats[3] = last[0];
-        }
-    }
-}
+// l0_clip, l0_key and l0_project_row are row_project.h's (fmn_sparse.hip projects with them too)
 
 template <bool VEC>
 __global__ __launch_bounds__(kRow) void l0_box_project_kernel(const float *__restrict__ x, const float *u, float *out,

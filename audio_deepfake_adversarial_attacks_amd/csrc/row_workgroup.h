@@ -1,4 +1,4 @@
-// row_workgroup.h — the one-workgroup-per-row geometry of fab.hip, apgdl1.hip and l0.hip (internal: not part of the C ABI in include/).
+// row_workgroup.h — the one-workgroup-per-row geometry of fab.hip, apgdl1.hip, l0.hip and fmn_sparse.hip (internal: not part of the C ABI in include/).
 //
 // One workgroup of kRow = 1024 threads (16 wave64) owns one row of T samples and makes several passes over it; at the repo's
 // T = 64 600 a row is 258 KB: it does not fit LDS, but stays L2 / Infinity-Cache resident between the passes, so only the first
@@ -49,30 +49,52 @@ __device__ __forceinline__ void row_reduce(float (&v)[NV], Op op, float *lds) {
 
 // The one row traversal: f(a_i, b_i, ...) over the samples of the N rows `in`, or f(i, a_i, b_i, ...) where f takes the sample
 // index.  The index form is chosen iff f is callable with N + 1 arguments, so f must have a fixed arity (no generic lambda).
-// VEC: quads q = threadIdx.x, += kRow, lanes x, y, z, w in order, one float4 load per row; otherwise samples
-// i = threadIdx.x, += kRow.  That order is each thread's accumulation order, so part of every reduced result's bits.
-// STORE: out_i = f(...), one float4 store per quad after all of the quad's loads.  out may alias an input (no __restrict__).
+// ROUTE (a kernel's bool VEC converts to the first two): kRouteQuads: quads q = threadIdx.x, += kRow, lanes x, y, z, w in order,
+// one float4 load per row; kRouteSamples: samples i = threadIdx.x, += kRow; kRouteQuadsBySample (fmn_sparse.hip, T % 4 == 0 with
+// a base that is not 16-byte aligned): the quads' sample -> thread map and order with four 4-byte accesses per quad, so every
+// reduced result has kRouteQuads' bits.  That order is each thread's accumulation order, so part of every reduced result's bits.
+// STORE: out_i = f(...), one store per quad after all of the quad's loads.  out may alias an input (no __restrict__).
+enum : int { kRouteSamples = 0, kRouteQuads = 1, kRouteQuadsBySample = 2 };
+static_assert((int)false == kRouteSamples && (int)true == kRouteQuads, "a kernel's VEC selects the first two routes");
+
+template <int ROUTE>
+__device__ __forceinline__ float4 load_quad(const float *p, int64_t q) {
+    if constexpr (ROUTE == kRouteQuads) return reinterpret_cast<const float4 *>(p)[q];
+    else return make_float4(p[4 * q], p[4 * q + 1], p[4 * q + 2], p[4 * q + 3]);
+}
+template <int ROUTE>
+__device__ __forceinline__ void store_quad(float *p, int64_t q, float4 v) {
+    if constexpr (ROUTE == kRouteQuads) {
+        reinterpret_cast<float4 *>(p)[q] = v;
+    } else {
+        p[4 * q] = v.x;
+        p[4 * q + 1] = v.y;
+        p[4 * q + 2] = v.z;
+        p[4 * q + 3] = v.w;
+    }
+}
+
 template <size_t>
 using Sample = float;
 
-template <bool VEC, bool STORE, class F, size_t... K>
+template <int ROUTE, bool STORE, class F, size_t... K>
 __device__ __forceinline__ void traverse(const float *const (&in)[sizeof...(K)], float *out, int64_t T, F f,
                                          std::index_sequence<K...>) {
     auto at = [&](int64_t i, Sample<K>... s) {
         if constexpr (std::is_invocable_v<F, int64_t, Sample<K>...>) return f(i, s...);
         else return f(s...);
     };
-    if constexpr (VEC) {
+    if constexpr (ROUTE != kRouteSamples) {
         const int64_t n4 = T >> 2;
         for (int64_t q = threadIdx.x; q < n4; q += kRow) {
-            const float4 v[] = {reinterpret_cast<const float4 *>(in[K])[q]...};
+            const float4 v[] = {load_quad<ROUTE>(in[K], q)...};
             if constexpr (STORE) {
                 float4 o;
                 o.x = at(4 * q, v[K].x...);
                 o.y = at(4 * q + 1, v[K].y...);
                 o.z = at(4 * q + 2, v[K].z...);
                 o.w = at(4 * q + 3, v[K].w...);
-                reinterpret_cast<float4 *>(out)[q] = o;
+                store_quad<ROUTE>(out, q, o);
             } else {
                 at(4 * q, v[K].x...);
                 at(4 * q + 1, v[K].y...);
@@ -87,21 +109,26 @@ __device__ __forceinline__ void traverse(const float *const (&in)[sizeof...(K)],
         }
     }
 }
-template <bool VEC, size_t N, class F>
+template <int ROUTE, size_t N, class F>
 __device__ __forceinline__ void visit_rows(const float *const (&in)[N], int64_t T, F f) {
-    traverse<VEC, false>(in, nullptr, T, f, std::make_index_sequence<N>());
+    traverse<ROUTE, false>(in, nullptr, T, f, std::make_index_sequence<N>());
 }
-template <bool VEC, size_t N, class F>
+template <int ROUTE, size_t N, class F>
 __device__ __forceinline__ void map_rows(const float *const (&in)[N], float *out, int64_t T, F f) {
-    traverse<VEC, true>(in, out, T, f, std::make_index_sequence<N>());
+    traverse<ROUTE, true>(in, out, T, f, std::make_index_sequence<N>());
 }
 
 // visit_rows for the search passes of apgdl1.hip and l0.hip: f(s) with s[k] = the sample of row in[k], or f(i, s) where f takes
 // the sample index, in visit_rows' order and sample -> thread map, but with the next element's loads issued before this
 // element's arithmetic (with one quad per thread in flight a pass waits out a full L2 latency per quad).
-template <bool VEC, int N, class F>
+template <int ROUTE, int N, class F>
 __device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], int64_t T, F f) {
+    constexpr bool VEC = ROUTE != kRouteSamples;
     using Elem = std::conditional_t<VEC, float4, float>;
+    auto load = [](const float *p, int64_t e) {
+        if constexpr (VEC) return load_quad<ROUTE>(p, e);
+        else return p[e];
+    };
     auto at = [&](int64_t i, const float(&s)[N]) {
         if constexpr (std::is_invocable_v<F, int64_t, const float(&)[N]>) f(i, s);
         else f(s);
@@ -111,7 +138,7 @@ __device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], in
     Elem next[N];
     if (e < n) {
 #pragma unroll
-        for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e];
+        for (int k = 0; k < N; ++k) next[k] = load(in[k], e);
     }
     for (; e < n; e += kRow) {
         Elem v[N];
@@ -119,7 +146,7 @@ __device__ __forceinline__ void visit_rows_ahead(const float *const (&in)[N], in
         for (int k = 0; k < N; ++k) v[k] = next[k];
         if (e + kRow < n) {
 #pragma unroll
-            for (int k = 0; k < N; ++k) next[k] = reinterpret_cast<const Elem *>(in[k])[e + kRow];
+            for (int k = 0; k < N; ++k) next[k] = load(in[k], e + kRow);
         }
         float s[N];
         if constexpr (VEC) {

@@ -28,6 +28,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   smooth_noise / smooth_tally        no counterpart: the noisy copies and the votes of torchattacks.Smoothing
   smoothadv_fill / _loss_grad / _step  no counterpart: PGD on the smoothed detector's soft vote, torchattacks.SmoothAdvPGD
   fmn_begin / fmn_norms / fmn_step   no counterpart: Fast Minimum-Norm (Pintor et al., NeurIPS 2021), torchattacks.FMN
+  fmn_sparse_step                    no counterpart: its L1 and L0 forms in one fused row launch, torchattacks.FMNSparse
 """
 from __future__ import annotations
 
@@ -1041,6 +1042,46 @@ def fmn_step(adv, grad, orig, z, labels, state, best_adv, ws, alpha: float, gamm
     _call("advstep_fmn_step_f32", adv.device, adv, grad, orig, z, labels, state, state_out, best_adv, out, row_norms, float(alpha),
           float(gamma), kind, 1 if move else 0, float(eps_div), lo, hi, B, T, ws, ws.numel() * 4, bracket="fmn_step",
           tensors=traffic)
+    return state_out, out
+
+
+FMN_SPARSE_NORMS = ("dabs", "dcnt", "gsq", "gmax")   # the row norms fmn_sparse_step's decision uses (include/advstep_fmn_sparse.h)
+_FMN_SPARSE_KINDS = {"L1": 2, "L0": 3}               # include/advstep_fmn.h's numbering, continued
+
+
+def fmn_sparse_step(adv, grad, orig, z, labels, state, best_adv, alpha: float, gamma: float, norm: str, move: bool = True,
+                    eps_div: float = 1e-10, state_out=None, out=None, row_norms=None):
+    """One step of the FMN recurrence for the L1 or the L0 threat model, ONE launch without a workspace (z = the logit of
+    model(adv), grad = dz / d adv turned towards the other class): the row's norms, its decision from `state` into `state_out`
+    (another (4, B) buffer: the launch only reads `state`), the row's iterate into `best_adv` iff it is adversarial and smaller
+    than every earlier one, then the move and the exact projection (L1 ball or k-sparse set, intersected with the box [0, 1])
+    into the row's NEW radius (include/advstep_fmn_sparse.h has the expressions).  move=False is the last call: decision and
+    copy only, grad may be None.  Returns (state_out, out) — out is None when move=False.  row_norms: an optional (4, B) tensor
+    that receives FMN_SPARSE_NORMS as the decision used them.  No host read."""
+    _require(adv, "adv"), _require(orig, "orig"), _require(best_adv, "best_adv"), _require(z, "z")
+    _same_shape(("adv", adv), ("orig", orig), ("best_adv", best_adv))
+    if grad is not None:
+        _require(grad, "grad")
+        _same_shape(("adv", adv), ("grad", grad))
+    elif move:
+        raise ValueError("fmn_sparse_step needs the gradient to move (grad=None only with move=False)")
+    B, T = _rows(adv, "adv")
+    if z.numel() != B or z.device != adv.device:
+        raise ValueError(f"z must hold one logit per row of adv ({B}) on {adv.device}, got {tuple(z.shape)}@{z.device}")
+    _per_row(labels, "labels", B, torch.int64)
+    if norm not in _FMN_SPARSE_KINDS:
+        raise ValueError(f"fmn_sparse_step norm must be 'L1' or 'L0', got {norm!r}")
+    if not 0.0 < float(gamma) < 1.0:
+        raise ValueError(f"gamma must lie in (0, 1), got {gamma}")
+    _shaped(_require(state, "state"), "state", (len(FMN_PLANES), B), adv.device)
+    state_out = _shaped(state_out, "state_out", (len(FMN_PLANES), B), adv.device)
+    if row_norms is not None:
+        _shaped(_require(row_norms, "row_norms"), "row_norms", (len(FMN_SPARSE_NORMS), B), adv.device)
+    out = _out_like(adv, out) if move else None
+    # compulsory traffic: adv, grad, orig and out once (every later pass re-reads the row from cache); improved rows move once more
+    _call("advstep_fmn_sparse_step_f32", adv.device, adv, grad, orig, z, labels, state, state_out, best_adv, out, row_norms,
+          float(alpha), float(gamma), _FMN_SPARSE_KINDS[norm], 1 if move else 0, float(eps_div), B, T, bracket="fmn_sparse_step",
+          tensors=(adv, grad, orig, out) if move else (adv, orig))
     return state_out, out
 
 

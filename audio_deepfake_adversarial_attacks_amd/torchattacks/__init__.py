@@ -11,7 +11,8 @@ black-box attack: decisions instead of scores) and PsyPGD (PGD pulled under the 
 utterance: `MaskingModel`), and beside them `Smoothing`, which is no attack: randomized smoothing's votes over noisy copies, for a
 certified lower bound on the radius the attacks bound from above, and SmoothAdvPGD (PGD on that smoothed detector's soft vote: the
 adversary the certificate has to withstand) and FMN (the minimal-norm attack: every utterance's radius in one run, without a
-largest radius and without an outer search), with the reference's constructor
+largest radius and without an outer search) and FMNSparse (its L1 and L0 forms: the minimal L1 norm and the minimal number of
+changed samples), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -21,6 +22,7 @@ from .attacks.eotpgd import EOTPGD
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
 from .attacks.fmn import FMN
+from .attacks.fmn_sparse import FMNSparse
 from .attacks.hopskipjump import HopSkipJump
 from .attacks.mifgsm import MIFGSM
 from .attacks.minradius import MinRadiusPGD
@@ -43,4 +45,5 @@ from .smoothing import Smoothing
 __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
-           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing", "SmoothAdvPGD", "FMN"]
+           "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing", "SmoothAdvPGD", "FMN",
+           "FMNSparse"]

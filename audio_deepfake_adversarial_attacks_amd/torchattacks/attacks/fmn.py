@@ -54,8 +54,9 @@ class FMN(Attack):
 
     The defaults are the paper's and are choices of scale: nobody has measured what they achieve against a trained detector.
 
-    Out of scope: L1 and L0 (their projections exist, csrc/apgdl1.hip and csrc/l0.hip), targeted mode, restarts, and hipGraph
-    replay (a captured graph returns only the gradient, and the step also needs the pass's logit).
+    Out of scope here: L1 and L0 (torchattacks.FMNSparse runs this recurrence with the projections of csrc/apgdl1.hip and
+    csrc/l0.hip), targeted mode, restarts, and hipGraph replay (a captured graph returns only the gradient, and the step also
+    needs the pass's logit).
 
     Examples::
         >>> attack = torchattacks.FMN(model, norm="L2", steps=60)
