@@ -17,7 +17,7 @@ ABI_VERSION = 3
 _p, _i64, _f32, _f64, _u64, _sz = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_double,
                                    ctypes.c_uint64, ctypes.c_size_t)
 
-# name -> (restype, argtypes); one entry per symbol declared in include/advstep.h, advstep_lcnn.h, advstep_frontend.h, advstep_fab.h, advstep_dataset.h, advstep_detector.h, advstep_apgd.h, advstep_momentum.h, advstep_multi.h, advstep_perturb.h, advstep_radius.h, advstep_apgdl1.h, advstep_snr.h, advstep_universal.h, advstep_spsa.h, advstep_channel.h, advstep_l0.h, advstep_hsj.h, advstep_masking.h, advstep_smooth.h, advstep_smoothadv.h, advstep_fmn.h and advstep_fmn_sparse.h
+# name -> (restype, argtypes); one entry per symbol declared in include/advstep.h, advstep_lcnn.h, advstep_frontend.h, advstep_fab.h, advstep_dataset.h, advstep_detector.h, advstep_apgd.h, advstep_momentum.h, advstep_multi.h, advstep_perturb.h, advstep_radius.h, advstep_apgdl1.h, advstep_snr.h, advstep_universal.h, advstep_spsa.h, advstep_channel.h, advstep_l0.h, advstep_hsj.h, advstep_masking.h, advstep_smooth.h, advstep_smoothadv.h, advstep_fmn.h, advstep_fmn_sparse.h and advstep_filter.h
 SIGNATURES = {
     "advstep_abi_version": (ctypes.c_int, []),
     "advstep_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -227,6 +227,12 @@ SIGNATURES = {
     # include/advstep_fmn_sparse.h
     "advstep_fmn_sparse_step_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _f32, ctypes.c_int, ctypes.c_int,
                                                    _f32, _i64, _i64, _p]),
+    # include/advstep_filter.h
+    "advstep_filter_apply_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _f32, _p]),
+    "advstep_filter_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "advstep_filter_tap_grad_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _f32, _f32, _p]),
+    "advstep_filter_tap_update_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f64, _f64, _f64, _f64,
+                                                     ctypes.c_int, _p]),
 }
 
 

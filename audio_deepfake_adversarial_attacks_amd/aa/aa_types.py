@@ -119,6 +119,15 @@ class AttackEnum(Enum):
     UAP_SPOOF_eps001 = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001, "source_label": 0})
     UAP_WAVE_SPOOF = (torchattacks.UniversalPGD, {"norm": "Linf", "eps": 0.001, "source_label": 0, "domain": "waveform"})
 
+    # --- additive members: one FIR filter for every fake (torchattacks.UniversalFilter, after Malafide: the convolutive threat
+    # model), fitted and applied through the universal protocol above (universal_fit / universal_load / universal_save).  The
+    # budget is the filter's length: 129 taps are 8 ms at 16 kHz, 257 are 16 ms, 1025 are 64 ms; label 0 is spoof.  The lengths,
+    # lr = 0.02 and 5 epochs are choices of scale: nobody has measured what they achieve against a trained detector, and they are
+    # not taken from the paper ---
+    FILTER_SPOOF = (torchattacks.UniversalFilter, {"taps": 129, "source_label": 0})
+    FILTER_SPOOF_L257 = (torchattacks.UniversalFilter, {"taps": 257, "source_label": 0})
+    FILTER_SPOOF_L1025 = (torchattacks.UniversalFilter, {"taps": 1025, "source_label": 0})
+
     # --- additive members: the score-based black-box attack (torchattacks.SPSA: the attacker reads the detector's score and
     # takes no gradient), at the radii of the PGD triplet above.  20 steps of 8 direction pairs are 20 * 17 = 340 queries per
     # utterance, SPSA100_eps003 (PGD40_eps003's radius) 100 * 33 = 3300.  These budgets are choices of scale: nobody has

@@ -18,7 +18,7 @@ SOURCES = [PKG / "csrc" / "advstep.hip", PKG / "csrc" / "lcnn_mfm.hip", PKG / "c
            PKG / "csrc" / "spsa.hip", PKG / "csrc" / "channel.hip", PKG / "csrc" / "l0.hip",
            PKG / "csrc" / "hsj.hip", PKG / "csrc" / "masking.hip", PKG / "csrc" / "smooth.hip",
            PKG / "csrc" / "smoothadv.hip", PKG / "csrc" / "fmn.hip",
-           PKG / "csrc" / "fmn_sparse.hip"]
+           PKG / "csrc" / "fmn_sparse.hip", PKG / "csrc" / "filter.hip"]
 HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants (tools/gen_stft_tables.py), #included by stft_reg.h
            PKG / "csrc" / "stft_reg.h",            # the register-resident 512-point transform and overlap-add of lfcc_stft.hip and masking.hip
            PKG / "csrc" / "advstep_common.h",      # internal helpers #included by every source
@@ -27,7 +27,8 @@ HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants
            PKG / "csrc" / "row_project.h",         # the L1 and L0 row projections that apgdl1.hip, l0.hip and fmn_sparse.hip all instantiate
            PKG / "csrc" / "direction_bits.h",      # the Philox direction bits spsa.hip and hsj.hip both regenerate
            PKG / "csrc" / "smooth_fill.h",         # the noised-slot fill that smooth.hip and smoothadv.hip both instantiate
-           PKG / "csrc" / "lcnn_wino_plan.h",      # lcnn_wino.hip's enumerators, predicates and launch plan (host side)
+           PKG / "csrc" / "fir_window.h",          # the LDS window and register-sliding tap loop that channel.hip and filter.hip both instantiate
+           PKG / "csrc" / "lcnn_wino_plan.h",     # lcnn_wino.hip's enumerators, predicates and launch plan (host side)
            ROOT / "include" / "advstep.h", ROOT / "include" / "advstep_lcnn.h", ROOT / "include" / "advstep_frontend.h",
            ROOT / "include" / "advstep_fab.h", ROOT / "include" / "advstep_dataset.h", ROOT / "include" / "advstep_detector.h",
            ROOT / "include" / "advstep_apgd.h", ROOT / "include" / "advstep_momentum.h",
@@ -37,7 +38,8 @@ HEADERS = [PKG / "csrc" / "stft_tables.inc",       # generated twiddle constants
            ROOT / "include" / "advstep_spsa.h", ROOT / "include" / "advstep_channel.h",
            ROOT / "include" / "advstep_l0.h", ROOT / "include" / "advstep_hsj.h", ROOT / "include" / "advstep_masking.h",
            ROOT / "include" / "advstep_smooth.h", ROOT / "include" / "advstep_smoothadv.h",
-           ROOT / "include" / "advstep_fmn.h", ROOT / "include" / "advstep_fmn_sparse.h"]
+           ROOT / "include" / "advstep_fmn.h", ROOT / "include" / "advstep_fmn_sparse.h",
+           ROOT / "include" / "advstep_filter.h"]
 LIB = PKG / "libadvstep.so"
 STAMP = PKG / "libadvstep.so.buildkey"   # git-ignored like the library; travels with it to the GPU box
 

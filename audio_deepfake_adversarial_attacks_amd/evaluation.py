@@ -153,6 +153,7 @@ format_perturbation = functools.partial(format_keys, prefix="perturbation", inte
                                         exclude="perturbation/misclassified/")
 format_min_radius = functools.partial(format_keys, prefix="min_radius")
 format_universal = functools.partial(format_keys, prefix="universal", integer_suffixes="_utterances")
+format_filter = functools.partial(format_keys, prefix="filter", integer_suffixes="/taps")
 format_blackbox = functools.partial(format_keys, prefix="blackbox", integer_suffixes="budget")
 format_sparse = functools.partial(format_keys, prefix="sparse", integer_suffixes=("_max", "/k"))
 format_masking = functools.partial(format_keys, prefix="masking")
@@ -248,6 +249,23 @@ class _UniversalReport(_Report):
 
     def scores(self):
         return {"universal_delta": self.delta}
+
+
+class _FilterReport(_UniversalReport):
+    """A universal FILTER (`is_filter`: torchattacks.UniversalFilter) goes through the same protocol; what it carries is taps, not
+    an additive perturbation, so the report keeps `universal_summary`'s group keys (sizes, accuracy_*, source_flipped_*), drops
+    its two `delta_*` norms and adds the `filter/*` keys of `metrics.filter_summary`; `scores["universal_delta"]` holds the taps."""
+
+    @staticmethod
+    def line(report):
+        return ", ".join(filter(None, (format_universal(report), format_filter(report))))
+
+    def finish(self, ctx):
+        out = super().finish(ctx)
+        for key in ("universal/delta_linf", "universal/delta_l2"):
+            del out[key]
+        out.update(metrics.filter_summary(self.delta))
+        return out
 
 
 class _MultiAttackReport(_Report):
@@ -440,7 +458,8 @@ def _active_reports(atk, device, seed: int, loader, n_batches: int, perturbation
                                   lambda rows, ctx: metrics.masking_summary(rows, masking.frames(ctx.samples) * 257),
                                   format_masking, width=3))
     if getattr(atk, "is_universal", False):
-        reports.append(_UniversalReport(atk, loader, device, n_batches, universal_fit, universal_load, universal_save))
+        kind = _FilterReport if getattr(atk, "is_filter", False) else _UniversalReport
+        reports.append(kind(atk, loader, device, n_batches, universal_fit, universal_load, universal_save))
     elif universal_fit is not None or universal_load is not None or universal_save is not None:
         raise ValueError("universal_fit / universal_load / universal_save need a universal attack (AttackEnum UAP*)")
     if isinstance(atk, MultiAttack):

@@ -29,6 +29,7 @@ Reference op chains replaced (see the header for line-by-line citations):
   smoothadv_fill / _loss_grad / _step  no counterpart: PGD on the smoothed detector's soft vote, torchattacks.SmoothAdvPGD
   fmn_begin / fmn_norms / fmn_step   no counterpart: Fast Minimum-Norm (Pintor et al., NeurIPS 2021), torchattacks.FMN
   fmn_sparse_step                    no counterpart: its L1 and L0 forms in one fused row launch, torchattacks.FMNSparse
+  filter_apply / _tap_grad / _tap_update  no counterpart: one adversarial FIR filter for every utterance, torchattacks.UniversalFilter
 """
 from __future__ import annotations
 
@@ -1530,6 +1531,93 @@ def channel_eot_step(adv, orig, grads, taps, shift, gain, alpha: float, eps: flo
     _call("advstep_channel_eot_step_f32", adv.device, adv, orig, grads, taps, shift, gain, out, B, T, K, L, alpha, eps, lo, hi,
           bracket="channel_eot_step", work=2.0 * K * L * B * T, tensors=(adv, orig, grads, out))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# universal adversarial filter (include/advstep_filter.h): one FIR for the batch, the gradient of its taps and their Adam step
+# ---------------------------------------------------------------------------------------------------------
+
+FILTER_MAX_TAPS = 1025                          # ADVSTEP_FILTER_MAX_TAPS
+FILTER_GROUP_ROWS = 16                          # ADVSTEP_FILTER_GROUP_ROWS: rows per group of the fold over rows
+_FILTER_TILE = 4096                             # samples of a row that one workgroup filters
+
+
+def _filter_taps(taps, device, name: str = "taps") -> int:
+    """L of a filter: `taps` holds an odd number of float32 values, 1 .. FILTER_MAX_TAPS, on `device`."""
+    _require(taps, name)
+    L = int(taps.numel())
+    if not 1 <= L <= FILTER_MAX_TAPS or L % 2 == 0:
+        raise ValueError(f"a filter has an odd number of taps between 1 and {FILTER_MAX_TAPS}, got {L}")
+    _on_device(taps, name, device)
+    return L
+
+
+def _filter_workspace(device: torch.device, B: int, T: int, L: int) -> Tuple[int, int]:
+    # the (tile, row) partials of the tap gradient, rewritten by every filter_tap_grad: keyed by stream like the row workspace
+    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(device), int(B), int(T), "filter", int(L))
+    nbytes = _lib.load().advstep_filter_workspace_bytes(B, T, L)
+    return _scratch(key, lambda: torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device))
+
+
+def filter_apply(x, center, taps, row_mask=None, lo: float = 0.0, hi: float = 1.0, out=None):
+    """out[b] = clamp(c_b + FIR(taps, x_b - c_b), lo, hi) for the rows with row_mask[b] != 0 (None: every row), x_b's bits for the
+    others: ONE centred filter of L taps (odd, <= 1025) for the batch, with silence (c = `center`, one value per row) outside the
+    utterance; include/advstep_filter.h fixes the arithmetic.  One launch, 8 B per sample, no host read.  `out` may be `x`: where
+    rows are longer than a 4096-sample tile (and L > 1) the launch cannot run in place, and the rows are filtered into a scratch
+    tensor that is then copied over `x`."""
+    _require(x, "x")
+    B, T = _rows(x, "x")
+    _per_row(center, "center", B, device=x.device)
+    L = _filter_taps(taps, x.device)
+    m = _optional_rows(row_mask, "row_mask", B, x.device)
+    out = _out_like(x, out)
+    in_place = out.data_ptr() == x.data_ptr() and T > _FILTER_TILE and L > 1
+    dst = torch.empty_like(x) if in_place else out
+    _call("advstep_filter_apply_f32", x.device, x, center, m, taps, dst, B, T, L, lo, hi,
+          bracket="filter_apply", work=2.0 * L * B * T, tensors=(x, dst))
+    if in_place:
+        out.copy_(dst)
+    return out
+
+
+def filter_tap_grad(x, center, grad, out_adv, taps: int, row_mask=None, lo: float = 0.0, hi: float = 1.0) -> None:
+    """The per-(tile, row) partials of d loss / d taps for a filter of `taps` taps, from grad = d loss / d out_adv and out_adv =
+    filter_apply(x, ...): dh[i] = sum_b sum_t gm[b, t] (x - c)[b, t + P - i], gm = grad where the row is unmasked and lo < out_adv
+    < hi, else 0.  They stay in this stream's workspace for `filter_tap_update` with the same (B, T, taps), which folds them: the
+    gradient never needs a host read.  One launch, 12 B per sample."""
+    _require(x, "x"), _require(grad, "grad"), _require(out_adv, "out_adv")
+    B, T = _rows(x, "x")
+    for name, t in (("grad", grad), ("out_adv", out_adv)):
+        if t.numel() != x.numel() or t.device != x.device:
+            raise ValueError(f"{name} must hold ({B}, {T}) values on {x.device}, got {tuple(t.shape)}@{t.device}")
+    _per_row(center, "center", B, device=x.device)
+    L = int(taps)
+    if not 1 <= L <= FILTER_MAX_TAPS or L % 2 == 0:
+        raise ValueError(f"a filter has an odd number of taps between 1 and {FILTER_MAX_TAPS}, got {L}")
+    m = _optional_rows(row_mask, "row_mask", B, x.device)
+    with _Launch("filter_tap_grad", x.device, work=2.0 * L * B * T, tensors=(x, grad, out_adv)):
+        ws, ws_bytes = _filter_workspace(x.device, B, T, L)
+        _call("advstep_filter_tap_grad_f32", x.device, x, center, m, grad, out_adv, ws, ws_bytes, B, T, L, lo, hi)
+
+
+def filter_tap_update(taps, adam_m, adam_v, B: int, T: int, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999,
+                      adam_eps: float = 1e-8, ascend: bool = True, dh_out=None):
+    """Fold the partials `filter_tap_grad` left on this stream for a (B, T) batch into dh (L,) in the order the header fixes, and
+    take one Adam step on `taps` along it, in place with its moments `adam_m`, `adam_v` (`step` is 1-based; ascend: the taps climb
+    the loss).  dh_out (L,): also receives dh.  One small launch, no host read.  Returns dh_out."""
+    L = _filter_taps(taps, taps.device)
+    for name, t in (("adam_m", adam_m), ("adam_v", adam_v)) + ((("dh_out", dh_out),) if dh_out is not None else ()):
+        _require(t, name)
+        if t.numel() != L or t.device != taps.device:
+            raise ValueError(f"{name} must hold one value per tap ({L}) on {taps.device}, got {tuple(t.shape)}@{t.device}")
+    B, T, step = int(B), int(T), int(step)
+    if B < 0 or T < 0 or step < 1:
+        raise ValueError(f"B and T must not be negative and step is 1-based, got B {B}, T {T}, step {step}")
+    with _Launch("filter_tap_update", taps.device, tensors=(taps, taps, adam_m, adam_m, adam_v, adam_v)):
+        ws, _ = _filter_workspace(taps.device, B, T, L)
+        _call("advstep_filter_tap_update_f32", taps.device, ws, taps, adam_m, adam_v, dh_out, B, T, L, step, lr, beta1, beta2,
+              adam_eps, int(bool(ascend)))
+    return dh_out
 
 
 # ---------------------------------------------------------------------------------------------------------

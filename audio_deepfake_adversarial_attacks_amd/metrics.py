@@ -252,6 +252,26 @@ def universal_summary(y, y_pred_label, fitted, delta, source_label: Optional[int
     return out
 
 
+def filter_summary(taps, n_fft: int = 4096) -> Dict[str, float]:
+    """What a universal FIR filter (torchattacks.UniversalFilter) does to a spectrum, from its taps alone: host, float64, from
+    |rfft(h, n_fft)| on n_fft / 2 + 1 frequencies between 0 and half the sampling rate.
+
+    filter/taps                        the filter's length L
+    filter/gain_db_max, gain_db_min    the largest and the smallest gain over those frequencies, 20 log10 |H| (a null: -inf)
+    filter/dc_gain_db                  the gain at frequency 0, 20 log10 |sum h|
+    filter/identity_distance           ||h - delta||_2, delta the centred unit impulse: 0 for the filter a fit starts from"""
+    h = np.asarray(taps, dtype=np.float64).ravel()
+    if h.size < 1 or h.size % 2 == 0 or h.size > n_fft:
+        raise ValueError(f"taps must hold an odd number of values, at most {n_fft}, got {h.size}")
+    mag = np.abs(np.fft.rfft(h, n_fft))
+    with np.errstate(divide="ignore"):
+        db = 20.0 * np.log10(mag)
+    impulse = np.zeros_like(h)
+    impulse[(h.size - 1) // 2] = 1.0
+    return {"filter/taps": int(h.size), "filter/gain_db_max": float(db.max()), "filter/gain_db_min": float(db.min()),
+            "filter/dc_gain_db": float(db[0]), "filter/identity_distance": float(np.sqrt(np.sum((h - impulse) ** 2)))}
+
+
 # ---------------------------------------------------------------------------------------------------------
 # black-box query report
 # ---------------------------------------------------------------------------------------------------------

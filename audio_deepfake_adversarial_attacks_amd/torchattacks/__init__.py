@@ -12,7 +12,8 @@ utterance: `MaskingModel`), and beside them `Smoothing`, which is no attack: ran
 certified lower bound on the radius the attacks bound from above, and SmoothAdvPGD (PGD on that smoothed detector's soft vote: the
 adversary the certificate has to withstand) and FMN (the minimal-norm attack: every utterance's radius in one run, without a
 largest radius and without an outer search) and FMNSparse (its L1 and L0 forms: the minimal L1 norm and the minimal number of
-changed samples), with the reference's constructor
+changed samples) and UniversalFilter (the convolutive threat model: one short FIR filter fitted once and applied to every fake,
+after Malafide), with the reference's constructor
 signatures and the reference's 1-logit -> 2-logit adapter (`cat([-z, z], 1)`)."""
 from .attack import Attack
 from .attacks.apgd import APGD
@@ -21,6 +22,7 @@ from .attacks.cw import CW
 from .attacks.eotpgd import EOTPGD
 from .attacks.fab import FAB
 from .attacks.fgsm import FGSM
+from .attacks.filter import UniversalFilter
 from .attacks.fmn import FMN
 from .attacks.fmn_sparse import FMNSparse
 from .attacks.hopskipjump import HopSkipJump
@@ -46,4 +48,4 @@ __version__ = "3.2.7+advstep"
 __all__ = ["Attack", "FGSM", "PGD", "PGDL2", "CW", "FAB", "APGD", "APGDL1", "MIFGSM", "NIFGSM", "VMIFGSM", "VNIFGSM",
            "MultiAttack", "MinRadiusPGD", "PGDSNR", "UniversalPGD", "SPSA", "EOTPGD", "Channel", "CHANNELS",
            "PGDL0", "HopSkipJump", "PsyPGD", "MaskingModel", "Smoothing", "SmoothAdvPGD", "FMN",
-           "FMNSparse"]
+           "FMNSparse", "UniversalFilter"]

@@ -78,7 +78,7 @@ def parse_arguments(argv=None):
                              "waveform the detector is given): perturbation/* keys and a second log line; with --qual also "
                              "perturbation_metrics.csv beside the WAV pairs")
     parser.add_argument("--universal_fit", type=int, default=None, metavar="N",
-                        help="universal attacks (UAP*): fit the perturbation on the first N batches of the run (default: a "
+                        help="universal attacks (UAP*, FILTER_*): fit the perturbation on the first N batches of the run (default: a "
                              "quarter of them, at least 1); every batch is then evaluated with the frozen perturbation")
     parser.add_argument("--universal_load", type=str, default=None, metavar="PATH",
                         help="universal attacks: apply the perturbation of this .npz instead of fitting one (required with "
